@@ -15,6 +15,13 @@ per-(example x probe) rates are secondary fields.
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) BEFORE anything touches the GPU; under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` the ranks already exist and the flag is
 only checked against WORLD_SIZE.
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line.  `--full` adds everything else the
+benchmark measures after the timed steps: the probe-sharded rate (N > 1), the per-kernel roofline, posterior samples/s,
+the split-precision, factor-mode and few-probe legs, ResNet-50, Lanczos, CG, evaluation, inducing-gradient, trace and
+Krylov legs, and the CPU baseline (`--samples 0`, `--no-resnet50` and `--no-cpu-baseline` trim it).
+`--dump-outputs DIR` writes what the last timed step returned as float32 `.npy` files: the whole (P, D) block if it
+fits in 32 MiB, else its first rows plus a fixed, seeded sample of its elements (at most 64 MB in all).
 """
 import argparse
 import json
@@ -106,6 +113,26 @@ def _leaves(tree):
         yield tree
 
 
+DUMP_WHOLE_BYTES = 32 << 20       # a block up to this size is written whole
+DUMP_ROWS = 4                     # else: its first rows (17 MB at D = 1 084 586) ...
+DUMP_SAMPLE = 4 << 20             # ... and this many elements at fixed, seeded positions (16 MB)
+
+
+def dump_outputs(Y, out_dir):
+    """Write the (P, D) block one timed step returned as float32 .npy files under `out_dir` (<= 64 MB in all)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    Y = Y.detach().float().contiguous()
+    if Y.numel() * 4 <= DUMP_WHOLE_BYTES:
+        np.save(os.path.join(out_dir, "ggn_vp.npy"), Y.cpu().numpy())
+        return
+    rows = min(DUMP_ROWS, Y.shape[0], max(1, (DUMP_WHOLE_BYTES // 4) // Y.shape[1]))
+    np.save(os.path.join(out_dir, "ggn_vp_rows.npy"), Y[:rows].cpu().numpy())
+    idx = np.sort(np.random.default_rng(20240901).choice(Y.numel(), size=min(DUMP_SAMPLE, Y.numel()), replace=False))
+    sample = Y.reshape(-1)[torch.from_numpy(idx).to(Y.device)]
+    np.save(os.path.join(out_dir, "ggn_vp_sample.npy"), sample.cpu().numpy())
+
+
 def spawn_ranks(n_ranks: int, argv) -> int:
     """`bench.py --gpus N` outside a launcher: start N copies of this script, one rank per GPU, and wait.  Nothing in
     this (parent) process has initialised HIP — `torch.cuda.device_count()` does not on this image — and the children
@@ -187,7 +214,14 @@ def main():
                     help="weak: --n examples per GPU (the data set grows with N); strong: ONE data set of --n-total examples "
                          "sharded over the ranks (configs[3] as written: a data batch sharded 8 ways)")
     ap.add_argument("--n-total", type=int, default=2048, help="examples of the whole data set under --scaling strong")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the secondary legs (roofline, samplers, ResNet-50, Krylov, "
+                         "CPU baseline, ...); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output block (or a fixed, seeded sample of it) as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -270,12 +304,14 @@ def main():
                     note="one all-reduce of the (P, D) float32 block per matvec, issued as 3/4 + 1/4 of the probes; the "
                          "exposed time is what the compute stream waits for after its last launch (events around the waits), "
                          "rank 0's view")
+    if args.dump_outputs and rank == 0:           # after the all-reduce every rank holds the same block
+        dump_outputs(Y, args.dump_outputs)
 
     # N > 1, secondary figure: the OTHER sharding north_star names — Hutchinson probes sharded, no data-path collective:
     # every rank sweeps its own block of P probes over a full 50-example set (the trace estimator then all-reduces P
     # scalars per rank, dist.sharded_hutchinson).  N * P products per step, each over a 50-example set.
     probe_sharded = None
-    if world > 1:
+    if world > 1 and args.full:
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -285,61 +321,63 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         probe_sharded = P * world * args.steps / float(t.item())
 
-    # ---- live per-kernel figure: HIP events on the launch stream, instrumented extra steps -------------
-    eng.profile(True)
-    prof_steps = max(1, min(3, args.steps))
-    for _ in range(prof_steps):
-        eng.ggn_vp(V, full / eng.n, alpha)
-    prof = eng.profile_read()
-    eng.profile(False)
-    # one-off primal forward of the binding (reported separately; 2 MACs_fwd FLOP per example)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(5):
-        nv.check(eng.lib.lip_engine_primal(eng.h, nv.stream_ptr()), "lip_engine_primal")
-    torch.cuda.synchronize()
-    primal_ms = 1e3 * (time.perf_counter() - t1) / 5
-    flops = eng.flops_per_probe()
-    xflops = eng.executed_flops_per_probe()        # Winograd ops multiply 4/9 as often as their algorithmic count says
-    kinds = {nv.OP_IGEMM: "igemm_kernel", nv.OP_WGRAD: "wgrad_kernel"}
-    per_kernel = {}
-    for k, name in kinds.items():
-        ms, cnt = prof.get(k, (0.0, 0))
-        if cnt:
-            per_kernel[name] = dict(ms_per_step=ms / prof_steps, launches_per_step=cnt // prof_steps,
-                                    avg_launch_ms=ms / cnt,
-                                    tflops=flops[k] * P * prof_steps / (ms * 1e-3) / 1e12,
-                                    executed_tflops=xflops[k] * P * prof_steps / (ms * 1e-3) / 1e12,
-                                    mfma_pipe_utilisation=xflops[k] * P * prof_steps / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS)
-    other_ms = sum(ms for k, (ms, c) in prof.items() if k not in kinds) / prof_steps
-    dom = "igemm_kernel"
-    achieved = per_kernel[dom]["tflops"]
-    # HBM bytes per launch are NOT measured inside this run (the PMC passes need rocprofv3 around the process): null here;
-    # the committed counter passes of this same command are profiles/r3_traffic.json (scripts/profile.sh)
-    traffic = None
-    winograd_on = bool(eng.lib.lip_get_winograd() != 0 and eng.lib.lip_get_precision() == 0)
-    roofline = dict(bound="mfma", kernel=dom + " (tangent-forward + data-gradient implicit GEMMs, f32 MFMA"
-                                         + ("; the 3x3 stride-1 layers as Winograd F(2x2,3x3)" if winograd_on else "") + ")",
-                    achieved=achieved, peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s", frac=achieved / PEAK_F32_MFMA_TFLOPS,
-                    winograd=winograd_on,
-                    executed=dict(tflops=per_kernel[dom]["executed_tflops"], frac=per_kernel[dom]["mfma_pipe_utilisation"],
-                                  whole_sweep_tflops=sum(xflops.values()) * P / (ms_per_step * 1e-3) / 1e12,
-                                  note="`achieved` / `frac` count ALGORITHMIC FLOPs (SURVEY 8d: 8 MACs_fwd per example-probe) "
-                                       "per second, so with the Winograd route on they can exceed the pipe's peak: those ops "
-                                       "issue 4/9 of their algorithmic multiplications.  `executed` counts the FLOPs the MFMA "
-                                       "instructions actually perform — its `frac` is the utilisation of the f32 matrix pipe"),
-                    traffic=traffic, per_kernel=per_kernel, other_kernels_ms_per_step=other_ms,
-                    primal_pass_ms=primal_ms, primal_pass_tflops=2 * net.macs_per_example() * n / (primal_ms * 1e-3) / 1e12,
-                    whole_sweep_tflops=sum(flops.values()) * P / (ms_per_step * 1e-3) / 1e12,
-                    flop_model="algorithmic FLOPs from the op tapes: conv segment 2*R*N*Ktot, data-gradient segment "
-                               "2*MACs of its conv, WGRAD 2*R*N*M (= 8*MACs_fwd per example-probe minus the input "
-                               "layer's two absent terms, SURVEY 8d)")
+    roofline = None
+    if args.full:
+        # ---- live per-kernel figure: HIP events on the launch stream, instrumented extra steps -------------
+        eng.profile(True)
+        prof_steps = max(1, min(3, args.steps))
+        for _ in range(prof_steps):
+            eng.ggn_vp(V, full / eng.n, alpha)
+        prof = eng.profile_read()
+        eng.profile(False)
+        # one-off primal forward of the binding (reported separately; 2 MACs_fwd FLOP per example)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(5):
+            nv.check(eng.lib.lip_engine_primal(eng.h, nv.stream_ptr()), "lip_engine_primal")
+        torch.cuda.synchronize()
+        primal_ms = 1e3 * (time.perf_counter() - t1) / 5
+        flops = eng.flops_per_probe()
+        xflops = eng.executed_flops_per_probe()        # Winograd ops multiply 4/9 as often as their algorithmic count says
+        kinds = {nv.OP_IGEMM: "igemm_kernel", nv.OP_WGRAD: "wgrad_kernel"}
+        per_kernel = {}
+        for k, name in kinds.items():
+            ms, cnt = prof.get(k, (0.0, 0))
+            if cnt:
+                per_kernel[name] = dict(ms_per_step=ms / prof_steps, launches_per_step=cnt // prof_steps,
+                                        avg_launch_ms=ms / cnt,
+                                        tflops=flops[k] * P * prof_steps / (ms * 1e-3) / 1e12,
+                                        executed_tflops=xflops[k] * P * prof_steps / (ms * 1e-3) / 1e12,
+                                        mfma_pipe_utilisation=xflops[k] * P * prof_steps / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS)
+        other_ms = sum(ms for k, (ms, c) in prof.items() if k not in kinds) / prof_steps
+        dom = "igemm_kernel"
+        achieved = per_kernel[dom]["tflops"]
+        # HBM bytes per launch are NOT measured inside this run (the PMC passes need rocprofv3 around the process): null here;
+        # the committed counter passes of this same command are profiles/r3_traffic.json (scripts/profile.sh)
+        traffic = None
+        winograd_on = bool(eng.lib.lip_get_winograd() != 0 and eng.lib.lip_get_precision() == 0)
+        roofline = dict(bound="mfma", kernel=dom + " (tangent-forward + data-gradient implicit GEMMs, f32 MFMA"
+                                             + ("; the 3x3 stride-1 layers as Winograd F(2x2,3x3)" if winograd_on else "") + ")",
+                        achieved=achieved, peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s", frac=achieved / PEAK_F32_MFMA_TFLOPS,
+                        winograd=winograd_on,
+                        executed=dict(tflops=per_kernel[dom]["executed_tflops"], frac=per_kernel[dom]["mfma_pipe_utilisation"],
+                                      whole_sweep_tflops=sum(xflops.values()) * P / (ms_per_step * 1e-3) / 1e12,
+                                      note="`achieved` / `frac` count ALGORITHMIC FLOPs (SURVEY 8d: 8 MACs_fwd per example-probe) "
+                                           "per second, so with the Winograd route on they can exceed the pipe's peak: those ops "
+                                           "issue 4/9 of their algorithmic multiplications.  `executed` counts the FLOPs the MFMA "
+                                           "instructions actually perform — its `frac` is the utilisation of the f32 matrix pipe"),
+                        traffic=traffic, per_kernel=per_kernel, other_kernels_ms_per_step=other_ms,
+                        primal_pass_ms=primal_ms, primal_pass_tflops=2 * net.macs_per_example() * n / (primal_ms * 1e-3) / 1e12,
+                        whole_sweep_tflops=sum(flops.values()) * P / (ms_per_step * 1e-3) / 1e12,
+                        flop_model="algorithmic FLOPs from the op tapes: conv segment 2*R*N*Ktot, data-gradient segment "
+                                   "2*MACs of its conv, WGRAD 2*R*N*M (= 8*MACs_fwd per example-probe minus the input "
+                                   "layer's two absent terms, SURVEY 8d)")
 
     # ---- posterior samples/s (reference algorithm src/sample.py:55-156).  N > 1: the inducing set is small, every
     # rank holds it and draws its own args.samples with its own seed (replicas, no collective); whole-job rate =
     # N * samples / slowest rank -----------
     samples_line = None
-    if args.samples > 0:
+    if args.full and args.samples > 0:
         from lip_amd.sample import sample
         st_dev = state.to(device=dev, dtype=torch.float32)
         Zd = Z.to(dev)
@@ -400,7 +438,7 @@ def main():
 
     # ---- opt-in split-precision MFMA mode (bf16x3): same workload, implicit-GEMM kernels on bf16 matrix cores ------
     split_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         from lip_amd.engine import set_precision
         Y32 = eng.ggn_vp(V, scale, alpha)
         try:
@@ -422,7 +460,7 @@ def main():
 
     # ---- opt-in materialised-factor mode (same results, two plain GEMMs; valid while d*D*4 B fits HBM) -------
     factor_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         from lip_amd.ggn import compute_ggn_vp
         st_dev = state.to(device=dev, dtype=torch.float32)
         torch.cuda.synchronize()
@@ -446,7 +484,7 @@ def main():
 
     # ---- few-probe call shape (the reference applies the operator to one vector at a time) -------------------------
     single_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         single_line = {}
         for Ps in (1, 8):
             Vs = V[:Ps].contiguous()
@@ -466,7 +504,7 @@ def main():
 
     # ---- BASELINE configs[4] slice: full-resolution ResNet-50 (25.6 M parameters, K = 1000), 8 images x 64 probes ---
     r50_line = None
-    if args.samples > 0 and not args.no_resnet50 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and not args.no_resnet50 and rank == 0 and world == 1:
         from lip_amd.scalemodels import ResNet50
         from lip_amd.toymodels import create_state as _cs50
         n50, P50 = 8, 64
@@ -556,7 +594,7 @@ def main():
 
     # ---- the north star's Krylov route: D-space Lanczos on the matrix-free GGN + alpha I (36 matvecs, full re-orth.) ----
     lanczos_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         from lip_amd.sample import sample_lanczos
         st_l = state.to(device=dev, dtype=torch.float32)
         Zl = Z.to(dev)
@@ -584,7 +622,7 @@ def main():
     # src/stochtrace.py:138-148, and any posterior-mean computation): plain float32 CG and CG with range(W) deflated
     # (krylov.RangeDeflation), at the reference's CIFAR experiments' alpha = 10 and at the config's alpha = 0.005 ----
     cg_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         from lip_amd.sample import range_deflation
         Bc = krylov.fill_normal(16, eng.D, 77, dev)
         cg_line = dict(rhs=16, tol=3e-3, maxiter=200, stall_guard_deflated=3,
@@ -616,7 +654,7 @@ def main():
 
     # ---- one evaluation batch (scale_experiments/evaluate.py:98-154 times its passes): MC predictive of 256 test images ----
     eval_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         from lip_amd.lla import predict_lla_scalable
         st_e = state.to(device=dev, dtype=torch.float32)
         Ze = Z.to(dev)
@@ -638,7 +676,7 @@ def main():
     # ---- one exact inducing-point gradient step (src/train_inducing.py:195-232) at this config: 50 inducing images,
     # a data batch of 256, factors + Gram algebra + the second-order pass (reverse over the tangent tape) on the engine --
     ipgrad_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         from lip_amd.train_inducing import variational_grad_scalable, _input_grad_of_pairing
         st_g = state.to(device=dev, dtype=torch.float32)
         Zg = Z.to(dev)
@@ -676,7 +714,7 @@ def main():
 
     # ---- trace-estimator legs, end to end (probe fill + block products + quadratic forms) ----------------------
     trace_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         from lip_amd import stochtrace
         from lip_amd.ggn import BlockOperator
         from lip_amd.scalemodels import LargeClassifier
@@ -750,7 +788,7 @@ def main():
             note="20 products for the sketch, the two quadratic forms (20 + 16 rows) from tangent sweeps")
 
     krylov_line = None
-    if args.samples > 0 and rank == 0 and world == 1:
+    if args.full and args.samples > 0 and rank == 0 and world == 1:
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         import krylov_bench
         del eng.work                                   # release the 6.7 GB probe workspace first
@@ -774,7 +812,7 @@ def main():
                                        "dot 8*D B per probe")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(net, n)
 
     if rank == 0:

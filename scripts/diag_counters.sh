@@ -5,7 +5,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/diag; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp
-ARGS="$R/bench.py --steps 2 --warmup 1 --samples 0 --no-cpu-baseline"
+ARGS="$R/bench.py --steps 2 --warmup 1 --samples 0 --no-cpu-baseline --full"
 i=0
 while read -r set; do
   i=$((i+1))

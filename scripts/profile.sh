@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp; export TMPDIR=/tmp
-ARGS="$R/bench.py --steps 5 --warmup 2 --samples 0 --no-cpu-baseline"
+ARGS="$R/bench.py --steps 5 --warmup 2 --samples 0 --no-cpu-baseline --full"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/stats" -o run -- python3 $ARGS > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
 echo "stats pass done"
 rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d "$OUT/fetch" -o run -- python3 $ARGS > /dev/null 2> "$OUT/fetch.err"
@@ -21,7 +21,7 @@ rocprofv3 --output-format csv --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MI
 echo "write pass done"
 rocprofv3 --output-format csv --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY -d "$OUT/sq" -o run -- python3 $ARGS > /dev/null 2> "$OUT/sq.err"
 echo "sq pass done"
-FULL="$R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-resnet50"
+FULL="$R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-resnet50 --full"
 rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/full" -o run -- python3 $FULL > "$OUT/bench_full_under_rocprof.json" 2> "$OUT/full.err"
 echo "full stats pass done"
 K="$R/scripts/krylov_bench.py"

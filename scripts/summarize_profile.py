@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Condense a gpurun_out/prof_rN directory (rocprofv3 csv output of `bench.py --steps 5 --warmup 2
---samples 0 --no-cpu-baseline`) into the small files committed under profiles/:
+--samples 0 --no-cpu-baseline --full`) into the small files committed under profiles/:
   rN_kernel_stats.csv      rocprofv3 --kernel-trace --stats summary (verbatim)
   rN_traffic.json          per-kernel HBM bytes per launch from the separate --pmc passes
                            (FETCH_SIZE x 2 on gfx950, MI355X_MICROARCH.md §HBM; WRITE_SIZE as is; KiB units)
@@ -47,7 +47,7 @@ for k in fetch:
     traffic[k] = dict(launches=n, avg_launch_ms=1e3 * f[1] / n, hbm_read_bytes_per_launch=rd,
                       hbm_write_bytes_per_launch=wr, hbm_bytes_per_launch=rd + wr,
                       hbm_tb_per_s=(rd + wr) / (f[1] / n) / 1e12, l2_hit_rate=h / max(h + m, 1.0))
-what = sys.argv[3] if len(sys.argv) > 3 else "python bench.py --steps 5 --warmup 2 --samples 0 --no-cpu-baseline"
+what = sys.argv[3] if len(sys.argv) > 3 else "python bench.py --steps 5 --warmup 2 --samples 0 --no-cpu-baseline --full"
 json.dump(dict(command="rocprofv3 --kernel-trace --pmc FETCH_SIZE  /  --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum  -- " + what,
                correction="read bytes = 2 x FETCH_SIZE (gfx950 counts 128-B requests as 64 B); KiB -> bytes",
                kernels=traffic), open(f"profiles/{tag}_traffic.json", "w"), indent=1)

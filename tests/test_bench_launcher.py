@@ -41,6 +41,31 @@ def test_failing_rank_fails_the_launch():
     assert r.returncode not in (0, 2)
 
 
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps, runs none of the --full legs, and --dump-outputs writes the last step's
+    block: its first rows and a seeded sample of its elements once the block exceeds 32 MiB (8 x D floats here)."""
+    import numpy as np
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--probes", "8",
+                        "--dump-outputs", str(tmp_path)], env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["dtype"] == "f32" and line["unit"] == "GGN-vp/s" and line["higher_is_better"]
+    assert abs(line["value"] - 8 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["posterior_samples"] is None
+    rows, sample = np.load(tmp_path / "ggn_vp_rows.npy"), np.load(tmp_path / "ggn_vp_sample.npy")
+    assert rows.dtype == np.float32 and rows.shape == (4, line["config"]["D"]) and np.isfinite(rows).all()
+    assert sample.dtype == np.float32 and sample.shape == (4 << 20,) and np.isfinite(sample).all()
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
+    # half of the block's elements: their mean magnitude is the whole block's (the line's checksum) to well under 1 %
+    assert abs(np.abs(sample).mean(dtype=np.float64) / line["checksum"] - 1) < 1e-2
+
+
 @pytest.mark.gpu
 def test_two_rank_rehearsal_on_one_card():
     """`python bench.py --gpus 2` starts its own two ranks (gloo collectives, both on the one card of the box) and
