@@ -111,7 +111,7 @@ typedef struct {
 typedef struct lip_engine lip_engine_t;
 
 /* ---- library ----------------------------------------------------------------------- */
-int lip_abi_version(void);                 /* bumps when this header changes                     */
+int lip_abi_version(void);                 /* bumps on incompatible changes of this header (added entry points keep it) */
 const char* lip_last_error(void);          /* text of the last failure on this thread            */
 int lip_sizeof_op(void);                   /* sizeof(lip_op_t): lets the ctypes mirror self-check */
 /* arithmetic of the MFMA kernels (process-wide): 0 = exact f32 MFMA (default, dtype "f32");
@@ -171,6 +171,18 @@ int lip_vjp(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t head_m
  * crosses examples, so a probe that holds e_k on every example yields the n rows J_i^T L_i e_k of the GGN's
  * square-root factor in ONE sweep (the reference builds them column by column: src/ggn.py:64-93, 207-219) */
 int lip_vjp_rows(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t head_mode, float c, void* stream);
+/* Square sum of those rows, ADDED into Y (D,):
+ *   Y[j] += sum_p sum_i ( J_i^T (c * L_i U[p,i,:]) )_j^2   (LIP_HEAD_L)   or   sum_p sum_i ( J_i^T U[p,i,:] )_j^2  (LIP_HEAD_IN)
+ * without the (P n, D) rows: every per-(probe, example) parameter cotangent is squared where it is formed.  With
+ * U[p,i,:] = e_p (P = K one-hot probes on every example) and c = 1 this is the GGN diagonal before the N/M (and
+ * exp(-logvar)) factor.  Y accumulates, so probe and example chunks add up; the result is bitwise reproducible (no
+ * float atomics).  `scratch` (device, caller-owned) holds >= lip_vjp_sqsum_scratch(e, P) floats; a bad head mode, a
+ * null pointer or too small a scratch returns LIP_ERR_ARG and leaves Y untouched.                              */
+int lip_vjp_sqsum(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t head_mode, float c, float* scratch,
+                  int64_t scratch_floats, void* stream);
+/* scratch floats lip_vjp_sqsum needs for P probes on this engine's binding; bounded by the tape geometry (independent
+ * of the example count and of P beyond a fixed group bound) and never more than for P = the bound chunk size      */
+int lip_vjp_sqsum_scratch(lip_engine_t* e, int32_t P, int64_t* floats);
 
 /* ---- Krylov / trace primitives on blocks of vectors: X is (P, N) row-major -----------
  * They replace what XLA emits for matfree's tridiag_sym (called at src/sample.py:114-126),

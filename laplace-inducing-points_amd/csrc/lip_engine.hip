@@ -57,6 +57,11 @@ struct RunCtx {
   float head_c;
   hipStream_t st;
   bool rows = false;   // lip_vjp_rows: Y holds one row per (probe, example); no reduction crosses examples
+  // lip_vjp_sqsum: Y is ONE (D,) vector; every parameter cotangent is formed per (probe, example) as in `rows`, squared
+  // and summed into Y by the square-accumulating kernels (weight gradients, bias / BN reductions); `scratch` is theirs
+  bool sqsum = false;
+  float* scratch = nullptr;
+  long long scratch_floats = 0;
   // summed products (lip_ggn_vp / lip_vjp): a weight gradient that reduces all rows in one block may WRITE
   // y = s acc + alpha v instead of adding to an initialised block (the initialisation then skips its parameters)
   bool fuse = false;
@@ -87,6 +92,7 @@ struct RowReds { float* red0; float* red1; const float* xhat; };
   } while (0)
 
 // Segmented (per-example) parameter reductions of lip_vjp_rows, taken over an op's output tensor [P][n][rows][N].
+// lip_vjp_sqsum (c.sqsum): the same per-example sums, squared and summed over examples and probes into the (D,) output.
 int rows_reduce(const RunCtx& c, const float* out, long long out_ps, int n_img, int rows, int N, const float* xhat,
                 float* red0, long long red0_ps, float* red1, long long red1_ps) {
   if (!red0 && !red1) return LIP_OK;
@@ -97,6 +103,11 @@ int rows_reduce(const RunCtx& c, const float* out, long long out_ps, int n_img, 
   r.nseg = n_img; r.red_seg = red0 ? red0_ps : red1_ps;
   r.red0_ps = red0_ps * n_img; r.red1_ps = red1_ps * n_img;
   if (N <= 0 || N > 8192 || (red1 && !xhat)) { set_error("per-example reduce: bad operands"); return LIP_ERR_ARG; }
+  if (c.sqsum) {
+    if (reduce_sqsum_scratch(N, (long long)c.P * n_img) > c.scratch_floats) { set_error("square-sum reduce: scratch too small"); return LIP_ERR_ARG; }
+    RUN_CHECK(launch_reduce_sqsum(r, c.P, c.scratch, c.scratch_floats, c.st), "square-sum reduce launch");
+    return LIP_OK;
+  }
   RUN_CHECK(launch_reduce(r, c.P, c.st), "per-example reduce launch");
   return LIP_OK;
 }
@@ -124,6 +135,8 @@ int make_wgrad(const RunCtx& c, const lip_op_t& op, WgradP& p) {
   p.ksplit = op.ksplit > 0 ? op.ksplit : 0;           // 0: the launcher picks the row split for the probe count
   if (c.rows) {
     p.ksplit = op.n_img; p.seg_rows = p.OHW; p.seg_ys = p.y_ps; p.y_ps *= op.n_img;
+  } else if (c.sqsum) {
+    p.ksplit = 1; p.seg_rows = p.OHW; p.seg_ys = 0;     // per-example row geometry; launch_wgrad_sqsum walks the examples
   }
   if (!p.a || !p.g || !p.y || p.R <= 0 || p.N <= 0 || p.M <= 0) { set_error("WGRAD: bad operands"); return LIP_ERR_ARG; }
   if ((long long)p.R * p.N >= (1ll << 31) || (long long)op.n_img * p.IH * p.IW * p.C >= (1ll << 31) || (long long)p.M * p.N >= (1ll << 31)) {
@@ -131,7 +144,7 @@ int make_wgrad(const RunCtx& c, const lip_op_t& op, WgradP& p) {
     return LIP_ERR_ARG;
   }
   if ((p.C & 3) == 0 && (((uintptr_t)p.a) & 15)) { set_error("WGRAD: activations not 16-byte aligned"); return LIP_ERR_ARG; }
-  if (c.fuse && !c.rows && op.out.space == LIP_SP_YOUT && wgrad_will_overwrite(p, c.P)) {
+  if (c.fuse && !c.rows && !c.sqsum && op.out.space == LIP_SP_YOUT && wgrad_will_overwrite(p, c.P)) {
     p.overwrite = 1;
     p.v = c.V ? c.V + op.out.off : nullptr; p.v_ps = op.out.pstride; p.alpha = c.alpha;
   }
@@ -185,7 +198,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       }
       if (p.e1 && !p.xhat) { set_error("IGEMM: e1 without xhat"); return LIP_ERR_ARG; }
       if (p.red1 && !p.xhat2) { set_error("IGEMM: red1 without xhat2"); return LIP_ERR_ARG; }
-      if (c.rows && (p.red0 || p.red1)) {
+      if ((c.rows || c.sqsum) && (p.red0 || p.red1)) {
         float* r0 = p.red0; float* r1 = p.red1;
         p.red0 = nullptr; p.red1 = nullptr;
         RUN_CHECK(launch_igemm(p, c.P, c.st), "igemm launch");
@@ -198,6 +211,11 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       WgradP p;
       const int rc = make_wgrad(c, op, p);
       if (rc) return rc;
+      if (c.sqsum) {
+        if (wgrad_sqsum_scratch(p.M, p.N, p.OHW, (long long)c.P * op.n_img) > c.scratch_floats) { set_error("square-sum WGRAD: scratch too small"); return LIP_ERR_ARG; }
+        RUN_CHECK(launch_wgrad_sqsum(p, c.P, op.n_img, c.scratch, c.scratch_floats, c.st), "square-sum wgrad launch");
+        return LIP_OK;
+      }
       RUN_CHECK(launch_wgrad(p, c.P, c.st), "wgrad launch");
       return LIP_OK;
     }
@@ -210,9 +228,14 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       p.red0 = resolve(c, op.red0); p.red0_ps = op.red0.pstride;
       p.red1 = resolve(c, op.red1); p.red1_ps = op.red1.pstride;
       if (!p.g || p.N <= 0 || p.N > 8192 || (p.red1 && !p.xhat)) { set_error("REDUCE: bad operands"); return LIP_ERR_ARG; }
-      if (c.rows) {
+      if (c.rows || c.sqsum) {
         p.R = op.OH * op.OW; p.nseg = op.n_img; p.red_seg = p.red0 ? p.red0_ps : p.red1_ps;
         p.red0_ps *= op.n_img; p.red1_ps *= op.n_img;
+      }
+      if (c.sqsum) {
+        if (reduce_sqsum_scratch(p.N, (long long)c.P * op.n_img) > c.scratch_floats) { set_error("square-sum REDUCE: scratch too small"); return LIP_ERR_ARG; }
+        RUN_CHECK(launch_reduce_sqsum(p, c.P, c.scratch, c.scratch_floats, c.st), "square-sum reduce launch");
+        return LIP_OK;
       }
       RUN_CHECK(launch_reduce(p, c.P, c.st), "reduce launch");
       return LIP_OK;
@@ -230,7 +253,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       p.red1 = resolve(c, op.red1); p.red1_ps = op.red1.pstride;
       if (!p.in || !p.out || p.C <= 0 || p.C > 8192 || (p.red1 && !p.xhat)) { set_error("POOL: bad operands"); return LIP_ERR_ARG; }
       if (op.kind == LIP_OP_POOL_FWD) RUN_CHECK(launch_pool_fwd(p, c.P, c.st), "pool_fwd launch");
-      else if (c.rows && (p.red0 || p.red1)) {
+      else if ((c.rows || c.sqsum) && (p.red0 || p.red1)) {
         float* r0 = p.red0; float* r1 = p.red1;
         p.red0 = nullptr; p.red1 = nullptr;
         RUN_CHECK(launch_pool_bwd(p, c.P, c.st), "pool_bwd launch");
@@ -257,7 +280,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       if (!p.in || !p.out || p.C <= 0 || p.C > 8192 || p.stride <= 0 || (p.red1 && !p.xhat)) { set_error("MAXPOOL: bad operands"); return LIP_ERR_ARG; }
       if (op.kind == LIP_OP_MAXPOOL_PRIMAL) RUN_CHECK(launch_maxpool_primal(p, c.st), "maxpool_primal launch");
       else if (op.kind == LIP_OP_MAXPOOL_FWD) RUN_CHECK(launch_maxpool_fwd(p, c.P, c.st), "maxpool_fwd launch");
-      else if (c.rows && (p.red0 || p.red1)) {
+      else if ((c.rows || c.sqsum) && (p.red0 || p.red1)) {
         float* r0 = p.red0; float* r1 = p.red1;
         p.red0 = nullptr; p.red1 = nullptr;
         RUN_CHECK(launch_maxpool_bwd(p, c.P, c.st), "maxpool_bwd launch");
@@ -379,6 +402,30 @@ int ready(const lip_engine* e, const char* who) {
   return LIP_OK;
 }
 
+// Probes per pass when P exceeds the workspace: equal passes (256 probes on an 85-probe workspace run 4 x 64, not
+// 85 + 85 + 85 + 1 — a one-probe pass costs 2 ms of under-filled launches, a quarter of a 64-probe pass)
+inline int balanced_chunk(int P, int max_chunk) {
+  const int passes = (P + max_chunk - 1) / max_chunk;
+  return (P + passes - 1) / passes;
+}
+
+// scratch floats of lip_vjp_sqsum on passes of pc probes: the largest need of one backward op (ops run in stream order
+// and reuse it).  Depends on the tape geometry only — bounded by the target grid, not by n or the probe count.
+int64_t sqsum_scratch(const lip_engine* e, int pc) {
+  int64_t need = 0;
+  for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
+    const long long pairs = (long long)pc * op.n_img;
+    int64_t k = 0;
+    if (op.kind == LIP_OP_WGRAD)
+      k = wgrad_sqsum_scratch(op.seg[0].KH * op.seg[0].KW * op.seg[0].C, op.N, op.OH * op.OW, pairs);
+    else if ((op.kind == LIP_OP_IGEMM || op.kind == LIP_OP_REDUCE || op.kind == LIP_OP_POOL_BWD || op.kind == LIP_OP_MAXPOOL_BWD) &&
+             (op.red0.space != LIP_SP_NONE || op.red1.space != LIP_SP_NONE))
+      k = reduce_sqsum_scratch(op.N, pairs);
+    need = std::max(need, k);
+  }
+  return need;
+}
+
 }  // namespace
 
 extern "C" {
@@ -483,13 +530,6 @@ int lip_debug_run_ops(lip_engine_t* e, int32_t which, int32_t first, int32_t cou
   return LIP_OK;
 }
 
-// Probes per pass when P exceeds the workspace: equal passes (256 probes on an 85-probe workspace run 4 x 64, not
-// 85 + 85 + 85 + 1 — a one-probe pass costs 2 ms of under-filled launches, a quarter of a 64-probe pass)
-static inline int balanced_chunk(int P, int max_chunk) {
-  const int passes = (P + max_chunk - 1) / max_chunk;
-  return (P + passes - 1) / passes;
-}
-
 int lip_ggn_vp(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale, float alpha, void* stream) {
   int rc = ready(e, "lip_ggn_vp");
   if (rc) return rc;
@@ -549,6 +589,38 @@ int lip_vjp_rows(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t h
     float* y = Y + (int64_t)c0 * ystride;
     RUN_CHECK(hipMemsetAsync(y, 0, sizeof(float) * (size_t)pc * ystride, st), "memset Y");
     RunCtx c{e, nullptr, y, const_cast<float*>(U) + (int64_t)c0 * hstride, pc, head_mode, cc, st, true};
+    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, false))) return rc;
+  }
+  return LIP_OK;
+}
+
+int lip_vjp_sqsum_scratch(lip_engine_t* e, int32_t P, int64_t* floats) {
+  if (!e || !floats || P <= 0) { set_error("lip_vjp_sqsum_scratch: bad argument"); return LIP_ERR_ARG; }
+  if (e->tape[LIP_TAPE_BACKWARD].empty()) { set_error("lip_vjp_sqsum_scratch: backward tape missing"); return LIP_ERR_STATE; }
+  *floats = sqsum_scratch(e, e->max_chunk > 0 ? balanced_chunk(P, e->max_chunk) : P);
+  return LIP_OK;
+}
+
+int lip_vjp_sqsum(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t head_mode, float cc, float* scratch,
+                  int64_t scratch_floats, void* stream) {
+  int rc = ready(e, "lip_vjp_sqsum");
+  if (rc) return rc;
+  if (!U || !Y || P <= 0 || (head_mode != LIP_HEAD_L && head_mode != LIP_HEAD_IN) || scratch_floats < 0) {
+    set_error("lip_vjp_sqsum: bad argument");
+    return LIP_ERR_ARG;
+  }
+  const int step = balanced_chunk(P, e->max_chunk);
+  const int64_t need = sqsum_scratch(e, step);
+  if (scratch_floats < need || (need > 0 && !scratch)) {
+    set_error("lip_vjp_sqsum: scratch of %lld floats, %lld needed (lip_vjp_sqsum_scratch)", (long long)scratch_floats, (long long)need);
+    return LIP_ERR_ARG;
+  }
+  const int64_t hstride = (int64_t)e->n_img * e->K;
+  hipStream_t st = (hipStream_t)stream;
+  for (int c0 = 0; c0 < P; c0 += step) {
+    const int pc = (P - c0) < step ? (P - c0) : step;
+    RunCtx c{e, nullptr, Y, const_cast<float*>(U) + (int64_t)c0 * hstride, pc, head_mode, cc, st};
+    c.sqsum = true; c.scratch = scratch; c.scratch_floats = scratch_floats;
     if ((rc = run_tape(c, LIP_TAPE_BACKWARD, false))) return rc;
   }
   return LIP_OK;

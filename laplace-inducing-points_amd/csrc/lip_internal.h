@@ -156,6 +156,23 @@ hipError_t launch_scale_copy_range(float* y, const float* x, float a, long long 
 // true when launch_wgrad(p, P) will run the one-block-per-tile kernel that honours WgradP::overwrite
 bool wgrad_will_overwrite(const WgradP& p, int P);
 
+// ---- square-accumulating reductions of lip_vjp_sqsum ----------------------------------------
+// y[j] += sum_{p < P} sum_{i < n} (per-(probe, example) partial product)_j^2, no (P, n, .) intermediate and no float
+// atomics: a block owns one output tile and a fixed group of (probe, example) pairs and writes one partial per group;
+// sqsum_finish adds the partials to y in group order.  A launch of one group adds into y directly.
+// Scratch: the caller's, `*_sqsum_scratch` floats (0 when the launch needs none); bounded by the target grid
+// (SQ_TARGET_BLOCKS), independent of n and of the probe count.
+constexpr int SQ_TARGET_BLOCKS = 512;                  // 2 blocks per CU on the 256 CUs of an MI355X
+// weight gradient (p as built for the per-example rows, p.seg_rows = OH*OW): the MFMA kernel per (probe, example)
+// tile, or, when OH*OW == 1, the rank-1 route  y[m][c] += sum_i a_i[m]^2 sum_p (s[c] g_pi[c])^2
+long long wgrad_sqsum_scratch(int M, int N, int OHW, long long pairs);
+hipError_t launch_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch, long long scratch_floats, hipStream_t st);
+// bias / BN cotangents: p.R rows per (probe, example) segment, p.nseg = n; red0 / red1 point into the (D,) output
+long long reduce_sqsum_scratch(int N, long long pairs);
+hipError_t launch_reduce_sqsum(const ReduceP& p, int P, float* scratch, long long scratch_floats, hipStream_t st);
+// y[j] += sum_{g < G} partial[g * len + j], g ascending
+hipError_t launch_sqsum_finish(const float* partial, int G, long long len, float* y, hipStream_t st);
+
 void set_error(const char* fmt, ...);
 int precision_mode();
 void set_precision_mode(int m);

@@ -3221,4 +3221,304 @@ hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st) {
   return small_m ? run_wgrad<2, 1, 1, 1>(p, P, st) : run_wgrad<4, 1, 1, 1>(p, P, st);
 }
 
+
+// ------------------------------------------------------------------------------------------
+// square-accumulating per-example weight gradient (lip_vjp_sqsum):
+//   y[m][c] += sum_{(p, i) in the block's group} ( s[c] * sum_{pix of example i} im2col(a_i)[pix][m] g_pi[pix][c] )^2
+// Operands and row geometry of the per-example (seg_rows) path of wgrad_kernel: the K loop of a pair covers the
+// OH*OW rows of example i only.  After each pair the M x N tile is scaled, squared in registers and added to a
+// second register set; the MFMA accumulators are then cleared for the next pair.  grid = (output tiles, groups):
+// block (t, g) takes pairs [g*per, (g+1)*per) in order and stores one partial per group (plain stores, no atomics);
+// sqsum_finish adds the partials in group order, so the result is bitwise reproducible.  f32 MFMA in every
+// precision mode.
+// ------------------------------------------------------------------------------------------
+struct SqGroupP {
+  float* partial;                       // [groups][M*N], or null: one group, add into y
+  int pairs, per, n_img;
+};
+
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(WM * WN * 64) void wgrad_sqsum_kernel(const WgradP prm, const SqGroupP sq) {
+  using T = Tile<WM, WN, TM, TN>;
+  constexpr int NT = T::NT, BM = T::BM, BN = T::BN, AE = T::AE, AQ = T::AQ, BE = T::BE;
+  constexpr int LDA = BM + 4, LDB = BN;
+  constexpr int QPR = BM / 4;
+  __shared__ __attribute__((aligned(16))) float As[BK * LDA];
+  __shared__ float Bs[BK * LDB];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int N = prm.N, M = prm.M;
+  const int tiles_n = (N + BN - 1) / BN;
+  const int tile_n = blockIdx.x % tiles_n, tile_m = blockIdx.x / tiles_n;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const int grp = blockIdx.y;
+  const int q0 = grp * sq.per, q1 = min(sq.pairs, q0 + sq.per);
+  const int l31 = lane & 31, lh = lane >> 5;
+
+  f32x16 acc[TM][TN], ssq[TM][TN];
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ssq[tm][tn][r] = 0.f;
+  float scv[TN];
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) {
+    const int col = n0 + (wn * TN + tn) * 32 + l31;
+    scv[tn] = (prm.scale && col < N) ? prm.scale[col] : 1.f;
+  }
+
+  const bool vec = (prm.C & 3) == 0;
+  const int my_m = vec ? (m0 + 4 * (tid % QPR)) : (m0 + (tid % BM));
+  int kh = 0, kw = 0, ci = 0;
+  const bool mvalid = my_m < M;
+  if (mvalid) {
+    const int tap = my_m / prm.C;
+    ci = my_m - tap * prm.C;
+    kh = tap / prm.KW;
+    kw = tap - kh * prm.KW;
+  }
+
+  float areg[AE], breg[BE];
+  const float* gbase = prm.g;
+  int rend = 0;
+
+  auto load_tile = [&](int rk0) {
+    if (vec) {
+#pragma unroll
+      for (int j = 0; j < AQ; ++j) {
+        const int k = (tid + j * NT) / QPR;
+        const int r = rk0 + k;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (mvalid && r < rend) {
+          const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
+          const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
+          const int ih = oh * prm.stride + kh - prm.pad_h, iw = ow * prm.stride + kw - prm.pad_w;
+          if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW)
+            v = *reinterpret_cast<const float4*>(prm.a + (unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + ci));
+        }
+        areg[4 * j + 0] = v.x; areg[4 * j + 1] = v.y; areg[4 * j + 2] = v.z; areg[4 * j + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < AE; ++j) {
+        const int k = (tid + j * NT) / BM;
+        const int r = rk0 + k;
+        float v = 0.f;
+        if (mvalid && r < rend) {
+          const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
+          const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
+          const int ih = oh * prm.stride + kh - prm.pad_h, iw = ow * prm.stride + kw - prm.pad_w;
+          if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW)
+            v = prm.a[(unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + ci)];
+        }
+        areg[j] = v;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BE; ++j) {
+      const int e = tid + j * NT;
+      const int k = e / BN, nn = e - k * BN;
+      const int r = rk0 + k, col = n0 + nn;
+      breg[j] = (e < BN * BK && r < rend && col < N) ? gbase[(unsigned)(r * N + col)] : 0.f;
+    }
+  };
+
+  auto store_tile = [&]() {
+    if (vec) {
+#pragma unroll
+      for (int j = 0; j < AQ; ++j) {
+        const int q = tid + j * NT;
+        const int k = q / QPR, mq = q - k * QPR;
+        *reinterpret_cast<float4*>(&As[k * LDA + 4 * mq]) =
+            make_float4(areg[4 * j + 0], areg[4 * j + 1], areg[4 * j + 2], areg[4 * j + 3]);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < AE; ++j) {
+        const int e = tid + j * NT;
+        const int k = e / BM, mm = e - k * BM;
+        As[k * LDA + mm] = areg[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BE; ++j) {
+      const int e = tid + j * NT;
+      if (e >= BN * BK) continue;
+      const int k = e / BN, nn = e - k * BN;
+      Bs[k * LDB + nn] = breg[j];
+    }
+  };
+
+  for (int q = q0; q < q1; ++q) {
+    const int p = q / sq.n_img, i = q - p * sq.n_img;
+    const int rbeg = i * prm.OHW;
+    rend = rbeg + prm.OHW;
+    gbase = prm.g + (long long)p * prm.g_ps;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+    int rk = rbeg;
+    load_tile(rk);
+    while (true) {
+      __syncthreads();                  // (also orders the previous pair's last sweep before these LDS stores)
+      store_tile();
+      __syncthreads();
+      rk += BK;
+      const bool more = rk < rend;
+      if (more) load_tile(rk);
+      mfma_sweep<WM, WN, TM, TN, LDA, LDB>(As, Bs, acc, wm, wn, lane);
+      if (!more) break;
+    }
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = acc[tm][tn][r] * scv[tn];
+          ssq[tm][tn][r] = fmaf(v, v, ssq[tm][tn][r]);
+        }
+  }
+
+  const long long MN = (long long)M * N;
+  float* out = sq.partial ? sq.partial + (long long)grp * MN : prm.y;
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) {
+    const int col = n0 + (wn * TN + tn) * 32 + l31;
+    if (col >= N) continue;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+      const int mb = m0 + (wm * TM + tm) * 32 + 4 * lh;
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int m = mb + (reg & 3) + 8 * (reg >> 2);
+        if (m >= M) continue;
+        const long long idx = (long long)m * N + col;
+        out[idx] = sq.partial ? ssq[tm][tn][reg] : out[idx] + ssq[tm][tn][reg];
+      }
+    }
+  }
+}
+
+// Dense weight gradients (OH*OW == 1): the per-example gradient is the outer product of the im2col row a_i (M) and
+// s * g_pi (N), so  sum_{p,i} (a_i[m] s[c] g_pi[c])^2 = sum_i a_i[m]^2 * b_i[c],  b_i[c] = sum_p (s[c] g_pi[c])^2 —
+// one GEMM of depth n on squared operands instead of n*P rank-1 tiles.  Block: 32 x 64 outputs, 8 per thread; per
+// example the block forms b_i of its 64 columns (probes summed in order) and a_i^2 of its 32 rows in LDS.
+__global__ __launch_bounds__(256) void wgrad_sqsum_dense_kernel(const WgradP prm, int P, int n_img) {
+  __shared__ float As2[32], Bs2[64];
+  const int tid = threadIdx.x, cl = tid & 63, mr = tid >> 6;
+  const int N = prm.N, M = prm.M;
+  const int c0 = blockIdx.x * 64, m0 = blockIdx.y * 32;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  // this thread's share of the operand formation: column c0 + tid (tid < 64) or row m0 + tid - 64 (64 <= tid < 96)
+  const int bc = c0 + tid;
+  const float sc = (tid < 64 && bc < N && prm.scale) ? prm.scale[bc] : 1.f;
+  const int am = m0 + tid - 64;
+  long long aoff = -1;                  // offset of a_i[am] within example i's activations (-1: padding / out of range)
+  if (tid >= 64 && tid < 96 && am < M) {
+    const int tap = am / prm.C, ci = am - tap * prm.C;
+    const int kh = tap / prm.KW, kw = tap - kh * prm.KW;
+    const int ih = kh - prm.pad_h, iw = kw - prm.pad_w;
+    if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW) aoff = ((long long)ih * prm.IW + iw) * prm.C + ci;
+  }
+  const long long img = (long long)prm.IH * prm.IW * prm.C;
+  for (int i = 0; i < n_img; ++i) {
+    if (tid < 64) {
+      float b = 0.f;
+      if (bc < N)
+        for (int p = 0; p < P; ++p) {
+          const float v = prm.g[(long long)p * prm.g_ps + (long long)i * N + bc] * sc;
+          b = fmaf(v, v, b);
+        }
+      Bs2[tid] = b;
+    } else if (tid < 96) {
+      const float v = aoff >= 0 ? prm.a[(long long)i * img + aoff] : 0.f;
+      As2[tid - 64] = v * v;
+    }
+    __syncthreads();
+    const float b = Bs2[cl];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = fmaf(As2[mr + 4 * j], b, acc[j]);
+    __syncthreads();
+  }
+  const int col = c0 + cl;
+  if (col >= N) return;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int m = m0 + mr + 4 * j;
+    if (m < M) prm.y[(long long)m * N + col] += acc[j];
+  }
+}
+
+static void sq_tile(int M, int N, int& BM, int& BN) {
+  const bool small_m = M <= 64;
+  if (N > 64) { BM = small_m ? 64 : 128; BN = 128; }
+  else if (N > 32) { BM = small_m ? 64 : 128; BN = 64; }
+  else { BM = small_m ? 64 : 128; BN = 32; }
+}
+
+// groups of (probe, example) pairs for a launch of `blocks_per_group` blocks per group: fill SQ_TARGET_BLOCKS.
+// Returns the group bound min(pairs, ceil(SQ_TARGET_BLOCKS / blocks)) — monotone in `pairs`, so the scratch sized for
+// the largest pass serves every smaller one — and the launch's G <= bound after rounding to whole groups.
+static long long sq_groups(long long blocks_per_group, long long pairs, int& G, int& per) {
+  long long g = (SQ_TARGET_BLOCKS + blocks_per_group - 1) / blocks_per_group;
+  if (g > pairs) g = pairs;
+  if (g < 1) g = 1;
+  per = (int)((pairs + g - 1) / g);
+  G = (int)((pairs + per - 1) / per);
+  return g;
+}
+
+long long wgrad_sqsum_scratch(int M, int N, int OHW, long long pairs) {
+  if (OHW == 1 || M <= 0 || N <= 0 || pairs <= 0) return 0;
+  int BM, BN, G, per;
+  sq_tile(M, N, BM, BN);
+  const long long bound = sq_groups((long long)((M + BM - 1) / BM) * ((N + BN - 1) / BN), pairs, G, per);
+  return bound > 1 ? bound * M * N : 0;
+}
+
+template <int WM, int WN, int TM, int TN>
+static hipError_t run_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch, long long scratch_floats, hipStream_t st) {
+  using T = Tile<WM, WN, TM, TN>;
+  const long long tiles = (long long)((p.M + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN);
+  const long long pairs = (long long)P * n_img;
+  int G, per;
+  sq_groups(tiles, pairs, G, per);
+  SqGroupP sq;
+  sq.pairs = (int)pairs; sq.per = per; sq.n_img = n_img;
+  sq.partial = nullptr;
+  const long long need = G > 1 ? (long long)G * p.M * p.N : 0;
+  if (need > scratch_floats || (need && !scratch)) return hipErrorInvalidValue;
+  if (G > 1) sq.partial = scratch;
+  hipLaunchKernelGGL((wgrad_sqsum_kernel<WM, WN, TM, TN>), dim3((unsigned)tiles, (unsigned)G), dim3(T::NT), 0, st, p, sq);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || G == 1) return e;
+  return launch_sqsum_finish(scratch, G, (long long)p.M * p.N, p.y, st);
+}
+
+hipError_t launch_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch, long long scratch_floats, hipStream_t st) {
+  if (P <= 0 || n_img <= 0 || p.OHW * n_img != p.R || (long long)P * n_img >= (1ll << 31)) return hipErrorInvalidValue;
+  if (p.OHW == 1) {
+    dim3 grid((unsigned)((p.N + 63) / 64), (unsigned)((p.M + 31) / 32));
+    hipLaunchKernelGGL(wgrad_sqsum_dense_kernel, grid, dim3(256), 0, st, p, P, n_img);
+    return hipGetLastError();
+  }
+  // ((C & 3) == 0 reads the activations as float4: the engine checked their 16-byte alignment)
+  const bool small_m = p.M <= 64;
+  if (p.N > 64) return small_m ? run_wgrad_sqsum<2, 2, 1, 2>(p, P, n_img, scratch, scratch_floats, st)
+                               : run_wgrad_sqsum<2, 2, 2, 2>(p, P, n_img, scratch, scratch_floats, st);
+  if (p.N > 32) return small_m ? run_wgrad_sqsum<2, 2, 1, 1>(p, P, n_img, scratch, scratch_floats, st)
+                               : run_wgrad_sqsum<4, 1, 1, 2>(p, P, n_img, scratch, scratch_floats, st);
+  return small_m ? run_wgrad_sqsum<2, 1, 1, 1>(p, P, n_img, scratch, scratch_floats, st)
+                 : run_wgrad_sqsum<4, 1, 1, 1>(p, P, n_img, scratch, scratch_floats, st);
+}
+
 }  // namespace lip

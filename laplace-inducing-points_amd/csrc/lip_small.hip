@@ -77,6 +77,119 @@ hipError_t launch_reduce(const ReduceP& p0, int P, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---- square-accumulating segmented reduce (lip_vjp_sqsum) ----------------------------------------------------------
+//   red0[c] += sum_{(p, i)} (sum_{r < R} g[p][i][r][c])^2 ,   red1[c] += sum_{(p, i)} (sum_r g[p][i][r][c] xhat[i][r][c])^2
+// Block = `cb` columns x (256 / cb) row lanes and a fixed group of (probe, example) pairs, taken in order: per pair the
+// row lanes sum strided rows, the lane sums meet in LDS and are added in lane order, squared and accumulated by row
+// lane 0.  One partial per group (plain stores) or, for a single group, added into the output directly.
+struct SqRedP {
+  float* part0; float* part1;           // [groups][N] each, or null: one group
+  int pairs, per, n_img, cb;
+};
+
+__global__ __launch_bounds__(256) void reduce_sqsum_kernel(const ReduceP prm, const SqRedP sq) {
+  __shared__ float s0[256], s1[256];
+  const int N = prm.N, cb = sq.cb, RL = 256 / cb;
+  const int cl = threadIdx.x % cb, rl = threadIdx.x / cb;
+  const int c = blockIdx.x * cb + cl;
+  const int grp = blockIdx.y;
+  const int q0 = grp * sq.per, q1 = min(sq.pairs, q0 + sq.per);
+  const bool on = c < N;
+  float a0 = 0.f, a1 = 0.f;
+  for (int q = q0; q < q1; ++q) {
+    const int p = q / sq.n_img, i = q - p * sq.n_img;
+    const long long seg = (long long)i * prm.R * N;
+    const float* g = prm.g + (long long)p * prm.g_ps + seg;
+    const float* xh = prm.xhat ? prm.xhat + seg : nullptr;
+    float t0 = 0.f, t1 = 0.f;
+    if (on)
+      for (int r = rl; r < prm.R; r += RL) {
+        const float v = g[(long long)r * N + c];
+        t0 += v;
+        if (xh) t1 = fmaf(v, xh[(long long)r * N + c], t1);
+      }
+    s0[threadIdx.x] = t0; s1[threadIdx.x] = t1;
+    __syncthreads();
+    if (rl == 0) {
+      float u0 = 0.f, u1 = 0.f;
+      for (int k = 0; k < RL; ++k) { u0 += s0[k * cb + cl]; u1 += s1[k * cb + cl]; }
+      a0 = fmaf(u0, u0, a0); a1 = fmaf(u1, u1, a1);
+    }
+    __syncthreads();
+  }
+  if (rl != 0 || !on) return;
+  if (sq.part0) {
+    if (prm.red0) sq.part0[(long long)grp * N + c] = a0;
+    if (prm.red1) sq.part1[(long long)grp * N + c] = a1;
+  } else {
+    if (prm.red0) prm.red0[c] += a0;
+    if (prm.red1) prm.red1[c] += a1;
+  }
+}
+
+static int sq_cb(int N) {
+  int cb = 64;
+  while (cb > 1 && cb / 2 >= N) cb >>= 1;
+  return cb;
+}
+
+// returns the group bound min(pairs, ceil(SQ_TARGET_BLOCKS / column blocks)) (monotone in `pairs`: the scratch size);
+// the launch's G <= bound after rounding to whole groups
+static long long sq_red_groups(int N, long long pairs, int& cb, int& G, int& per) {
+  cb = sq_cb(N);
+  const long long colblocks = (N + cb - 1) / cb;
+  long long g = (SQ_TARGET_BLOCKS + colblocks - 1) / colblocks;
+  if (g > pairs) g = pairs;
+  if (g < 1) g = 1;
+  per = (int)((pairs + g - 1) / g);
+  G = (int)((pairs + per - 1) / per);
+  return g;
+}
+
+long long reduce_sqsum_scratch(int N, long long pairs) {
+  if (N <= 0 || pairs <= 0) return 0;
+  int cb, G, per;
+  const long long bound = sq_red_groups(N, pairs, cb, G, per);
+  return bound > 1 ? 2ll * bound * N : 0;
+}
+
+hipError_t launch_reduce_sqsum(const ReduceP& p, int P, float* scratch, long long scratch_floats, hipStream_t st) {
+  if (!p.red0 && !p.red1) return hipSuccess;
+  const long long pairs = (long long)P * p.nseg;
+  if (P <= 0 || p.nseg <= 0 || p.N <= 0 || p.R <= 0 || pairs >= (1ll << 31)) return hipErrorInvalidValue;
+  SqRedP sq;
+  int G, per;
+  sq_red_groups(p.N, pairs, sq.cb, G, per);
+  sq.pairs = (int)pairs; sq.per = per; sq.n_img = p.nseg;
+  sq.part0 = sq.part1 = nullptr;
+  const long long need = G > 1 ? 2ll * G * p.N : 0;
+  if (need > scratch_floats || (need && !scratch)) return hipErrorInvalidValue;
+  if (G > 1) { sq.part0 = scratch; sq.part1 = scratch + (long long)G * p.N; }
+  hipLaunchKernelGGL(reduce_sqsum_kernel, dim3((unsigned)((p.N + sq.cb - 1) / sq.cb), (unsigned)G), dim3(256), 0, st, p, sq);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || G == 1) return e;
+  if (p.red0 && (e = launch_sqsum_finish(sq.part0, G, p.N, p.red0, st)) != hipSuccess) return e;
+  if (p.red1) e = launch_sqsum_finish(sq.part1, G, p.N, p.red1, st);
+  return e;
+}
+
+// y[j] += sum_g partial[g][j] in group order (the fixed-order second pass of the square-accumulating reductions)
+__global__ __launch_bounds__(256) void sqsum_finish_kernel(const float* __restrict__ partial, int G, long long len,
+                                                           float* __restrict__ y) {
+  for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < len; j += (long long)gridDim.x * 256) {
+    float s = 0.f;
+    for (int g = 0; g < G; ++g) s += partial[(long long)g * len + j];
+    y[j] += s;
+  }
+}
+
+hipError_t launch_sqsum_finish(const float* partial, int G, long long len, float* y, hipStream_t st) {
+  if (len <= 0 || G <= 0) return hipSuccess;
+  const long long blocks = (len + 255) / 256;
+  hipLaunchKernelGGL(sqsum_finish_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, partial, G, len, y);
+  return hipGetLastError();
+}
+
 // ---- mean pool over pixels: out[p][i][c] = inv * sum_pix in[p][i][pix][c]  (jnp.mean(x,(1,2))) ------
 __global__ __launch_bounds__(256) void pool_fwd_kernel(const PoolP prm) {
   extern __shared__ float sm[];           // [C]

@@ -688,3 +688,28 @@ class LinearizedNet:
         nv.check(self.lib.lip_vjp_rows(self.h, nv.ptr(Ub), nv.ptr(Y), Ub.shape[0], m, float(c), nv.stream_ptr()),
                  "lip_vjp_rows")
         return Y
+
+    def vjp_sqsum(self, U: torch.Tensor, mode: str = "raw", c: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Square sum of the rows of :meth:`vjp_rows` -> (D,):  ``sum_p sum_i (J_i^T (c L_i U[p, i]))**2`` ('l') or
+        ``sum_p sum_i (J_i^T U[p, i])**2`` ('raw'), ADDED into ``out`` when it is given (a zero vector otherwise).
+        Every per-(probe, example) parameter cotangent is squared where the backward sweep forms it (``lip_vjp_sqsum``),
+        so no (P, n, D) rows exist; the result is bitwise reproducible.  One-hot probes e_k on every example give the
+        GGN diagonal (:func:`ggn.compute_ggn_diag`); per-example loss gradients ('raw') the empirical-Fisher diagonal.
+        The kernels' scratch is a device buffer allocated once per engine, sized for the engine's probe chunk."""
+        if mode not in ("l", "raw"):
+            raise ValueError("mode must be 'l' or 'raw'")
+        Ub = U.reshape(-1, self.n * self.K).to(device=self.device, dtype=torch.float32).contiguous()
+        if out is None:
+            out = torch.zeros(self.D, device=self.device, dtype=torch.float32)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.D):
+            raise ValueError(f"out must be a contiguous float32 device vector of {self.D} floats")
+        scratch = getattr(self, "_sq_scratch", None)
+        if scratch is None:
+            floats = C.c_int64(0)
+            nv.check(self.lib.lip_vjp_sqsum_scratch(self.h, int(self.chunk), C.byref(floats)), "lip_vjp_sqsum_scratch")
+            scratch = torch.empty(max(1, floats.value), device=self.device, dtype=torch.float32)
+            self._sq_scratch = scratch
+        m = nv.HEAD_L if mode == "l" else nv.HEAD_IN
+        nv.check(self.lib.lip_vjp_sqsum(self.h, nv.ptr(Ub), nv.ptr(out), Ub.shape[0], m, float(c), nv.ptr(scratch),
+                                        scratch.numel(), nv.stream_ptr()), "lip_vjp_sqsum")
+        return out

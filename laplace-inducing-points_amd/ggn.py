@@ -213,6 +213,31 @@ def materialize_factor(eng: LinearizedNet, c: float = 1.0, block: Optional[int] 
     return Wm
 
 
+def compute_ggn_diag(state, Z, model_type, full_set_size=None, example_chunk: Optional[int] = None) -> torch.Tensor:
+    """diag((N/M) sum_i J_i^T H_i J_i) (x exp(-logvar) for the regressor) -> (D,) float32 on the device.
+
+    Not a reference function (the reference has no diagonal): the exact GGN diagonal, the curvature of a diagonal
+    Laplace posterior and the Jacobi preconditioner of the D-space solves.  K one-hot probes (e_k on every example)
+    go through ONE square-accumulating backward sweep (:meth:`LinearizedNet.vjp_sqsum`): diag = recal * sum_k sum_i
+    (J_i^T L_i e_k)^2 with the same N/M (x exp(-logvar)) factor as :func:`compute_ggn_vp`, and without the (M K, D)
+    factor rows ``(materialize_factor(eng) ** 2).sum(0)`` would write.  ``example_chunk`` binds the examples in chunks
+    as :class:`ExampleChunkedGGN` does; the chunks' sums add up in one output vector."""
+    M = Z.shape[0]
+    N = full_set_size or M
+    recal = N / M
+    if model_type == "regressor":
+        recal *= math.exp(-_logvar(state))
+    if example_chunk is None or example_chunk >= M:
+        engines = [get_engine(state, Z, model_type)]
+    else:
+        engines = ExampleChunkedGGN(state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk).engines
+    Y = torch.zeros(engines[0].D, device=engines[0].device, dtype=torch.float32)
+    for eng in engines:
+        E = torch.eye(eng.K, device=eng.device, dtype=torch.float32)[:, None, :].expand(eng.K, eng.n, eng.K)
+        eng.vjp_sqsum(E.contiguous(), "l", 1.0, out=Y)
+    return Y.mul_(recal)
+
+
 FACTOR_BYTES_LIMIT = 64 << 30
 
 

@@ -12,10 +12,10 @@ import math
 
 import torch
 
-from .distributions import MultivariateNormalFullCovariance
+from .distributions import MultivariateNormalDiag, MultivariateNormalFullCovariance
 from .engine import LinearizedNet
-from .ggn import BlockOperator, compute_ggn_dense, compute_ggn_vp, get_engine
-from .sample import sample
+from .ggn import BlockOperator, compute_ggn_dense, compute_ggn_diag, compute_ggn_vp, get_engine
+from .sample import sample, sample_diag
 from .utils import flatten_nn_params
 
 
@@ -110,6 +110,30 @@ def predict_lla_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_s
     eng = get_engine(map_state, Xnew, model_type, workspace_bytes=4 << 30)      # a per-batch binding: capped workspace
     fmu = eng.outputs()                                                         # (B, C)
     dys = eng.jvp(w_samples, "raw")                                             # (S, B, C)
+    return fmu[None] + dys
+
+
+def posterior_lla_diag(map_state, Z, model_type, alpha, full_set_size=None) -> MultivariateNormalDiag:
+    """Diagonal Laplace posterior N(theta_MAP, diag(1 / (alpha + diag(GGN)))) with the GGN of
+    :func:`compute_ggn_vp` (N/M, exp(-logvar)).  Not a reference function: the diagonal-LA baseline; its variances
+    are the per-weight uncertainties."""
+    diag = compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size)
+    flat_params, _ = flatten_nn_params(map_state.params)
+    loc = flat_params.detach().to(device=diag.device, dtype=diag.dtype)
+    return MultivariateNormalDiag(loc, variance=1.0 / (float(alpha) + diag))
+
+
+def predict_lla_diag_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1):
+    """:func:`predict_lla_scalable` with draws of the diagonal posterior (:func:`sample_diag`):
+    f(x; theta_MAP) + J(x) w_s -> (S, B, C).  Not a reference function."""
+    flat_params, _ = flatten_nn_params(map_state.params)
+    D = flat_params.shape[0]
+    key = key if key is not None else 123
+    w_samples = sample_diag(map_state, Z, D, alpha=alpha, key=key, model_type=model_type, num_samples=num_samples,
+                            full_set_size=full_set_size)
+    eng = get_engine(map_state, Xnew, model_type, workspace_bytes=4 << 30)
+    fmu = eng.outputs()
+    dys = eng.jvp(w_samples, "raw")
     return fmu[None] + dys
 
 

@@ -30,8 +30,8 @@ from typing import Optional
 import torch
 
 from . import krylov
-from .ggn import (FACTOR_BYTES_LIMIT, BlockOperator, build_WTW, compute_ggn_vp, compute_W_vps, gram_from_factor,
-                  materialize_factor)
+from .ggn import (FACTOR_BYTES_LIMIT, BlockOperator, build_WTW, compute_ggn_diag, compute_ggn_vp, compute_W_vps,
+                  gram_from_factor, materialize_factor)
 from .utils import flatten_nn_params
 
 REFERENCE_CLIP_MIN = 1.0
@@ -295,6 +295,18 @@ def sample(state, Z, D, alpha, key, model_type, num_samples=1, full_set_size=Non
         krylov.fill_normal(e - s, eng.D, _seed(key) * 1000003 + s, eng.device, out=out[s:e])
         fun.parts.apply_(out[s:e])
     return out
+
+
+def sample_diag(state, Z, D, alpha, key, model_type, num_samples=1, full_set_size=None):
+    """``num_samples`` zero-mean draws of the DIAGONAL Laplace posterior -> (S, D): eps / sqrt(alpha + diag(GGN)),
+    eps ~ N(0, I) from the same in-kernel generator and seeding as :func:`sample` (theta_MAP not added, as there).
+    Not a reference function: the diagonal-LA baseline an inducing-point posterior is compared against
+    (diag from :func:`ggn.compute_ggn_diag`)."""
+    diag = compute_ggn_diag(state, Z, model_type, full_set_size=full_set_size)
+    if diag.numel() != D:
+        raise ValueError(f"D = {D} does not match the network's {diag.numel()} parameters")
+    out = krylov.fill_normal(num_samples, D, _seed(key) * 1000003, diag.device)
+    return out.mul_(torch.rsqrt(diag + float(alpha)))
 
 
 def range_deflation(state, Z, D, alpha, model_type, full_set_size=None) -> "krylov.RangeDeflation":
