@@ -160,6 +160,13 @@ int lip_engine_run_op(lip_engine_t* e, const lip_op_t* op /*host*/, const float*
 int lip_debug_run_ops(lip_engine_t* e, int32_t which, int32_t first, int32_t count, const float* V, float* Y,
                       float* H, int32_t P, int32_t head_mode, float head_c, void* stream);
 
+/* test hook: launch-route census of the conv GEMM dispatchers and the square-sum kernels.  Every launch adds one to
+ * a host-side counter of its route (kernel instantiation and the flags that picked it, e.g. "igemm_fast<4,1,1,2>/par/bv4");
+ * no GPU work.  lip_debug_route_count: the number of routes known so far.  lip_debug_routes fills counts[i] and
+ * names[i] (static strings) for i < min(n, count), either may be NULL, then clears every count.               */
+int lip_debug_route_count(void);
+int lip_debug_routes(int64_t* counts, int32_t n, const char** names);
+
 /* Y[p] = scale * sum_i J_i^T H_i J_i V[p] + alpha * V[p]      src/ggn.py:133-144, src/lla.py:21-22
  * (scale carries N/M and, for the regressor, exp(-logvar): src/ggn.py:111-113)           */
 int lip_ggn_vp(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale, float alpha, void* stream);

@@ -70,6 +70,8 @@ SIGNATURES = {
     "lip_engine_run_op": (C.c_int, [_V, C.POINTER(Op), _V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V]),
     "lip_debug_run_ops": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, C.c_int32, C.c_int32,
                                     C.c_float, _V]),
+    "lip_debug_route_count": (C.c_int, []),
+    "lip_debug_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_char_p)]),
     "lip_ggn_vp": (C.c_int, [_V, _V, _V, C.c_int32, C.c_float, C.c_float, _V]),
     "lip_jvp": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V]),
     "lip_vjp": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V]),

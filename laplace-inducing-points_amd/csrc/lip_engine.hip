@@ -530,6 +530,14 @@ int lip_debug_run_ops(lip_engine_t* e, int32_t which, int32_t first, int32_t cou
   return LIP_OK;
 }
 
+int lip_debug_route_count(void) { return route_count(); }
+
+int lip_debug_routes(int64_t* counts, int32_t n, const char** names) {
+  if (n < 0) { set_error("lip_debug_routes: bad argument"); return LIP_ERR_ARG; }
+  routes_read(counts, n, names);
+  return LIP_OK;
+}
+
 int lip_ggn_vp(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale, float alpha, void* stream) {
   int rc = ready(e, "lip_ggn_vp");
   if (rc) return rc;

@@ -173,6 +173,21 @@ hipError_t launch_reduce_sqsum(const ReduceP& p, int P, float* scratch, long lon
 // y[j] += sum_{g < G} partial[g * len + j], g ascending
 hipError_t launch_sqsum_finish(const float* partial, int G, long long len, float* y, hipStream_t st);
 
+// ---- route census (lip_debug_routes): one host-side counter per launch route -----------------
+// A route is one kernel instantiation as launched, with the flags that picked it, e.g. "igemm_fast<4,1,1,2>/par/bv4".
+// route_id() formats the name and returns its slot (the table of known routes in lip_mfma.hip, or a new slot appended
+// after it); LIP_ROUTE caches the slot per launch site and adds one with a relaxed atomic.  No GPU work.
+int route_id(const char* fmt, ...);
+void route_hit(int id);
+int route_count();
+// copies min(n, route_count()) counts and names (names stay valid for the life of the process), then clears the counts
+int routes_read(int64_t* counts, int n, const char** names);
+#define LIP_ROUTE(...)                                                  \
+  do {                                                                  \
+    static const int lip_route_slot_ = ::lip::route_id(__VA_ARGS__);    \
+    ::lip::route_hit(lip_route_slot_);                                  \
+  } while (0)
+
 void set_error(const char* fmt, ...);
 int precision_mode();
 void set_precision_mode(int m);

@@ -20,8 +20,11 @@
 //   C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5).
 // LDS images are k-major (As[k][m], Bs[k][n]) so every MFMA operand read is 32 consecutive
 // dwords per half-wave: conflict-free ds_read_b32.
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
+#include <atomic>
 #include <mutex>
 #include "lip_internal.h"
 
@@ -1568,8 +1571,8 @@ static hipError_t run_igemm_first(const IgemmP& p, int P, hipStream_t st) {
   if (pgroups > P / 8) pgroups = P / 8;                                      // >= 8 probes per wave amortise its A / x-hat / act' gathers
   if (pgroups < 1) pgroups = 1;
   dim3 grid((unsigned)rblocks, (unsigned)pgroups);
-  if (p.seg[0].Ktot <= 28) hipLaunchKernelGGL((igemm_first_kernel<14>), grid, dim3(256), 0, st, p, P, pgroups);
-  else hipLaunchKernelGGL((igemm_first_kernel<32>), grid, dim3(256), 0, st, p, P, pgroups);
+  if (p.seg[0].Ktot <= 28) { LIP_ROUTE("igemm_first<14>"); hipLaunchKernelGGL((igemm_first_kernel<14>), grid, dim3(256), 0, st, p, P, pgroups); }
+  else { LIP_ROUTE("igemm_first<32>"); hipLaunchKernelGGL((igemm_first_kernel<32>), grid, dim3(256), 0, st, p, P, pgroups); }
   return hipGetLastError();
 }
 
@@ -2119,6 +2122,7 @@ bool wgrad_will_overwrite(const WgradP& p, int P) { return wgrad_skinny_ok(p) ||
 
 template <int TM, int KK>
 static hipError_t run_wgrad_skinny(const WgradP& p0, int P, hipStream_t st) {
+  LIP_ROUTE("wgrad_skinny<%d,%d>", TM, KK);
   WgradP p = p0;
   p.P = P;
   const int mgroups = (p.M + 32 * TM - 1) / (32 * TM);
@@ -2232,6 +2236,7 @@ static hipError_t run_wgrad_first(const WgradP& p0, int P, hipStream_t st) {
   if (rsplit > maxsplit) rsplit = maxsplit;
   if (rsplit < 1) rsplit = 1;
   const long long items = (long long)P * rsplit;
+  LIP_ROUTE("wgrad_first<%d>", KC);
   hipLaunchKernelGGL((wgrad_first_kernel<KC>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, p, rsplit);
   return hipGetLastError();
 }
@@ -2477,8 +2482,8 @@ static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st) {
     attr_set = true;
   }
   const dim3 grid((unsigned)((p.C / 32) * (p.N / 32) * S), (unsigned)P);
-  if ((TW & 3) == 0) hipLaunchKernelGGL(wgrad_wino_kernel<true>, grid, dim3(256), shmem, st, q);
-  else hipLaunchKernelGGL(wgrad_wino_kernel<false>, grid, dim3(256), shmem, st, q);
+  if ((TW & 3) == 0) { LIP_ROUTE("wgrad_wino/rowq"); hipLaunchKernelGGL(wgrad_wino_kernel<true>, grid, dim3(256), shmem, st, q); }
+  else { LIP_ROUTE("wgrad_wino"); hipLaunchKernelGGL(wgrad_wino_kernel<false>, grid, dim3(256), shmem, st, q); }
   return hipGetLastError();
 }
 
@@ -2764,6 +2769,83 @@ hipError_t launch_gemm_nn_axpy(const float* T, long long ldt, int m, int k, cons
 }
 
 // ------------------------------------------------------------------------------------------
+// route census: every launch route of the conv GEMM dispatchers (launch_igemm, launch_wgrad) and of the square-sum
+// kernels, in the names LIP_ROUTE forms at the launch sites.  tests/test_kernel_routes.py reaches each of them except
+// the A/B-only ones it lists; a route missing here still counts (in a slot appended at its first launch) but is not
+// part of that coverage check — add new routes to this table.  The LIP_TILE experiment tiles are not listed.
+// ------------------------------------------------------------------------------------------
+#define LIP_T6(pre, post) pre "<2,2,1,2>" post, pre "<2,2,2,2>" post, pre "<2,2,1,1>" post, pre "<4,1,1,2>" post, \
+                          pre "<2,1,1,1>" post, pre "<4,1,1,1>" post
+static const char* const kRoutes[] = {
+    "igemm_first<14>", "igemm_first<32>", "igemm_wino/vepi", "igemm_wino",
+    "igemm_fast<2,2,1,1>/ks/bv4", "igemm_fast<2,2,1,1>/ks", "igemm_fast<2,1,1,1>/ks/bv4", "igemm_fast<2,1,1,1>/ks",
+    "igemm_adirect<4,1,1,2>/bv4", "igemm_adirect<4,1,1,2>", "igemm_adirect<4,1,1,1>/bv4", "igemm_adirect<4,1,1,1>",
+    LIP_T6("igemm_fast", ""), LIP_T6("igemm_fast", "/bv4"), LIP_T6("igemm_fast", "/par"), LIP_T6("igemm_fast", "/par/bv4"),
+    LIP_T6("igemm_fast", "/x3"), LIP_T6("igemm_fast", "/x3/par"), LIP_T6("igemm", ""),
+    "wgrad_first<32>", "wgrad_skinny<2,8>", "wgrad_skinny<2,26>", "wgrad_skinny<2,32>", "wgrad_wino/rowq", "wgrad_wino",
+    "wgrad_pb<1,4,3,1>", "wgrad_pb<3,1,1,4>", "wgrad_pb<3,1,1,4>/x3", "wgrad_pb<2,2,2,2>", "wgrad_pb<2,2,2,2>/x3",
+    "wgrad_fast<2,2,1,2>/v4", "wgrad_fast<2,2,2,2>/v4", "wgrad_fast<2,2,1,1>/v4", "wgrad_fast<4,1,1,2>/v4",
+    "wgrad_fast<2,2,2,2>/x3", "wgrad_fast<4,1,1,2>/x3", "wgrad_fast<2,1,1,1>/x3", "wgrad_fast<4,1,1,1>/x3",
+    LIP_T6("wgrad_fast", ""), LIP_T6("wgrad", ""),
+    LIP_T6("wgrad_sqsum", ""), "wgrad_sqsum_dense", "reduce_sqsum",
+};
+#undef LIP_T6
+
+namespace {
+constexpr int kMaxRoutes = 512;
+struct RouteTable {
+  std::mutex mu;
+  int n = 0;
+  char names[kMaxRoutes][48];
+  std::atomic<long long> counts[kMaxRoutes];
+  RouteTable() {
+    for (int i = 0; i < kMaxRoutes; ++i) counts[i].store(0, std::memory_order_relaxed);
+    for (const char* r : kRoutes) snprintf(names[n++], sizeof(names[0]), "%s", r);
+    snprintf(names[kMaxRoutes - 1], sizeof(names[0]), "%s", "(route table full)");
+  }
+};
+RouteTable& route_table() {
+  static RouteTable t;
+  return t;
+}
+}  // namespace
+
+int route_id(const char* fmt, ...) {
+  char name[48];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(name, sizeof(name), fmt, ap);
+  va_end(ap);
+  RouteTable& t = route_table();
+  std::lock_guard<std::mutex> lock(t.mu);
+  for (int i = 0; i < t.n; ++i)
+    if (!strcmp(t.names[i], name)) return i;
+  if (t.n == kMaxRoutes - 1) return kMaxRoutes - 1;
+  snprintf(t.names[t.n], sizeof(t.names[0]), "%s", name);
+  return t.n++;
+}
+
+void route_hit(int id) { route_table().counts[id].fetch_add(1, std::memory_order_relaxed); }
+
+int route_count() {
+  RouteTable& t = route_table();
+  std::lock_guard<std::mutex> lock(t.mu);
+  return t.n;
+}
+
+int routes_read(int64_t* counts, int n, const char** names) {
+  RouteTable& t = route_table();
+  std::lock_guard<std::mutex> lock(t.mu);
+  const int m = n < t.n ? n : t.n;
+  for (int i = 0; i < m; ++i) {
+    if (counts) counts[i] = t.counts[i].load(std::memory_order_relaxed);
+    if (names) names[i] = t.names[i];
+  }
+  for (int i = 0; i < kMaxRoutes; ++i) t.counts[i].store(0, std::memory_order_relaxed);
+  return m;
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers: pick the tile shape from the problem shape
 // ------------------------------------------------------------------------------------------
 // 256 bytes of device zeros (per device): the source of masked gather rows in the fast kernels.
@@ -2898,8 +2980,8 @@ static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
         if (scratch) {
           q.partial = scratch; q.partial_zs = (long long)plane;
           dim3 g3((unsigned)tiles, (unsigned)P, (unsigned)ks);
-          if (bv4) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, false, false, true, true>), g3, dim3(T::NT), 0, st, q);
-          else hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, false, false, false, true>), g3, dim3(T::NT), 0, st, q);
+          if (bv4) { LIP_ROUTE("igemm_fast<%d,%d,%d,%d>/ks/bv4", WM, WN, TM, TN); hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, false, false, true, true>), g3, dim3(T::NT), 0, st, q); }
+          else { LIP_ROUTE("igemm_fast<%d,%d,%d,%d>/ks", WM, WN, TM, TN); hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, false, false, false, true>), g3, dim3(T::NT), 0, st, q); }
           hipLaunchKernelGGL((igemm_finish_kernel<WM, WN, TM, TN>), grid, dim3(T::NT), 0, st, q, (int)ks);
           return hipGetLastError();
         }
@@ -2909,12 +2991,16 @@ static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
       // A operand straight into the MFMA registers (A/B switch LIP_NOADIRECT)
       static const bool noad = getenv("LIP_NOADIRECT") != nullptr;
       if (!noad && !split && !par && !dbg) {
-        if (bv4) hipLaunchKernelGGL((igemm_adirect_kernel<TM, TN, true>), grid, dim3(256), 0, st, q);
-        else hipLaunchKernelGGL((igemm_adirect_kernel<TM, TN, false>), grid, dim3(256), 0, st, q);
+        if (bv4) { LIP_ROUTE("igemm_adirect<%d,%d,%d,%d>/bv4", WM, WN, TM, TN); hipLaunchKernelGGL((igemm_adirect_kernel<TM, TN, true>), grid, dim3(256), 0, st, q); }
+        else { LIP_ROUTE("igemm_adirect<%d,%d,%d,%d>", WM, WN, TM, TN); hipLaunchKernelGGL((igemm_adirect_kernel<TM, TN, false>), grid, dim3(256), 0, st, q); }
         return hipGetLastError();
       }
     }
-#define LIP_LAUNCH_IGEMM(S_, P_, V_) hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, S_, P_, V_>), grid, dim3(T::NT), 0, st, q)
+#define LIP_LAUNCH_IGEMM(S_, P_, V_)                                                                                   \
+  do {                                                                                                                 \
+    LIP_ROUTE("igemm_fast<%d,%d,%d,%d>%s%s%s", WM, WN, TM, TN, S_ ? "/x3" : "", P_ ? "/par" : "", V_ ? "/bv4" : "");  \
+    hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, S_, P_, V_>), grid, dim3(T::NT), 0, st, q);                  \
+  } while (0)
     if (split) {
       if (par) LIP_LAUNCH_IGEMM(true, true, false); else LIP_LAUNCH_IGEMM(true, false, false);
     } else {
@@ -2941,8 +3027,10 @@ static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
       }
     }
   }
-  else
+  else {
+    LIP_ROUTE("igemm<%d,%d,%d,%d>", WM, WN, TM, TN);
     hipLaunchKernelGGL((igemm_kernel<WM, WN, TM, TN>), grid, dim3(T::NT), 0, st, p);
+  }
   return hipGetLastError();
 }
 
@@ -3003,7 +3091,7 @@ static bool igemm_wino_ok(const IgemmP& p, int P) {
     if (n_img * p.OHW * q.C * 4 >= (1ll << 31) || 16ll * q.C * p.N * 4 >= (1ll << 31)) return false;
   }
   const WinoGeom g = wino_geom(OH, p.OW, n_img);
-  if (g.NS > WINO_SLOTS) return false;                 // (maps smaller than 8 x 8: the direct kernels)
+  if (g.NS > WINO_SLOTS) return false;                 // (4 x 4 maps and smaller: the direct kernels; 6 x 6 fits)
   // (a rule "only launches that fill the chip" was measured and dropped: with the route on every eligible launch a
   //  single product takes 1.85 instead of 2.02 ms, two 2.21 instead of 3.43, four 2.99 instead of 4.66, eight 4.65
   //  instead of 5.15 — an under-filled Winograd launch lasts one short block, an under-filled direct launch one long one)
@@ -3053,8 +3141,8 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st) {
   static const bool novepi = getenv("LIP_WINO_NOVEPI") != nullptr;
   const bool vepi = !novepi && al16(p.out, p.out_ps) && al16(p.res, p.res_ps) && al16(p.xhat, 0) && al16(p.dphi, 0) && al16(p.xhat2, 0);
   dim3 grid((unsigned)((long long)g.nbx * g.nby * g.nbi * (p.N / 32)), (unsigned)P, 1);
-  if (vepi) hipLaunchKernelGGL(igemm_wino_kernel<true>, grid, dim3(256), shmem, st, q, wx);
-  else hipLaunchKernelGGL(igemm_wino_kernel<false>, grid, dim3(256), shmem, st, q, wx);
+  if (vepi) { LIP_ROUTE("igemm_wino/vepi"); hipLaunchKernelGGL(igemm_wino_kernel<true>, grid, dim3(256), shmem, st, q, wx); }
+  else { LIP_ROUTE("igemm_wino"); hipLaunchKernelGGL(igemm_wino_kernel<false>, grid, dim3(256), shmem, st, q, wx); }
   return hipGetLastError();
 }
 
@@ -3139,17 +3227,23 @@ static hipError_t run_wgrad(const WgradP& p0, int P, hipStream_t st) {
     const bool v4 = (p.N & 3) == 0 && (p.g_ps & 3) == 0 && (((uintptr_t)p.g) & 15) == 0;
     if constexpr (T::AQ == 2) {
       if (precision_mode() == 1 && v4) {              // split precision (bf16x3 operands), every tile width
+        LIP_ROUTE("wgrad_fast<%d,%d,%d,%d>/x3", WM, WN, TM, TN);
         hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, false, true, true>), grid, dim3(T::NT), 0, st, q);
         return hipGetLastError();
       }
     }
-    if (!nobv4 && T::BN >= 64 && v4)
+    if (!nobv4 && T::BN >= 64 && v4) {
+      LIP_ROUTE("wgrad_fast<%d,%d,%d,%d>/v4", WM, WN, TM, TN);
       hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, false, true>), grid, dim3(T::NT), 0, st, q);
-    else
+    } else {
+      LIP_ROUTE("wgrad_fast<%d,%d,%d,%d>", WM, WN, TM, TN);
       hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, false, false>), grid, dim3(T::NT), 0, st, q);
+    }
   }
-  else
+  else {
+    LIP_ROUTE("wgrad<%d,%d,%d,%d>", WM, WN, TM, TN);
     hipLaunchKernelGGL((wgrad_kernel<WM, WN, TM, TN>), grid, dim3(T::NT), 0, st, p);
+  }
   return hipGetLastError();
 }
 
@@ -3175,10 +3269,12 @@ static hipError_t run_wgrad_pb(const WgradP& p, int P, hipStream_t st) {
   dim3 grid((unsigned)tiles, 1, (unsigned)q.ksplit);
   if constexpr (T::NT % (T::BM / 4) == 0) {        // (the split-precision loader needs one m-quad per thread)
     if (precision_mode() == 1) {
+      LIP_ROUTE("wgrad_pb<%d,%d,%d,%d>/x3", WM, WN, TM, TN);
       hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, true, true, true>), grid, dim3(T::NT), 0, st, q);
       return hipGetLastError();
     }
   }
+  LIP_ROUTE("wgrad_pb<%d,%d,%d,%d>", WM, WN, TM, TN);
   hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, true>), grid, dim3(T::NT), 0, st, q);
   return hipGetLastError();
 }
@@ -3498,6 +3594,7 @@ static hipError_t run_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scra
   const long long need = G > 1 ? (long long)G * p.M * p.N : 0;
   if (need > scratch_floats || (need && !scratch)) return hipErrorInvalidValue;
   if (G > 1) sq.partial = scratch;
+  LIP_ROUTE("wgrad_sqsum<%d,%d,%d,%d>", WM, WN, TM, TN);
   hipLaunchKernelGGL((wgrad_sqsum_kernel<WM, WN, TM, TN>), dim3((unsigned)tiles, (unsigned)G), dim3(T::NT), 0, st, p, sq);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || G == 1) return e;
@@ -3508,6 +3605,7 @@ hipError_t launch_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch,
   if (P <= 0 || n_img <= 0 || p.OHW * n_img != p.R || (long long)P * n_img >= (1ll << 31)) return hipErrorInvalidValue;
   if (p.OHW == 1) {
     dim3 grid((unsigned)((p.N + 63) / 64), (unsigned)((p.M + 31) / 32));
+    LIP_ROUTE("wgrad_sqsum_dense");
     hipLaunchKernelGGL(wgrad_sqsum_dense_kernel, grid, dim3(256), 0, st, p, P, n_img);
     return hipGetLastError();
   }

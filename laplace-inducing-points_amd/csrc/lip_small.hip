@@ -165,6 +165,7 @@ hipError_t launch_reduce_sqsum(const ReduceP& p, int P, float* scratch, long lon
   const long long need = G > 1 ? 2ll * G * p.N : 0;
   if (need > scratch_floats || (need && !scratch)) return hipErrorInvalidValue;
   if (G > 1) { sq.part0 = scratch; sq.part1 = scratch + (long long)G * p.N; }
+  LIP_ROUTE("reduce_sqsum");
   hipLaunchKernelGGL(reduce_sqsum_kernel, dim3((unsigned)((p.N + sq.cb - 1) / sq.cb), (unsigned)G), dim3(256), 0, st, p, sq);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || G == 1) return e;

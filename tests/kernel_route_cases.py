@@ -1,0 +1,201 @@
+"""Case table of tests/test_kernel_routes.py: one synthetic op per row, with the launch route it must take.
+
+Shared with the CPU test of the reference (tests/test_kernel_routes_cpu.py), which checks the float64 emulator on the
+same geometries.  Expected routes assume the 256 CUs of an MI355X where ``cu`` is set: the few-probe tile rule, split-K
+and the probe-batched split depend on the CU count.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict, List
+
+from lip_amd import _native as nv
+from op_harness import OpSpec, SegSpec
+
+
+@dataclass
+class Case:
+    name: str
+    route: str
+    spec: OpSpec
+    prec: int = 0                     # lip_set_precision
+    wino: int = 1                     # lip_set_winograd
+    split_k: int = 1                  # lip_set_split_k
+    tol: str = "exact"                # "exact" | "wino" | "x3"
+    cu: bool = False                  # route depends on the CU count
+    det: bool = True                  # no float atomics: a second run is bitwise equal
+
+
+def conv(n, H, C, N, P, k=3, s=1, pad=None, W=None, mode=0, OH=None, OW=None, epi=None, nseg=1, **kw):
+    """one implicit GEMM over an n x H x W x C map; mode 1 is the transposed conv onto OH x OW."""
+    W = W or H
+    pad = (k - 1) // 2 if pad is None else pad
+    seg_kw = {x: kw.pop(x) for x in list(kw) if x in SegSpec.__dataclass_fields__}
+    if mode == 0:
+        OH, OW = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
+    else:
+        OH = OH or H * s
+        OW = OW or OH
+    segs = [SegSpec(H, W, C, k, k, s, pad, mode, **seg_kw) for _ in range(nseg)]
+    return OpSpec(nv.OP_IGEMM, segs, n, OH, OW, N, P, epi=dict(epi or {}), **kw)
+
+
+def wgrad(n, H, C, N, P, k=3, s=1, pad=None, W=None, epi=None, **kw):
+    W = W or H
+    pad = (k - 1) // 2 if pad is None else pad
+    OH, OW = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
+    return OpSpec(nv.OP_WGRAD, [SegSpec(H, W, C, k, k, s, pad, 0)], n, OH, OW, N, P, epi=dict(epi or {}), **kw)
+
+
+def dense_wgrad(n, C, N, P, **kw):
+    return OpSpec(nv.OP_WGRAD, [SegSpec(1, 1, C, 1, 1, 1, 0, 0)], n, 1, 1, N, P, **kw)
+
+
+T6 = ("2,2,1,2", "2,2,2,2", "2,2,1,1", "4,1,1,2", "2,1,1,1", "4,1,1,1")
+# a geometry per tile of the direct conv kernels (3 x 3, pad 1 over an H x H map; N the 16-byte-aligned column count):
+#   N > 64: R <= 64 -> <2,2,1,2>, else <2,2,2,2>; 33..64: <2,2,1,1> / <4,1,1,2>; <= 32: <2,1,1,1> / <4,1,1,1>.
+# R > 64 takes the 128-row tiles only with >= 2 * 256 blocks of 128 rows (the few-probe rule): 8 row tiles x 64 probes
+IG = {"2,2,1,2": dict(n=1, H=8, N=128, P=3, cu=False), "2,2,2,2": dict(n=1, H=32, N=128, P=64, cu=True),
+      "2,2,1,1": dict(n=1, H=8, N=64, P=2, cu=False), "4,1,1,2": dict(n=1, H=32, N=64, P=64, cu=True),
+      "2,1,1,1": dict(n=1, H=8, N=32, P=7, cu=False), "4,1,1,1": dict(n=1, H=32, N=32, P=64, cu=True)}
+
+
+def _igemm_cases() -> List[Case]:
+    cs = []
+    for t in T6:
+        g = IG[t]
+        n, H, N, P, cu = g["n"], g["H"], g["N"], g["P"], g["cu"]
+        adirect = t.startswith("4,1")
+        # plain conv (mode 0), C = 16: the fast kernel (no Winograd: C % 32 != 0); N % 4 decides the dwordx4 B loads
+        if not adirect:
+            cs.append(Case(f"fast{t}", f"igemm_fast<{t}>", conv(n, H, 16, N - 1, P, a_pp=True), cu=cu))
+            cs.append(Case(f"fast{t}_bv4", f"igemm_fast<{t}>/bv4", conv(n, H, 16, N, P, b_pp=True, epi={"scale": "shared"}), cu=cu))
+        else:
+            cs.append(Case(f"adirect{t}", f"igemm_adirect<{t}>", conv(n, H, 16, N - 1, P, a_pp=True, epi={"e0": "probe"}), cu=cu))
+            cs.append(Case(f"adirect{t}_bv4", f"igemm_adirect<{t}>/bv4",
+                           conv(n, H, 16, N, P, b_pp=True, epi={"scale": "shared", "e1": "probe", "xhat": "shared", "dphi": "shared"}), cu=cu))
+        # stride-2 data gradient (mode 1) onto the even H x H map: parity-class row order
+        cs.append(Case(f"fast{t}_par", f"igemm_fast<{t}>/par", conv(n, H // 2, 16, N - 1, P, s=2, mode=1, OH=H, a_pp=True), cu=cu))
+        cs.append(Case(f"fast{t}_par_bv4", f"igemm_fast<{t}>/par/bv4",
+                       conv(n, H // 2, 16, N, P, s=2, mode=1, OH=H, b_pp=True, epi={"res": "probe", "dphi": "shared"}), cu=cu))
+        # split precision (bf16x3)
+        cs.append(Case(f"fast{t}_x3", f"igemm_fast<{t}>/x3", conv(n, H, 16, N, P, a_pp=True, epi={"e0": "shared"}), prec=1, tol="x3", cu=cu))
+        cs.append(Case(f"fast{t}_x3_par", f"igemm_fast<{t}>/x3/par", conv(n, H // 2, 16, N - 1, P, s=2, mode=1, OH=H, b_pp=True),
+                       prec=1, tol="x3", cu=cu))
+        # the generic kernel: C % 16 != 0
+        cs.append(Case(f"generic{t}", f"igemm<{t}>", conv(n, H, 17, N, P, a_pp=True), cu=cu))
+    cs += [
+        # ---- sizes and channel counts of the direct kernels
+        Case("generic_N1_C1", "igemm<2,1,1,1>", conv(1, 8, 1, 1, 2)),
+        Case("generic_N3_C3", "igemm<2,1,1,1>", conv(1, 5, 3, 3, 1, epi={"scale": "shared", "e0": "shared"})),
+        Case("fast_N33", "igemm_fast<2,2,1,1>", conv(1, 8, 16, 33, 3, epi={"red0": ""}), det=False),
+        Case("fast_N65", "igemm_fast<2,2,1,2>", conv(1, 8, 16, 65, 2, epi={"red1": "", "xhat2": "shared"}), det=False),
+        Case("fast_N129", "igemm_fast<2,2,1,2>", conv(1, 8, 16, 129, 2, epi={"e0": "probe", "red0": "", "red1": "", "xhat2": "shared"}), det=False),
+        Case("fast_N31_R63", "igemm_fast<2,1,1,1>", conv(1, 9, 32, 31, 2, W=7)),
+        Case("generic_C17_N63_R49", "igemm<2,2,1,1>", conv(1, 7, 17, 63, 9, epi={"red0": ""}), det=False),
+        Case("fast_C64_N16", "igemm_fast<2,1,1,1>/bv4", conv(1, 4, 64, 16, 8, k=1)),
+        # transposed stride 2 onto an ODD map: no parity-class order
+        Case("tconv_odd", "igemm_fast<2,2,1,1>/bv4", conv(1, 4, 16, 64, 2, s=2, mode=1, OH=7)),
+        Case("tconv_odd_generic", "igemm<2,2,1,1>", conv(1, 4, 17, 48, 2, s=2, mode=1, OH=7)),
+        # multi-segment and transposed B
+        Case("fast_nseg2", "igemm_fast<2,2,1,2>/bv4", conv(1, 8, 16, 96, 2, nseg=2, b_pp=True)),
+        Case("fast_nseg3_par", "igemm_fast<2,2,1,1>/par/bv4", conv(1, 4, 16, 64, 2, s=2, mode=1, OH=8, nseg=3)),
+        Case("generic_btrans", "igemm<2,2,1,1>", conv(1, 8, 16, 64, 2, b_trans=True, b_pp=True)),
+        Case("generic_btrans_nseg2", "igemm<2,1,1,1>", conv(1, 8, 32, 32, 2, nseg=2, b_trans=True)),
+        # per-probe A with an odd probe stride (C % 4 != 0)
+        Case("generic_a_odd", "igemm<2,1,1,1>", conv(1, 6, 5, 20, 3, a_pp=True, a_odd=True)),
+        # every epilogue field in one launch, shared and per-probe addends, other spaces
+        Case("fast_all_epi", "igemm_fast<2,2,1,1>/bv4",
+             conv(1, 8, 16, 64, 3, epi={"scale": "shared:C", "e0": "probe:H", "e1": "shared", "xhat": "shared",
+                                        "res": "probe:H", "dphi": "shared", "red0": "", "red1": "", "xhat2": "shared"}), det=False),
+        Case("generic_all_epi", "igemm<2,2,1,2>",
+             conv(1, 8, 17, 80, 2, epi={"scale": "shared", "e0": "shared", "e1": "probe", "xhat": "shared",
+                                        "res": "probe", "dphi": "shared", "red0": "", "red1": "", "xhat2": "shared"}), det=False),
+        # operands in WORK (offsets scaled by the chunk size), output in PRIM (no split-K, no Winograd), CONST epilogue
+        Case("work_operands", "igemm_fast<2,1,1,1>/bv4", conv(1, 4, 16, 16, 2, a_pp=True, a_space="W", out_space="W")),
+        Case("prim_out_no_ksplit", "igemm_fast<2,2,1,1>/bv4", conv(1, 7, 64, 64, 1, out_space="P", epi={"scale": "shared:C"})),
+        Case("prim_out_no_wino", "igemm_fast<2,1,1,1>/bv4", conv(1, 8, 32, 32, 1, out_space="P")),
+        # ---- first-layer kernels: C % 16 != 0, Ktot <= 64, N = 32, shared A, P >= 8
+        Case("first14_C3_P8", "igemm_first<14>", conv(2, 16, 3, 32, 8, epi={"scale": "shared", "e1": "shared", "xhat": "shared", "dphi": "shared"})),
+        Case("first14_C1_P256", "igemm_first<14>", conv(1, 8, 1, 32, 256, epi={"e0": "probe"})),
+        Case("first32_C7_P9", "igemm_first<32>", conv(1, 12, 7, 32, 9)),
+        Case("first32_C5_P64", "igemm_first<32>", conv(1, 9, 5, 32, 64, epi={"e0": "shared", "dphi": "shared"})),
+        Case("first_P7_generic", "igemm<2,1,1,1>", conv(1, 8, 3, 32, 7)),
+        # ---- split-K (few probes, long K): 7 x 7 maps (no Winograd), C = 64 -> 36 K-tiles, 3 shares
+        Case("ks_2211_bv4", "igemm_fast<2,2,1,1>/ks/bv4", conv(1, 7, 64, 64, 2, epi={"e0": "probe", "dphi": "shared"}), cu=True),
+        Case("ks_2211", "igemm_fast<2,2,1,1>/ks", conv(1, 7, 64, 63, 2, epi={"red0": "", "red1": "", "xhat2": "shared"}), cu=True, det=False),
+        Case("ks_2111_bv4", "igemm_fast<2,1,1,1>/ks/bv4", conv(1, 7, 64, 32, 1, epi={"scale": "shared", "res": "probe"}), cu=True),
+        Case("ks_2111", "igemm_fast<2,1,1,1>/ks", conv(1, 7, 64, 31, 2), cu=True),
+        # Ktot just below (23 K-tiles: 1 share) and at (24: 2 shares) the threshold of 12 K-tiles per share
+        Case("ks_below", "igemm_fast<2,2,1,1>/bv4", conv(1, 9, 368, 64, 1, k=1), cu=True),
+        Case("ks_above", "igemm_fast<2,2,1,1>/ks/bv4", conv(1, 9, 384, 64, 1, k=1), cu=True),
+        Case("ks_off", "igemm_fast<2,2,1,1>/bv4", conv(1, 7, 64, 64, 2), split_k=0),
+        # ---- Winograd F(2x2, 3x3): C, N multiples of 32, even maps >= 8 x 8
+        Case("wino_8x8", "igemm_wino/vepi", conv(1, 8, 32, 32, 2, epi={"scale": "shared", "e0": "probe"})),
+        Case("wino_28x28", "igemm_wino/vepi", conv(1, 28, 32, 64, 2, epi={"dphi": "shared", "res": "probe"})),
+        Case("wino_24x24_t", "igemm_wino/vepi", conv(2, 24, 64, 32, 1, mode=1, OH=24, s=1, b_pp=True)),
+        Case("wino_12x12", "igemm_wino/vepi", conv(3, 12, 32, 32, 3, nseg=2, epi={"red0": "", "red1": "", "xhat2": "shared"}), det=False),
+        Case("wino_misaligned_out", "igemm_wino", conv(1, 8, 32, 32, 2, out_shift=1, epi={"e1": "shared", "xhat": "shared"})),
+        Case("wino_off", "igemm_fast<2,1,1,1>/bv4", conv(1, 8, 32, 32, 2), wino=0),
+        Case("wino_6x6", "igemm_wino/vepi", conv(1, 6, 32, 32, 2, a_pp=True)),
+        Case("wino_4x4_ineligible", "igemm_fast<2,1,1,1>/bv4", conv(1, 4, 32, 32, 2)),
+    ]
+    for c in cs:
+        if c.route.startswith("igemm_wino"):
+            c.tol = "wino"
+    return cs
+
+
+def _wgrad_cases() -> List[Case]:
+    return [
+        Case("wg_first", "wgrad_first<32>", wgrad(2, 32, 3, 32, 8), det=False),
+        Case("wg_first_C1_P9", "wgrad_first<32>", wgrad(1, 48, 1, 16, 9, epi={"scale": "shared"}), det=False),
+        # skinny: one output pixel per example (dense layers), R <= 16 / <= 52 / <= 64
+        Case("wg_skinny8", "wgrad_skinny<2,8>", dense_wgrad(16, 40, 45, 3, epi={"scale": "shared"})),
+        Case("wg_skinny8_R3", "wgrad_skinny<2,8>", dense_wgrad(3, 130, 1, 2)),
+        Case("wg_skinny26", "wgrad_skinny<2,26>", dense_wgrad(52, 130, 33, 2)),
+        Case("wg_skinny32", "wgrad_skinny<2,32>", dense_wgrad(64, 64, 64, 2, epi={"scale": "shared"})),
+        Case("wg_skinny32_map", "wgrad_skinny<2,32>", OpSpec(nv.OP_WGRAD, [SegSpec(2, 2, 16, 2, 2, 1, 0, 0)], 53, 1, 1, 96, 1)),
+        # Winograd weight gradient: one split (no atomics), several splits (atomics)
+        Case("wg_wino_rowq", "wgrad_wino/rowq", wgrad(1, 8, 32, 32, 2), tol="wino"),
+        Case("wg_wino_24", "wgrad_wino/rowq", wgrad(1, 24, 32, 64, 1, epi={"scale": "shared"}), tol="wino"),
+        Case("wg_wino_12", "wgrad_wino", wgrad(2, 12, 32, 32, 2), tol="wino"),
+        Case("wg_wino_14", "wgrad_wino", wgrad(1, 28, 32, 32, 2), tol="wino"),
+        Case("wg_wino_split", "wgrad_wino/rowq", wgrad(4, 32, 32, 32, 2), tol="wino", det=False),
+        # probe-batched tiles (N <= 64, M >= 96; N = 16 keeps the 3 x 3 layers off the Winograd route)
+        Case("wg_pb96_288", "wgrad_pb<1,4,3,1>", wgrad(1, 8, 32, 16, 4), det=False),
+        Case("wg_pb96_576", "wgrad_pb<1,4,3,1>", wgrad(2, 6, 64, 16, 9, epi={"scale": "shared"}), det=False),
+        Case("wg_pb96_x3", "wgrad_pb<3,1,1,4>/x3", wgrad(1, 8, 32, 16, 4), prec=1, tol="x3", det=False),
+        Case("wg_pb128", "wgrad_pb<2,2,2,2>", wgrad(1, 8, 16, 32, 4), det=False),
+        Case("wg_pb128_P7N12", "wgrad_pb<2,2,2,2>", wgrad(1, 8, 16, 12, 7), det=False),
+        Case("wg_pb128_P64", "wgrad_pb<2,2,2,2>", wgrad(2, 8, 16, 20, 64), det=False),
+        Case("wg_pb128_x3", "wgrad_pb<2,2,2,2>/x3", wgrad(1, 8, 16, 32, 4), prec=1, tol="x3", det=False),
+        # per-probe tiles
+        Case("wg_2212_v4", "wgrad_fast<2,2,1,2>/v4", wgrad(1, 8, 4, 128, 2), det=False),
+        Case("wg_2212", "wgrad_fast<2,2,1,2>", wgrad(1, 8, 4, 127, 2), det=False),
+        Case("wg_2212_generic", "wgrad<2,2,1,2>", wgrad(1, 8, 3, 129, 2), det=False),
+        Case("wg_2222_v4", "wgrad_fast<2,2,2,2>/v4", wgrad(1, 8, 16, 128, 2, epi={"scale": "shared"}), det=False),
+        Case("wg_2222", "wgrad_fast<2,2,2,2>", wgrad(1, 8, 16, 127, 1), det=False),
+        Case("wg_2222_x3", "wgrad_fast<2,2,2,2>/x3", wgrad(1, 8, 16, 128, 2), prec=1, tol="x3", det=False),
+        Case("wg_2222_generic", "wgrad<2,2,2,2>", wgrad(1, 8, 17, 65, 2), det=False),
+        Case("wg_2211_v4", "wgrad_fast<2,2,1,1>/v4", wgrad(1, 8, 4, 64, 2), det=False),
+        Case("wg_2211", "wgrad_fast<2,2,1,1>", wgrad(1, 8, 4, 63, 2), det=False),
+        Case("wg_2211_generic", "wgrad<2,2,1,1>", wgrad(1, 8, 3, 33, 2), det=False),
+        Case("wg_4112_v4", "wgrad_fast<4,1,1,2>/v4", wgrad(1, 8, 16, 64, 1), det=False),
+        Case("wg_4112_v4_ks3", "wgrad_fast<4,1,1,2>/v4", wgrad(1, 8, 16, 64, 1, ksplit=3), det=False),
+        Case("wg_4112", "wgrad_fast<4,1,1,2>", wgrad(1, 8, 16, 63, 2), det=False),
+        Case("wg_4112_x3", "wgrad_fast<4,1,1,2>/x3", wgrad(1, 8, 16, 64, 1), prec=1, tol="x3", det=False),
+        Case("wg_4112_generic", "wgrad<4,1,1,2>", wgrad(1, 8, 17, 64, 2), det=False),
+        Case("wg_2111", "wgrad_fast<2,1,1,1>", wgrad(1, 8, 4, 32, 2), det=False),
+        Case("wg_2111_x3", "wgrad_fast<2,1,1,1>/x3", wgrad(1, 8, 4, 32, 2), prec=1, tol="x3", det=False),
+        Case("wg_2111_generic", "wgrad<2,1,1,1>", wgrad(1, 8, 3, 31, 2), det=False),
+        Case("wg_4111", "wgrad_fast<4,1,1,1>", wgrad(1, 8, 16, 32, 1), det=False),
+        Case("wg_4111_s2", "wgrad_fast<4,1,1,1>", wgrad(1, 9, 16, 3, 1, s=2, ksplit=2), det=False),
+        Case("wg_4111_x3", "wgrad_fast<4,1,1,1>/x3", wgrad(1, 8, 16, 32, 1), prec=1, tol="x3", det=False),
+        Case("wg_4111_generic", "wgrad<4,1,1,1>", wgrad(1, 8, 17, 32, 1), det=False),
+    ]
+
+
+CASES: List[Case] = _igemm_cases() + _wgrad_cases()
+BY_NAME: Dict[str, Case] = {c.name: c for c in CASES}
+assert len(BY_NAME) == len(CASES)

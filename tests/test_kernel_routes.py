@@ -1,0 +1,279 @@
+"""GPU: every launch route of the conv GEMM dispatchers (launch_igemm, launch_wgrad), op by op against float64.
+
+Each row of tests/kernel_route_cases.py is one synthetic IGEMM / WGRAD op run through lip_engine_run_op.  The test
+asserts that the route census of that call is exactly the expected route, then checks every output element against
+the float64 emulator (tests/op_harness.py: bound on Mag, RMS, canaries, accumulation, determinism).  The coverage
+test asserts that the table reaches every route the library lists except the A/B-only ones below.
+"""
+import pytest
+import torch
+
+from lip_amd import _native as nv
+from kernel_route_cases import CASES
+from op_harness import Harness, check, emulate, all_routes
+
+pytestmark = pytest.mark.gpu
+
+MI355X_CUS = 256
+
+# routes reachable only through an A/B environment switch (read once per process, so never set by a test)
+AB_ONLY = {
+    "igemm_fast<4,1,1,2>", "igemm_fast<4,1,1,2>/bv4",      # LIP_NOADIRECT: the 128-row f32 tiles take igemm_adirect
+    "igemm_fast<4,1,1,1>", "igemm_fast<4,1,1,1>/bv4",      # (same switch)
+    "wgrad_pb<3,1,1,4>",                                   # LIP_WGRAD3: the three-wave 96-row tile in f32 mode
+}
+# routes of the per-example square-sum path (lip_vjp_sqsum), reached by the nets of test_sqsum_and_rows_routes below
+SQSUM_NETS = {"a": {"wgrad_sqsum<2,2,1,2>", "wgrad_sqsum<4,1,1,2>", "wgrad_sqsum<2,2,2,2>", "wgrad_sqsum<4,1,1,1>",
+                    "wgrad_sqsum_dense", "reduce_sqsum"},
+              "b": {"wgrad_sqsum<4,1,1,1>", "wgrad_sqsum<2,2,1,1>", "wgrad_sqsum<2,1,1,1>", "wgrad_sqsum_dense",
+                    "reduce_sqsum"}}
+SQSUM_ROUTES = set().union(*SQSUM_NETS.values())
+
+# error constants, in units of 2^-24 * Mag (Mag: the emulator's result on |every operand|); "RMS" is the RMS of the
+# normalised error over an output divided by sqrt(K), K the reduction length (Ktot; WGRAD: R; red0 / red1: + R)
+#   exact f32 routes: worst case Ktot + 16 for any summation order (worst measured 0.10 (Ktot + 16)); RMS measured 0.24
+RMS_EXACT = 1.0
+#   Winograd F(2x2, 3x3): the transforms add and subtract up to 16 input and weight terms in f32: worst measured 3.9;
+#   bound 16.  RMS measured 0.075; bound 0.3
+K_WINO, RMS_WINO = 16.0, 0.3
+#   bf16x3 split precision (~1e-5 relative per product): worst measured 219 (stride-2 data gradients), 86 elsewhere;
+#   bound 1024.  RMS measured 2.0; bound 8
+K_X3, RMS_X3 = 1024.0, 8.0
+#   square sums (lip_vjp_sqsum): per element, in units of 2^-24 sum_{p,i} |r_pij| max_tensor |r| (r: the per-example
+#   rows): worst measured 4.2; bound 16
+K_SQ = 16.0
+
+_H = None
+
+
+def harness():
+    global _H
+    if _H is None:
+        _H = Harness(max_chunk=256)
+    return _H
+
+
+def _ktot(spec):
+    return spec.R if spec.kind == nv.OP_WGRAD else sum(s.Ktot for s in spec.segs)
+
+
+def tolerances(case):
+    """k_of(output name) -> (worst-case k, RMS reference length), and the RMS constant of the route class."""
+    spec = case.spec
+    kt = _ktot(spec)
+
+    def k_of(name):
+        kk = kt + (spec.R if name in ("red0", "red1") else 0)
+        if case.tol == "wino":
+            return K_WINO * (1 + (spec.R if name in ("red0", "red1") else 0) / 16), kk
+        if case.tol == "x3":
+            return K_X3 * (1 + (spec.R if name in ("red0", "red1") else 0) / 16), kk
+        return kk + 16, kk
+
+    rms_c = {"exact": RMS_EXACT, "wino": RMS_WINO, "x3": RMS_X3}[case.tol]
+    return k_of, rms_c
+
+
+def set_modes(lib, case):
+    prev = (lib.lip_get_precision(), lib.lip_get_winograd())
+    nv.check(lib.lip_set_precision(case.prec), "lip_set_precision")
+    nv.check(lib.lip_set_winograd(case.wino), "lip_set_winograd")
+    nv.check(lib.lip_set_split_k(case.split_k), "lip_set_split_k")
+    return prev
+
+
+def restore_modes(lib, prev):
+    lib.lip_set_precision(prev[0])
+    lib.lip_set_winograd(prev[1])
+    lib.lip_set_split_k(1)
+
+
+def run_case(case, seed=0):
+    """run one case; returns (census of the first run, stats {output: (max err, rms / sqrt(K))})."""
+    h = harness()
+    op, L, host, outs = h.build(case.spec, seed)
+    P = case.spec.P
+    prev = set_modes(h.lib, case)
+    try:
+        dev = h.upload(host)
+        h.routes()                                   # clear
+        h.run(op, dev, P)
+        census = h.routes()
+        got = h.download(dev)
+        if case.det:
+            dev = h.upload(host)
+            h.run(op, dev, P)
+            again = h.download(dev)
+    finally:
+        restore_modes(h.lib, prev)
+    ref = emulate(h.eng.cn, h.chunk, op, host, P)
+    mag = emulate(h.eng.cn, h.chunk, op, host, P, absolute=True)
+    k_of, rms_c = tolerances(case)
+    stats = check(got, ref, mag, host, outs, k_of, rms_c, what=case.name)
+    if case.det:
+        for k in got:
+            assert torch.equal(got[k].view(torch.int32), again[k].view(torch.int32)), \
+                f"{case.name}: a second run differs in space {k} (route without float atomics)"
+    return census, stats
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_route(case):
+    census, _ = run_case(case)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if case.cu and cus != MI355X_CUS:
+        pytest.skip(f"route of {case.name} assumes {MI355X_CUS} CUs, this device has {cus} (numbers checked)")
+    assert census == {case.route: 1}, f"{case.name}: expected the route {case.route}, the census shows {census}"
+
+
+def test_table_reaches_every_route():
+    lib = nv.load()
+    every = set(all_routes(lib))
+    table = {c.route for c in CASES}
+    assert AB_ONLY <= every and SQSUM_ROUTES <= every
+    assert {r for r in every if "sqsum" in r} == SQSUM_ROUTES
+    assert not (table & AB_ONLY), sorted(table & AB_ONLY)
+    missing = every - AB_ONLY - SQSUM_ROUTES - table
+    assert not missing, f"routes without a case in kernel_route_cases.py: {sorted(missing)}"
+    assert table <= every, sorted(table - every)
+
+
+# ---------------------------------------------------------------------------------------------- paths run_op cannot reach
+def _net_a():
+    """square-sum tiles <2,2,1,2>, <4,1,1,2>, <2,2,2,2>, <4,1,1,1>, the dense square sum and the bias reduce"""
+    from lip_amd.netspec import NetSpec
+    net = NetSpec((6, 6, 3))
+    x = net.conv(0, "Conv_0", 72, 3, 1, padding=1, act="relu", use_bias=True)       # M = 27, N = 72
+    x = net.conv(x, "Conv_1", 40, 3, 1, padding=1, act="relu")                      # M = 648, N = 40
+    x = net.conv(x, "Conv_2", 80, 3, 1, padding=1, act="relu")                      # M = 360, N = 80
+    x = net.conv(x, "Conv_3", 20, 3, 1, padding=1, act="relu")                      # M = 720, N = 20
+    x = net.meanpool(x)
+    net.dense(x, "Dense_0", 5)
+    net.model_type = "classifier"
+    return net
+
+
+def _net_b():
+    """square-sum tiles <2,2,1,1>, <2,1,1,1>; in lip_ggn_vp the fused-overwrite weight gradients of the 3 x 3 layer
+    (Winograd, one split) and of the last dense layer (skinny)"""
+    from lip_amd.netspec import NetSpec
+    net = NetSpec((8, 8, 32))
+    x = net.conv(0, "Conv_0", 32, 3, 1, padding=1, act="relu", use_bias=True)       # M = 288, N = 32
+    x = net.conv(x, "Conv_1", 48, 1, 1, padding=0, act="relu")                      # M = 32, N = 48
+    x = net.conv(x, "Conv_2", 16, 1, 1, padding=0, act="relu")                      # M = 48, N = 16
+    x = net.meanpool(x)
+    x = net.dense(x, "Dense_0", 40, act="relu")
+    net.dense(x, "Dense_1", 5)                                                       # M = 40, R = n
+    net.model_type = "classifier"
+    return net
+
+
+def _net_c():
+    """lip_ggn_vp on a 3 x 3 layer whose Winograd weight gradient splits (float atomics into the initialised block)"""
+    from lip_amd.netspec import NetSpec
+    net = NetSpec((32, 32, 32))
+    x = net.conv(0, "Conv_0", 32, 3, 1, padding=1, act="relu")
+    x = net.meanpool(x)
+    net.dense(x, "Dense_0", 3)
+    net.model_type = "classifier"
+    return net
+
+
+def _census(lib):
+    import ctypes as C
+    n = lib.lip_debug_route_count()
+    counts, names = (C.c_int64 * n)(), (C.c_char_p * n)()
+    nv.check(lib.lip_debug_routes(counts, n, names), "lip_debug_routes")
+    return {names[i].decode(): counts[i] for i in range(n) if counts[i]}
+
+
+def _tensor_slices(params):
+    from lip_amd.utils import _walk, nn_param_tree
+    out, o = [], 0
+    for name, leaf in _walk(nn_param_tree(params)):
+        n = torch.as_tensor(leaf).numel()
+        out.append((name, o, o + n))
+        o += n
+    return out
+
+
+def _per_tensor(got, ref, slices, tol, what):
+    """max |got - ref| over each parameter tensor, scaled by that tensor's max |ref|"""
+    got = got.double().cpu().reshape(-1, ref.shape[-1])
+    ref = ref.reshape(-1, ref.shape[-1])
+    for name, a, b in slices:
+        s = ref[:, a:b].abs().max().item()
+        err = (got[:, a:b] - ref[:, a:b]).abs().max().item()
+        assert err <= tol * s + 1e-30, f"{what}: parameter tensor {name}: max err {err:.3e} > {tol} x {s:.3e}"
+
+
+def _bind(net, n, seed, P):
+    from lip_amd.engine import LinearizedNet, build_consts
+    from lip_amd.toymodels import create_state
+    from lip_amd.utils import flatten_nn_params
+    from tape_emulator import TapeMachine
+    state = create_state(net, seed, dtype=torch.float64)
+    Z = torch.rand(n, *net.tensors[0], dtype=torch.float64, generator=torch.Generator().manual_seed(seed))
+    eng = LinearizedNet(state, Z, "classifier", workspace_bytes=1 << 28, max_chunk=P)
+    flat, _ = flatten_nn_params(state.params)
+    tm = TapeMachine(eng.cn, flat, build_consts(eng.cn, state.params, state.batch_stats, "cpu", torch.float64), Z, chunk=eng.chunk)
+    tm.primal()
+    return eng, tm, _tensor_slices(state.params)
+
+
+@pytest.mark.parametrize("which", ["a", "b"])
+def test_sqsum_and_rows_routes(which):
+    """lip_vjp_sqsum element by element against float64 squares of the emulator's per-example rows, lip_vjp_rows
+    against those rows; the census shows the square-sum routes."""
+    net = _net_a() if which == "a" else _net_b()
+    n, P = 3, 2
+    eng, tm, slices = _bind(net, n, 7, P)
+    U = torch.randn(P, n, eng.K, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+    rows = torch.zeros(P, n, eng.D, dtype=torch.float64)
+    for i in range(n):
+        Ui = torch.zeros_like(U)
+        Ui[:, i] = U[:, i]
+        rows[:, i] = tm.vjp(Ui, nv.HEAD_L, 0.7)
+    ref = (rows ** 2).sum((0, 1))
+    lib = eng.lib
+    all_routes(lib)                                  # clear the census
+    y0 = (torch.rand(eng.D, dtype=torch.float64, generator=torch.Generator().manual_seed(5)) * ref).float().cuda()
+    got = eng.vjp_sqsum(U, "l", 0.7, out=y0.clone())  # the square sum is ADDED to y0
+    torch.cuda.synchronize()
+    census = set(_census(lib))
+    want = y0.double().cpu() + ref
+    _per_tensor(got, want[None], slices, 1e-5, f"sqsum net {which}")
+    # element by element: a row element r with error e <= k 2^-24 max|r| (its tensor's rows) moves r^2 by ~2 |r| e, so
+    # |y_j - want_j| <= 2^-24 (K_SQ sum_{p,i} |r_pij| max_t|r| + 4 want_j)
+    err = (got.double().cpu() - want).abs()
+    unit = torch.zeros_like(want)
+    sabs = rows.abs().sum((0, 1))
+    for name, a, b in slices:
+        unit[a:b] = 2.0 ** -24 * sabs[a:b] * rows[:, :, a:b].abs().max()
+    worst = ((err - 2.0 ** -24 * 4 * want).clamp_min(0) / unit.clamp_min(1e-300)).max().item()
+    assert (err <= K_SQ * unit + 2.0 ** -24 * 4 * want + 1e-30).all(), \
+        f"sqsum net {which}: worst error {worst:.3g} x 2^-24 sum|r| max|r| > {K_SQ}"
+    again = eng.vjp_sqsum(U, "l", 0.7, out=y0.clone())
+    assert torch.equal(again, got), "lip_vjp_sqsum is not bitwise reproducible"
+    r = eng.vjp_rows(U, "l", 0.7)
+    _per_tensor(r, rows.reshape(P * n, -1), slices, 2e-5, f"rows net {which}")
+    want = SQSUM_NETS[which]
+    assert want <= census, f"net {which}: square-sum routes {sorted(want - census)} not taken (census {sorted(census)})"
+
+
+@pytest.mark.parametrize("which", ["b", "c"])
+def test_ggn_vp_fused_overwrite(which):
+    """lip_ggn_vp with alpha != 0: the weight gradients that WRITE y = s acc + alpha v (skinny, Winograd with one split)
+    and the Winograd gradient with several splits that adds into the alpha v block, per parameter tensor vs float64"""
+    net = _net_b() if which == "b" else _net_c()
+    n, P = (3, 2) if which == "b" else (4, 2)
+    eng, tm, slices = _bind(net, n, 11, P)
+    V = torch.randn(P, eng.D, dtype=torch.float64, generator=torch.Generator().manual_seed(4))
+    all_routes(eng.lib)
+    Y = eng.ggn_vp(V, 1.7, 0.37)
+    torch.cuda.synchronize()
+    census = _census(eng.lib)
+    ref = tm.ggn_vp(V, 1.7, 0.37)
+    _per_tensor(Y, ref, slices, 2e-5, f"ggn_vp net {which}")
+    want = {"b": {"wgrad_wino/rowq", "wgrad_skinny<2,8>"}, "c": {"wgrad_wino/rowq"}}[which]
+    assert want <= set(census), f"net {which}: routes {sorted(want - set(census))} not taken (census {census})"

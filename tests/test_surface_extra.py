@@ -141,6 +141,13 @@ def test_cifar_resnet1m_full_size_properties():
     Y256 = vp(V256)
     assert (Y256[:16] - Y).abs().max().item() <= 2e-5 * Y.abs().max().item()
     assert torch.isfinite(Y256).all()
+    # late probe positions of the same block against the float64 oracle: rows 127 and 128 sit on either side of a
+    # probe-group boundary of the probe-batched weight gradient, row 255 is in its last group
+    ref_vp = og.compute_ggn_vp_batched(st64, Z, "classifier", full_set_size=49000)
+    for r in (127, 128, 255):
+        ref = ref_vp(cpu64(V256[r]))
+        err = (cpu64(Y256[r]) - ref).abs().max() / ref.abs().max()
+        assert err < 2e-4, (r, err)
     # per-example rows at full size: their sum over examples is the summed product
     eng = vp.engine
     U = torch.randn(4, eng.n, eng.K, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
