@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "lip.h"
 
 namespace lip {
@@ -133,6 +134,34 @@ struct HeadP {
   int n, K, mode, classifier; float c;
 };
 
+// ---- code path of the non-GEMM kernels that pick one from the channel count and the pointer alignment ----------
+// One predicate per kernel, used by the kernel (per block, on the block's own pointers) and by its launcher (per probe,
+// for the route census), so a census label cannot drift from the branch that ran.
+enum SmallPath { SP_QUAD = 0, SP_QUAD_WIDE = 1, SP_FIXED = 2, SP_ATOMIC = 3, SP_MIXED = 4 };
+
+__host__ __device__ __forceinline__ bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
+// reduce_kernel: g, xh are the first row of the block (xh may be null)
+__host__ __device__ __forceinline__ int reduce_path(int N, const float* g, const float* xh) {
+  if ((N & 3) == 0 && aligned16(g, xh)) return (N >> 2) <= 256 ? SP_QUAD : SP_QUAD_WIDE;
+  return (N <= 256 && (256 % N) == 0) ? SP_FIXED : SP_ATOMIC;
+}
+// pool_fwd_kernel: in is the first pixel of the (probe, example) map
+__host__ __device__ __forceinline__ int pool_fwd_path(int C, const float* in) {
+  if (C <= 256 && (256 % C) == 0) return SP_FIXED;
+  return ((C & 3) == 0 && aligned16(in)) ? SP_QUAD : SP_ATOMIC;
+}
+// pool_bwd_kernel: in / out / dphi / xhat at the block's first element (dphi, xhat may be null)
+__host__ __device__ __forceinline__ int pool_bwd_path(int C, const float* in, const float* out, const float* dphi, const float* xhat) {
+  if ((256 % C) == 0) return SP_FIXED;
+  return ((C & 3) == 0 && aligned16(in, out, dphi, xhat)) ? SP_QUAD : SP_ATOMIC;
+}
+// head_kernel: plain scaling (regressor, or the OUT / IN modes) against the softmax factor actions
+__host__ __device__ __forceinline__ bool head_scales(int classifier, int mode) {
+  return !classifier || mode == LIP_HEAD_OUT || mode == LIP_HEAD_IN;
+}
+
 // ---- launchers (return hipError_t of the launch) ------------------------------------------
 hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st);
 hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st);
@@ -186,6 +215,21 @@ int routes_read(int64_t* counts, int n, const char** names);
   do {                                                                  \
     static const int lip_route_slot_ = ::lip::route_id(__VA_ARGS__);    \
     ::lip::route_hit(lip_route_slot_);                                  \
+  } while (0)
+
+// a launch site whose name depends on a run-time key in [0, nkeys): one cached slot per key
+#define LIP_ROUTE_KEYED(key, nkeys, ...)                                \
+  do {                                                                  \
+    static std::atomic<int> lip_route_slots_[nkeys];                    \
+    int lip_slot_ = lip_route_slots_[key].load(std::memory_order_relaxed) - 1;             \
+    if (lip_slot_ < 0) { lip_slot_ = ::lip::route_id(__VA_ARGS__); lip_route_slots_[key].store(lip_slot_ + 1, std::memory_order_relaxed); } \
+    ::lip::route_hit(lip_slot_);                                        \
+  } while (0)
+// "<kernel>/quad | quad_wide | fixed | atomic | mixed" from a SmallPath (mixed: the probes of one launch differ)
+#define LIP_ROUTE_PATH(kernel, path)                                    \
+  do {                                                                  \
+    static const char* const lip_pn_[5] = {"quad", "quad_wide", "fixed", "atomic", "mixed"};  \
+    LIP_ROUTE_KEYED(path, 5, kernel "/%s", lip_pn_[path]);              \
   } while (0)
 
 void set_error(const char* fmt, ...);

@@ -2769,9 +2769,9 @@ hipError_t launch_gemm_nn_axpy(const float* T, long long ldt, int m, int k, cons
 }
 
 // ------------------------------------------------------------------------------------------
-// route census: every launch route of the conv GEMM dispatchers (launch_igemm, launch_wgrad) and of the square-sum
-// kernels, in the names LIP_ROUTE forms at the launch sites.  tests/test_kernel_routes.py reaches each of them except
-// the A/B-only ones it lists; a route missing here still counts (in a slot appended at its first launch) but is not
+// route census: every launch route of the conv GEMM dispatchers (launch_igemm, launch_wgrad), of the square-sum
+// kernels and of the non-GEMM kernels, in the names LIP_ROUTE forms at the launch sites.  tests/test_kernel_routes.py
+// and tests/test_small_ops.py reach each of them except the A/B-only ones the former lists; a route missing here still counts (in a slot appended at its first launch) but is not
 // part of that coverage check — add new routes to this table.  The LIP_TILE experiment tiles are not listed.
 // ------------------------------------------------------------------------------------------
 #define LIP_T6(pre, post) pre "<2,2,1,2>" post, pre "<2,2,2,2>" post, pre "<2,2,1,1>" post, pre "<4,1,1,2>" post, \
@@ -2788,6 +2788,15 @@ static const char* const kRoutes[] = {
     "wgrad_fast<2,2,2,2>/x3", "wgrad_fast<4,1,1,2>/x3", "wgrad_fast<2,1,1,1>/x3", "wgrad_fast<4,1,1,1>/x3",
     LIP_T6("wgrad_fast", ""), LIP_T6("wgrad", ""),
     LIP_T6("wgrad_sqsum", ""), "wgrad_sqsum_dense", "reduce_sqsum",
+    // the non-GEMM kernels of lip_small.hip (tests/test_small_ops.py): the code path a launch takes
+    "reduce/quad", "reduce/quad_wide", "reduce/fixed", "reduce/atomic", "reduce/mixed", "reduce/rows",
+    "pool_fwd/quad", "pool_fwd/fixed", "pool_fwd/atomic", "pool_fwd/mixed",
+    "pool_bwd/quad", "pool_bwd/fixed", "pool_bwd/atomic", "pool_bwd/mixed",
+    "maxpool_primal/max", "maxpool_primal/avg", "maxpool_fwd/max", "maxpool_fwd/avg",
+    "maxpool_bwd/quad", "maxpool_bwd/scalar", "maxpool_bwd/quad/avg", "maxpool_bwd/scalar/avg",
+    "primal_post/none", "primal_post/relu", "primal_post/tanh", "primal_post/gelu",
+    "primal_post/none/bn", "primal_post/relu/bn", "primal_post/tanh/bn", "primal_post/gelu/bn",
+    "softmax", "head/ggn", "head/lt", "head/l", "head/scale",
 };
 #undef LIP_T6
 

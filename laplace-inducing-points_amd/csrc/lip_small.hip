@@ -22,8 +22,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceP prm) {
   const float* g = prm.g + (long long)p * prm.g_ps + seg0 + (long long)rbeg * N;
   const float* xh = prm.xhat ? prm.xhat + seg0 + (long long)rbeg * N : nullptr;
   const long long cnt = (long long)rows * N;
-  const bool quads = (N & 3) == 0 && (((uintptr_t)g | (uintptr_t)xh) & 15) == 0;
-  if (quads) {
+  const int path = reduce_path(N, g, xh);
+  if (path == SP_QUAD || path == SP_QUAD_WIDE) {
     const int nq = N >> 2;
     const int groups = nq <= 256 ? 256 / nq : 1;                 // row groups working side by side
     const int rg = nq <= 256 ? (int)threadIdx.x / nq : 0;
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceP prm) {
       atomicAdd(&s0[4 * cq], a0.x); atomicAdd(&s0[4 * cq + 1], a0.y); atomicAdd(&s0[4 * cq + 2], a0.z); atomicAdd(&s0[4 * cq + 3], a0.w);
       if (xh) { atomicAdd(&s1[4 * cq], a1.x); atomicAdd(&s1[4 * cq + 1], a1.y); atomicAdd(&s1[4 * cq + 2], a1.z); atomicAdd(&s1[4 * cq + 3], a1.w); }
     }
-  } else if (N <= 256 && (256 % N) == 0) {
+  } else if (path == SP_FIXED) {
     // fixed channel per thread: accumulate privately, one LDS atomic per thread
     const int c = threadIdx.x % N;
     float a0 = 0.f, a1 = 0.f;
@@ -73,6 +73,12 @@ hipError_t launch_reduce(const ReduceP& p0, int P, hipStream_t st) {
   p.rpb = 128;
   while (p.rpb > 16 && (long long)((p.R + p.rpb - 1) / p.rpb) * segs < 2048) p.rpb >>= 1;
   dim3 grid((p.R + p.rpb - 1) / p.rpb, P, p.nseg > 0 ? p.nseg : 1);
+  // with N % 4 == 0 every row block and segment of a probe starts on the alignment of the probe's first row
+  int path = reduce_path(p.N, p.g, p.xhat);
+  for (int q = 1; q < P && q < 4; ++q)
+    if (reduce_path(p.N, p.g + (long long)q * p.g_ps, p.xhat) != path) path = SP_MIXED;
+  LIP_ROUTE_PATH("reduce", path);
+  if (p.nseg > 0) LIP_ROUTE("reduce/rows");
   hipLaunchKernelGGL(reduce_kernel, grid, dim3(256), 2 * p.N * sizeof(float), st, p);
   return hipGetLastError();
 }
@@ -193,13 +199,14 @@ hipError_t launch_sqsum_finish(const float* partial, int G, long long len, float
 
 // ---- mean pool over pixels: out[p][i][c] = inv * sum_pix in[p][i][pix][c]  (jnp.mean(x,(1,2))) ------
 __global__ __launch_bounds__(256) void pool_fwd_kernel(const PoolP prm) {
-  extern __shared__ float sm[];           // [C]
+  extern __shared__ float sm[];           // [C + 256]
   const int C = prm.C, i = blockIdx.x, p = blockIdx.y;
   for (int c = threadIdx.x; c < C; c += 256) sm[c] = 0.f;
   __syncthreads();
   const float* in = prm.in + (long long)p * prm.in_ps + (long long)i * prm.HW * C;
   const long long cnt = (long long)prm.HW * C;
-  if ((C & 3) == 0 && ((uintptr_t)in & 15) == 0 && !(C <= 256 && (256 % C) == 0)) {
+  const int path = pool_fwd_path(C, in);
+  if (path == SP_QUAD) {
     // a thread owns whole channel quads: float4 loads down the pixels, no LDS traffic (wide layers: the per-element
     // LDS atomic + modulo of the general branch ran ResNet-50's 2048-channel pool at 0.3 TB/s)
     for (int cq = threadIdx.x; cq < (C >> 2); cq += 256) {
@@ -211,13 +218,26 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const PoolP prm) {
       }
       sm[4 * cq] = a.x; sm[4 * cq + 1] = a.y; sm[4 * cq + 2] = a.z; sm[4 * cq + 3] = a.w;
     }
-  } else if (C <= 256 && (256 % C) == 0) {
-    const int c = threadIdx.x % C;
+  } else if (path == SP_FIXED) {
+    // a thread keeps one channel; the 256 / C partial sums of a channel meet in LDS and are added in thread order (LDS
+    // float atomics here made the tangent differ from run to run)
+    float* part = sm + C;                 // [256]
     float a = 0.f;
     for (long long idx = threadIdx.x; idx < cnt; idx += 256) a += in[idx];
-    atomicAdd(&sm[c], a);
+    part[threadIdx.x] = a;
+    __syncthreads();
+    if ((int)threadIdx.x < C) {
+      float t = 0.f;
+      for (int k = threadIdx.x; k < 256; k += C) t += part[k];
+      sm[threadIdx.x] = t;
+    }
   } else {
-    for (long long idx = threadIdx.x; idx < cnt; idx += 256) atomicAdd(&sm[idx % C], in[idx]);
+    // any other channel count or alignment: one channel per thread, pixels in order
+    for (int c = threadIdx.x; c < C; c += 256) {
+      float a = 0.f;
+      for (int px = 0; px < prm.HW; ++px) a += in[(long long)px * C + c];
+      sm[c] = a;
+    }
   }
   __syncthreads();
   float* out = prm.out + (long long)p * prm.out_ps + (long long)i * C;
@@ -225,7 +245,11 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const PoolP prm) {
 }
 
 hipError_t launch_pool_fwd(const PoolP& p, int P, hipStream_t st) {
-  hipLaunchKernelGGL(pool_fwd_kernel, dim3(p.n, P, 1), dim3(256), p.C * sizeof(float), st, p);
+  int path = pool_fwd_path(p.C, p.in);                 // C % 4 == 0: every example of a probe starts on the probe's alignment
+  for (int q = 1; q < P && q < 4; ++q)
+    if (pool_fwd_path(p.C, p.in + (long long)q * p.in_ps) != path) path = SP_MIXED;
+  LIP_ROUTE_PATH("pool_fwd", path);
+  hipLaunchKernelGGL(pool_fwd_kernel, dim3(p.n, P, 1), dim3(256), (p.C + 256) * sizeof(float), st, p);
   return hipGetLastError();
 }
 
@@ -248,10 +272,10 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const PoolP prm) {
   const long long cnt = (long long)npix * C;
   // 256 % C == 0: a thread keeps ONE channel for all its pixels, so the column sums accumulate in registers and
   // reach LDS once per thread (an LDS atomic per element made this broadcast kernel run at 0.4 TB/s)
-  const bool fixed_c = (256 % C) == 0;
+  const int path = pool_bwd_path(C, in, out, prm.dphi ? prm.dphi + base : nullptr, prm.xhat ? prm.xhat + base : nullptr);
+  const bool fixed_c = path == SP_FIXED;
   float a0 = 0.f, a1 = 0.f;
-  if (!fixed_c && (C & 3) == 0 && (((uintptr_t)in | (uintptr_t)out | (uintptr_t)(prm.dphi ? prm.dphi + base : nullptr) |
-                                    (uintptr_t)(prm.xhat ? prm.xhat + base : nullptr)) & 15) == 0) {
+  if (path == SP_QUAD) {
     // wide layers: a thread owns whole channel quads for all the block's pixels; sums stay in registers and go to the
     // per-probe totals directly (no LDS, no per-element atomics)
     for (int cq = threadIdx.x; cq < (C >> 2); cq += 256) {
@@ -310,6 +334,10 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const PoolP prm) {
 
 hipError_t launch_pool_bwd(const PoolP& p, int P, hipStream_t st) {
   dim3 grid((p.HW + PB_PIX - 1) / PB_PIX, p.n, P);
+  int path = pool_bwd_path(p.C, p.in, p.out, p.dphi, p.xhat);   // C % 4 == 0: blocks keep their probe's alignment
+  for (int q = 1; q < P && q < 4; ++q)
+    if (pool_bwd_path(p.C, p.in + (long long)q * p.in_ps, p.out + (long long)q * p.out_ps, p.dphi, p.xhat) != path) path = SP_MIXED;
+  LIP_ROUTE_PATH("pool_bwd", path);
   hipLaunchKernelGGL(pool_bwd_kernel, grid, dim3(256), 2 * p.C * sizeof(float), st, p);
   return hipGetLastError();
 }
@@ -347,6 +375,7 @@ __global__ __launch_bounds__(256) void maxpool_primal_kernel(const MaxPoolP prm)
 hipError_t launch_maxpool_primal(const MaxPoolP& p, hipStream_t st) {
   const long long total = (long long)p.n * p.OH * p.OW * p.C;
   const long long blocks = (total + 255) / 256;
+  if (p.amax_w) LIP_ROUTE("maxpool_primal/max"); else LIP_ROUTE("maxpool_primal/avg");
   hipLaunchKernelGGL(maxpool_primal_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, p);
   return hipGetLastError();
 }
@@ -385,6 +414,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const MaxPoolP prm) {
 hipError_t launch_maxpool_fwd(const MaxPoolP& p, int P, hipStream_t st) {
   const long long total = (long long)p.n * p.OH * p.OW * p.C;
   const long long blocks = (total + 255) / 256;
+  if (p.amax) LIP_ROUTE("maxpool_fwd/max"); else LIP_ROUTE("maxpool_fwd/avg");
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096), P), dim3(256), 0, st, p);
   return hipGetLastError();
 }
@@ -528,11 +558,13 @@ hipError_t launch_maxpool_bwd(const MaxPoolP& p, int P, hipStream_t st) {
     // few, long-lived blocks per probe: every block ends in 2 C global atomics on the same per-probe sums (4 096 blocks
     // per probe: 33 M contended atomics, 3.97 ms; 128 per probe: 0.4 ms)
     const long long blocks = (total / 4 + 255) / 256, want = 8192 / (P > 0 ? P : 1) > 8 ? 8192 / (P > 0 ? P : 1) : 8;
+    if (p.amax) LIP_ROUTE("maxpool_bwd/quad"); else LIP_ROUTE("maxpool_bwd/quad/avg");
     hipLaunchKernelGGL(maxpool_bwd_quad_kernel, dim3((unsigned)(blocks < want ? blocks : want), P), dim3(256),
                        2 * p.C * sizeof(float), st, p);
     return hipGetLastError();
   }
   const long long blocks = (total + 255) / 256;
+  if (p.amax) LIP_ROUTE("maxpool_bwd/scalar"); else LIP_ROUTE("maxpool_bwd/scalar/avg");
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048), P), dim3(256),
                      2 * p.C * sizeof(float), st, p);
   return hipGetLastError();
@@ -572,6 +604,8 @@ __global__ __launch_bounds__(256) void primal_post_kernel(const PrimalPostP prm)
 
 hipError_t launch_primal_post(const PrimalPostP& p, hipStream_t st) {
   const long long blocks = (p.count + 255) / 256;
+  static const char* const kAct[4] = {"none", "relu", "tanh", "gelu"};
+  if (p.act >= 0 && p.act < 4) LIP_ROUTE_KEYED(p.act * 2 + (p.gamma ? 1 : 0), 8, "primal_post/%s%s", kAct[p.act], p.gamma ? "/bn" : "");
   hipLaunchKernelGGL(primal_post_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, p);
   return hipGetLastError();
 }
@@ -596,6 +630,7 @@ __global__ __launch_bounds__(64) void softmax_kernel(const float* logits, float*
 }
 
 hipError_t launch_softmax(const float* logits, float* prob, float* sqrtp, int n, int K, hipStream_t st) {
+  LIP_ROUTE("softmax");
   hipLaunchKernelGGL(softmax_kernel, dim3(n), dim3(64), 0, st, logits, prob, sqrtp, n, K);
   return hipGetLastError();
 }
@@ -609,7 +644,7 @@ __global__ __launch_bounds__(64) void head_kernel(const HeadP prm) {
   const int i = blockIdx.x, p = blockIdx.y, lane = threadIdx.x, K = prm.K;
   const float* u = prm.in + (long long)p * prm.in_ps + (long long)i * K;
   float* o = prm.out + (long long)p * prm.out_ps + (long long)i * K;
-  if (!prm.classifier || prm.mode == LIP_HEAD_OUT || prm.mode == LIP_HEAD_IN) {
+  if (head_scales(prm.classifier, prm.mode)) {
     for (int k = lane; k < K; k += 64) o[k] = prm.c * u[k];
     return;
   }
@@ -629,6 +664,10 @@ __global__ __launch_bounds__(64) void head_kernel(const HeadP prm) {
 }
 
 hipError_t launch_head(const HeadP& p, int P, hipStream_t st) {
+  if (head_scales(p.classifier, p.mode)) LIP_ROUTE("head/scale");
+  else if (p.mode == LIP_HEAD_GGN) LIP_ROUTE("head/ggn");
+  else if (p.mode == LIP_HEAD_LT) LIP_ROUTE("head/lt");
+  else LIP_ROUTE("head/l");
   hipLaunchKernelGGL(head_kernel, dim3(p.n, P, 1), dim3(64), 0, st, p);
   return hipGetLastError();
 }

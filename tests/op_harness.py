@@ -1,4 +1,5 @@
-"""Op-level harness for the conv GEMM kernel routes — TEST INFRASTRUCTURE (a plain helper module).
+"""Op-level harness for the kernel routes — TEST INFRASTRUCTURE (a plain helper module; the specs and Mag of the
+non-GEMM ops are in its sibling small_op_harness.py).
 
 One synthetic IGEMM / WGRAD op is laid out in the caller-owned V, Y and H blocks (plus, for a few cases, the engine's
 WORK, PRIM and CONST buffers), run once through ``lip_engine_run_op`` and compared element by element with
@@ -203,7 +204,19 @@ class Harness:
             off, ps, base = L.alloc(sp, count, Pf)
             setattr(op, name, _ref(sp, off, ps))
             fills.append((sp, base, count, ps, Pf))
-        # buffers: everything canary, then the inputs and the accumulation prefills
+        host = self.buffers(L)
+        for sp, base, count, ps, Pn in fills:
+            for p in range(Pn):
+                v = torch.randn(count, generator=g, dtype=F64).float()
+                host[sp][base + p * ps: base + p * ps + count] = v
+        for name, sp, base, count, ps, Pn, pre in outs:
+            if pre:
+                for p in range(Pn):
+                    host[sp][base + p * ps: base + p * ps + count] = torch.randn(count, generator=g, dtype=F64).float()
+        return op, L, host, outs
+
+    def buffers(self, L):
+        """host copies of every space, sized by the layout, every float a canary"""
         eng = self.eng
         sizes = {k: L.size(k) for k in "VYH"}
         host = {k: torch.full((sizes[k],), 0, dtype=torch.int32).view(torch.float32) for k in "VYH"}
@@ -216,15 +229,7 @@ class Harness:
             host[k] = torch.full((t.numel(),), 0, dtype=torch.int32)
             host[k].fill_(CANARY)
             host[k] = host[k].view(torch.float32)
-        for sp, base, count, ps, Pn in fills:
-            for p in range(Pn):
-                v = torch.randn(count, generator=g, dtype=F64).float()
-                host[sp][base + p * ps: base + p * ps + count] = v
-        for name, sp, base, count, ps, Pn, pre in outs:
-            if pre:
-                for p in range(Pn):
-                    host[sp][base + p * ps: base + p * ps + count] = torch.randn(count, generator=g, dtype=F64).float()
-        return op, L, host, outs
+        return host
 
     def upload(self, host):
         eng = self.eng
@@ -234,10 +239,14 @@ class Harness:
         eng.consts.copy_(host["C"])
         return dev
 
-    def run(self, op, dev, P):
-        nv.check(self.lib.lip_engine_run_op(self.eng.h, op, nv.ptr(dev["V"]), nv.ptr(dev["Y"]), nv.ptr(dev["H"]), P, 0,
-                                            1.0, nv.stream_ptr()), "lip_engine_run_op")
+    def run(self, op, dev, P, head_mode=0, head_c=1.0):
+        nv.check(self.run_rc(op, dev, P, head_mode, head_c), "lip_engine_run_op")
         torch.cuda.synchronize()
+
+    def run_rc(self, op, dev, P, head_mode=0, head_c=1.0):
+        """the return code of lip_engine_run_op (for ops the engine must refuse)"""
+        return self.lib.lip_engine_run_op(self.eng.h, op, nv.ptr(dev["V"]), nv.ptr(dev["Y"]), nv.ptr(dev["H"]), P, head_mode,
+                                          head_c, nv.stream_ptr())
 
     def download(self, dev):
         eng = self.eng
@@ -245,20 +254,31 @@ class Harness:
         out["W"], out["P"], out["C"] = eng.work.cpu(), eng.prim.cpu(), eng.consts.cpu()
         return out
 
-    def emulate(self, op, host, P, absolute=False):
-        return emulate(self.eng.cn, self.chunk, op, host, P, absolute)
+    def emulate(self, op, host, P, absolute=False, head_mode=0, head_c=1.0):
+        return emulate(self.eng.cn, self.chunk, op, host, P, absolute, head_mode, head_c)
 
 
-def emulate(cn, chunk, op, host, P, absolute=False):
-    """float64 result of the op on copies of the host buffers (absolute: on |every operand|, giving Mag)."""
-    from tape_emulator import TapeMachine
-    tm = TapeMachine.__new__(TapeMachine)
+def _machine(cls, cn, chunk, b):
+    tm = cls.__new__(cls)
     tm.cn, tm.chunk = cn, chunk
-    b = {k: (host[k].double().abs() if absolute else host[k].double()) for k in host}
     tm.V, tm.Y, tm.H = b["V"], b["Y"], b["H"]
     tm.work, tm.prim, tm.consts = b["W"], b["P"], b["C"]
     tm.theta = torch.zeros(1, dtype=F64)
-    tm.run_op(op, P)
+    return tm
+
+
+def emulate(cn, chunk, op, host, P, absolute=False, head_mode=0, head_c=1.0):
+    """float64 result of the op on copies of the host buffers (absolute: on |every operand|, giving Mag; the ops that
+    subtract or are not linear take their Mag from small_op_harness.MagMachine)."""
+    from tape_emulator import TapeMachine
+    b = {k: (host[k].double().abs() if absolute else host[k].double()) for k in host}
+    if absolute and op.kind in (nv.OP_HEAD, nv.OP_PRIMAL_POST, nv.OP_SOFTMAX):
+        from small_op_harness import MagMachine
+        tm = _machine(MagMachine, cn, chunk, b)
+        tm.signed = _machine(TapeMachine, cn, chunk, {k: host[k].double() for k in host})
+    else:
+        tm = _machine(TapeMachine, cn, chunk, b)
+    tm.run_op(op, P, head_mode, abs(head_c) if absolute else head_c)
     return b
 
 
@@ -271,9 +291,14 @@ def output_mask(host, outs):
     return m
 
 
-def check(got, ref, mag, host, outs, k_of, rms_c, what=""):
+def check(got, ref, mag, host, outs, k_of, rms_c, what="", exact=(), skip=None, floor=None):
     """element-wise + RMS bound on every output, canaries and inputs bitwise unchanged.  k_of(name) -> (k, kref) where
-    kref scales the RMS bound (sqrt(kref) * rms_c).  Returns {output name: (max normalised err, rms normalised err)}."""
+    kref scales the RMS bound (sqrt(kref) * rms_c), or (k, kref, rms_c) with a constant of its own for that output.
+    Returns {output name: (max normalised err, rms normalised err)}.
+
+    exact: output names that must equal the float32 value of the reference bitwise (gathers: no Mag).
+    skip: {output name: bool mask over the output's (probe, element) order} of elements left out of the comparison
+    (they must still be written and finite).  floor: {output name: absolute error allowed on top of the bound}."""
     mask = output_mask(host, outs)
     for k in host:
         keep = ~mask[k]
@@ -290,16 +315,31 @@ def check(got, ref, mag, host, outs, k_of, rms_c, what=""):
         r = ref[sp][idx]
         M = mag[sp][idx]
         assert torch.isfinite(y).all(), f"{what}: {name}: {int((~torch.isfinite(y)).sum())} elements not written or not finite"
-        k, kref = k_of(name)
-        e = (y - r).abs() / (U24 * M + TINY)
+        if name in exact:
+            a, b = got[sp][idx].view(torch.int32), r.float().view(torch.int32)
+            if skip is not None and name in skip:
+                a, b = a[~skip[name]], b[~skip[name]]
+            ne = a != b
+            if ne.any():
+                i = int(torch.nonzero(ne)[0])
+                raise AssertionError(f"{what}: {name}: {int(ne.sum())} of {ne.numel()} elements differ bitwise from the float32 "
+                                     f"reference (first at {i}: got bits {int(a[i]):#x}, ref bits {int(b[i]):#x})")
+            stats[name] = (0.0, 0.0)
+            continue
+        kk = k_of(name)
+        k, kref = kk[0], kk[1]
+        c_rms = kk[2] if len(kk) > 2 else rms_c
+        e = ((y - r).abs() - (floor or {}).get(name, 0.0)).clamp_min(0) / (U24 * M + TINY)
+        if skip is not None and name in skip:
+            e = e[~skip[name]]
         bad = e > k
         if bad.any():
             i = int(torch.argmax(e))
             raise AssertionError(f"{what}: {name}: {int(bad.sum())} of {e.numel()} elements above {k:.3g} * 2^-24 * Mag "
                                  f"(worst {e[i].item():.3g} at {i}: got {y[i].item():.9g}, ref {r[i].item():.9g}, Mag {M[i].item():.3g})")
         rms = e.pow(2).mean().sqrt().item()
-        bound = rms_c * math.sqrt(kref)
-        assert rms <= bound, f"{what}: {name}: RMS of the normalised error {rms:.4g} above {bound:.4g} (= {rms_c} sqrt({kref}))"
+        bound = c_rms * math.sqrt(kref)
+        assert rms <= bound, f"{what}: {name}: RMS of the normalised error {rms:.4g} above {bound:.4g} (= {c_rms} sqrt({kref}))"
         stats[name] = (e.max().item(), rms / math.sqrt(kref))
     return stats
 
