@@ -209,8 +209,11 @@ int lip_multi_axpy_norm(const float* Q, const float* c, float* w, float* nrm2 /*
 /* Q[p][j] = w[p] * rsqrt(nrm2[p])   (next Lanczos vector; the row padding is zeroed)     */
 int lip_scale_store(const float* w, const float* nrm2, float* Q, int32_t j, int32_t P, int32_t kmax, int64_t N,
                     int64_t ldq, void* stream);
-/* fused CG update (one pass): x += a p; r -= a Ap; rr[p] = <r,r>, a[p] = rr_old[p]/pAp[p]; inactive probes
- * (active[p]==0) are left untouched.                                                     */
+/* fused CG update (one pass): x += a p; r -= a Ap; rr[p] = <r,r>, a[p] = rr_old[p]/pAp[p]; the rows x[p], r[p] of
+ * inactive probes (active[p]==0; active == NULL: every probe is active) are left untouched and their rr_new[p] is
+ * set to 0 (rr_new is zeroed before the pass): a caller keeps its own rr of an inactive probe.  The four blocks must
+ * share their alignment modulo 16 bytes (any 4-byte alignment), as must X, Y of lip_bdot / lip_axpby and p, r of
+ * lip_cg_direction.                                                                       */
 int lip_cg_update(float* x, float* r, const float* p, const float* Ap, const float* rr_old, const float* pAp,
                   const int32_t* active, float* rr_new /*[P], overwritten*/, int32_t P, int64_t N, void* stream);
 /* p = r + (rr_new/rr_old) p                                                              */

@@ -765,16 +765,18 @@ int lip_dot_nt_f64(const float* A, int64_t lda, int32_t m, const float* B, int64
   static const bool valu = getenv("LIP_DOT_NT_VALU") != nullptr;          // A/B switch: the VALU / LDS kernel
   static const bool noquad = getenv("LIP_DOT_NT_NOQUAD") != nullptr;      // A/B switch: one tile per block, waves split K
   const int tm32 = (m + DT_B - 1) / DT_B, tn32 = (n + DT_B - 1) / DT_B;
-  if (valu)
+  if (valu) {
+    if (part) LIP_ROUTE("dot_nt/valu/part"); else LIP_ROUTE("dot_nt/valu/atomic");
     hipLaunchKernelGGL(dot_nt_f64_kernel, dim3((unsigned)tiles, (unsigned)ks), dim3(256), 0, st, A, (long long)lda, m, B,
                        (long long)ldb, n, (long long)K, kper, C, part);
-  else if (!noquad && tm32 >= 2 && tn32 >= 2 && (!part || tiles * ks * 4 <= DT_SCRATCH_TILES) && chunks / (ks * 4) >= 4) {
+  } else if (!noquad && tm32 >= 2 && tn32 >= 2 && (!part || tiles * ks * 4 <= DT_SCRATCH_TILES) && chunks / (ks * 4) >= 4) {
     // a wave per tile and K-split: four times the K-splits keep the number of waves (a wave of the other form sweeps a
     // quarter of its block's K-range)
     long long ks4 = ks * 4;
     const long long kper4 = (chunks + ks4 - 1) / ks4 * DT_KC;
     ks4 = (K + kper4 - 1) / kper4;
     const unsigned blocks = (unsigned)(((tm32 + 1) / 2) * ((tn32 + 1) / 2));
+    if (part) LIP_ROUTE("dot_nt/quad/part"); else LIP_ROUTE("dot_nt/quad/atomic");
     hipLaunchKernelGGL((dot_nt_f64_mfma_kernel<true>), dim3(blocks, (unsigned)ks4), dim3(256), 0, st, A, (long long)lda, m, B,
                        (long long)ldb, n, (long long)K, kper4, C, part);
     LIP_CHECK_HIP(hipGetLastError());
@@ -783,9 +785,11 @@ int lip_dot_nt_f64(const float* A, int64_t lda, int32_t m, const float* B, int64
       LIP_CHECK_HIP(hipGetLastError());
     }
     return LIP_OK;
-  } else
+  } else {
+    if (part) LIP_ROUTE("dot_nt/tile/part"); else LIP_ROUTE("dot_nt/tile/atomic");
     hipLaunchKernelGGL((dot_nt_f64_mfma_kernel<false>), dim3((unsigned)tiles, (unsigned)ks), dim3(256), 0, st, A, (long long)lda, m, B,
                        (long long)ldb, n, (long long)K, kper, C, part);
+  }
   LIP_CHECK_HIP(hipGetLastError());
   if (part) {
     hipLaunchKernelGGL(dot_nt_reduce_kernel, dim3((unsigned)(tiles * 16)), dim3(1024), 0, st, part, (int)tiles, (int)ks, m, n, C);
@@ -826,12 +830,15 @@ int lip_rows_combine(const double* Cm, const float* Y, int64_t ldy, int32_t s, c
   if (Out == Y || Out == Z) { set_error("lip_rows_combine: the output must not alias an input"); return LIP_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   const unsigned ny = (unsigned)((N + 1023) / 1024);
-  if (r <= 4 || s > 1365)        // the coefficient tile lives in LDS (RT * s floats <= 64 KiB): 12 rows up to s = 1365, 4 rows up to 4096
+  if (r <= 4 || s > 1365) {      // the coefficient tile lives in LDS (RT * s floats <= 64 KiB): 12 rows up to s = 1365, 4 rows up to 4096
+    LIP_ROUTE("rows_combine<4>");
     hipLaunchKernelGGL((rows_combine_kernel<4>), dim3((unsigned)((r + 3) / 4), ny), dim3(256), sizeof(float) * 4 * s, st, Cm, Y,
                        (long long)ldy, s, Z, (long long)ldz, zscale, Out, (long long)ldo, r, (long long)N);
-  else
+  } else {
+    LIP_ROUTE("rows_combine<12>");
     hipLaunchKernelGGL((rows_combine_kernel<12>), dim3((unsigned)((r + 11) / 12), ny), dim3(256), sizeof(float) * 12 * s, st, Cm, Y,
                        (long long)ldy, s, Z, (long long)ldz, zscale, Out, (long long)ldo, r, (long long)N);
+  }
   LIP_CHECK_HIP(hipGetLastError());
   return LIP_OK;
 }
@@ -839,6 +846,7 @@ int lip_rows_combine(const double* Cm, const float* Y, int64_t ldy, int32_t s, c
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream) {
   if (!X || P <= 0 || N <= 0) { set_error("lip_fill_rademacher: bad argument"); return LIP_ERR_ARG; }
   const long long total = (long long)P * N;
+  LIP_ROUTE("fill_rademacher");
   hipLaunchKernelGGL(fill_rademacher_kernel, dim3(nblk_for(total, KT * 128, 16384)), dim3(KT), 0, (hipStream_t)stream, X, total,
                      (unsigned long long)seed);
   LIP_CHECK_HIP(hipGetLastError());
@@ -848,6 +856,7 @@ int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* str
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream) {
   if (!X || P <= 0 || N <= 0) { set_error("lip_fill_normal: bad argument"); return LIP_ERR_ARG; }
   const long long total = (long long)P * N;
+  LIP_ROUTE("fill_normal");
   hipLaunchKernelGGL((fill_kernel<true>), dim3(nblk_for(total, KT * 16, 8192)), dim3(KT), 0, (hipStream_t)stream, X, total,
                      (unsigned long long)seed);
   LIP_CHECK_HIP(hipGetLastError());

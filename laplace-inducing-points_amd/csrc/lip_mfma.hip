@@ -2602,6 +2602,7 @@ hipError_t launch_gemm_nt(const float* A, long long lda, int m, const float* B, 
   ks = (K + p.kper - 1) / p.kper;
   hipError_t e = hipMemsetAsync(C, 0, sizeof(float) * (size_t)m * n, st);
   if (e != hipSuccess) return e;
+  if (ks == 1) LIP_ROUTE("gemm_nt/ks1"); else LIP_ROUTE("gemm_nt/ks");
   hipLaunchKernelGGL(gemm_nt_kernel, dim3((unsigned)tiles, (unsigned)ks), dim3(256), 0, st, p);
   return hipGetLastError();
 }
@@ -2764,6 +2765,7 @@ hipError_t launch_gemm_nn_axpy(const float* T, long long ldt, int m, int k, cons
   GemmNnP p;
   p.t = T; p.ldt = ldt; p.m = m; p.k = k; p.b = B; p.ldb = ldb; p.N = N; p.v = V; p.ldv = ldv; p.beta = beta; p.out = Out; p.ldo = ldo;
   const long long blocks = (long long)((m + 127) / 128) * ((N + 127) / 128);
+  LIP_ROUTE("gemm_nn_axpy");
   hipLaunchKernelGGL(gemm_nn_axpy_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
   return hipGetLastError();
 }
@@ -2771,7 +2773,7 @@ hipError_t launch_gemm_nn_axpy(const float* T, long long ldt, int m, int k, cons
 // ------------------------------------------------------------------------------------------
 // route census: every launch route of the conv GEMM dispatchers (launch_igemm, launch_wgrad), of the square-sum
 // kernels and of the non-GEMM kernels, in the names LIP_ROUTE forms at the launch sites.  tests/test_kernel_routes.py
-// and tests/test_small_ops.py reach each of them except the A/B-only ones the former lists; a route missing here still counts (in a slot appended at its first launch) but is not
+// , tests/test_small_ops.py and tests/test_krylov_ops.py reach each of them except the A/B-only ones they list; a route missing here still counts (in a slot appended at its first launch) but is not
 // part of that coverage check — add new routes to this table.  The LIP_TILE experiment tiles are not listed.
 // ------------------------------------------------------------------------------------------
 #define LIP_T6(pre, post) pre "<2,2,1,2>" post, pre "<2,2,2,2>" post, pre "<2,2,1,1>" post, pre "<4,1,1,2>" post, \
@@ -2797,6 +2799,10 @@ static const char* const kRoutes[] = {
     "primal_post/none", "primal_post/relu", "primal_post/tanh", "primal_post/gelu",
     "primal_post/none/bn", "primal_post/relu/bn", "primal_post/tanh/bn", "primal_post/gelu/bn",
     "softmax", "head/ggn", "head/lt", "head/l", "head/scale",
+    // the Krylov primitives (lip_krylov.hip and the two tall-skinny GEMMs above; tests/test_krylov_ops.py): the kernel and
+    // reduction mode a launch takes.  dot_nt/valu/* need the LIP_DOT_NT_VALU A/B switch
+    "dot_nt/quad/part", "dot_nt/quad/atomic", "dot_nt/tile/part", "dot_nt/tile/atomic", "dot_nt/valu/part", "dot_nt/valu/atomic",
+    "rows_combine<4>", "rows_combine<12>", "gemm_nt/ks1", "gemm_nt/ks", "gemm_nn_axpy", "fill_normal", "fill_rademacher",
 };
 #undef LIP_T6
 

@@ -12,6 +12,7 @@ from lip_amd import _native as nv
 from kernel_route_cases import CASES
 from op_harness import Harness, check, emulate, all_routes
 from small_op_cases import SMALL_ROUTES      # labels of the non-GEMM kernels: tests/test_small_ops.py reaches each of them
+from krylov_cases import KRYLOV_ROUTES       # labels of the Krylov primitives: tests/test_krylov_ops.py reaches each of them
 
 pytestmark = pytest.mark.gpu
 
@@ -131,10 +132,10 @@ def test_table_reaches_every_route():
     lib = nv.load()
     every = set(all_routes(lib))
     table = {c.route for c in CASES}
-    assert AB_ONLY <= every and SQSUM_ROUTES <= every and SMALL_ROUTES <= every
+    assert AB_ONLY <= every and SQSUM_ROUTES <= every and SMALL_ROUTES <= every and KRYLOV_ROUTES <= every
     assert {r for r in every if "sqsum" in r} == SQSUM_ROUTES
     assert not (table & AB_ONLY), sorted(table & AB_ONLY)
-    missing = every - AB_ONLY - SQSUM_ROUTES - SMALL_ROUTES - table
+    missing = every - AB_ONLY - SQSUM_ROUTES - SMALL_ROUTES - KRYLOV_ROUTES - table
     assert not missing, f"routes without a case in kernel_route_cases.py: {sorted(missing)}"
     assert table <= every, sorted(table - every)
 
