@@ -191,6 +191,22 @@ int lip_vjp_sqsum(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t 
  * of the example count and of P beyond a fixed group bound) and never more than for P = the bound chunk size      */
 int lip_vjp_sqsum_scratch(lip_engine_t* e, int32_t P, int64_t* floats);
 
+/* Weighted square norm of those rows, ADDED into out (P*n,):
+ *   out[p*n + i] += sum_d w[d] * r_{p,i}[d]^2 ,   r_{p,i} = the row lip_vjp_rows writes for probe p and example i
+ * (same head modes, same c) — the other reduction of the squares lip_vjp_sqsum forms: over the parameters, keeping the
+ * (probe, example) pair.  w is a (D,) device vector in flat-parameter order (NULL: all ones).  With one-hot probes e_k
+ * and w = the variances of a diagonal posterior this is the linearised predictive variance of output k at example i;
+ * with w = NULL it is the diagonal of J J^T.  No rows are written, no float atomics: bitwise reproducible.  `scratch`
+ * (device, caller-owned) holds >= lip_vjp_wnorm_scratch(e, P) floats: (pairs of one pass) x (output tiles of the
+ * largest op).  A bad head mode, a null U / out or too small a scratch returns LIP_ERR_ARG and leaves out untouched. */
+int lip_vjp_wnorm(lip_engine_t* e, const float* U, const float* w, float* out, int32_t P, int32_t head_mode, float c,
+                  float* scratch, int64_t scratch_floats, void* stream);
+int lip_vjp_wnorm_scratch(lip_engine_t* e, int32_t P, int64_t* floats);
+/* test hook: launch census of the lip_vjp_wnorm kernels, a table of its own (they are not part of lip_debug_routes);
+ * same calling convention as lip_debug_route_count / lip_debug_routes.                                          */
+int lip_debug_wnorm_route_count(void);
+int lip_debug_wnorm_routes(int64_t* counts, int32_t n, const char** names);
+
 /* ---- Krylov / trace primitives on blocks of vectors: X is (P, N) row-major -----------
  * They replace what XLA emits for matfree's tridiag_sym (called at src/sample.py:114-126),
  * jax.scipy.sparse.linalg.cg (src/stochtrace.py:146,192; src/sample.py:71) and the

@@ -78,6 +78,10 @@ SIGNATURES = {
     "lip_vjp_rows": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V]),
     "lip_vjp_sqsum": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V, C.c_int64, _V]),
     "lip_vjp_sqsum_scratch": (C.c_int, [_V, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_vjp_wnorm": (C.c_int, [_V, _V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V, C.c_int64, _V]),
+    "lip_vjp_wnorm_scratch": (C.c_int, [_V, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_debug_wnorm_route_count": (C.c_int, []),
+    "lip_debug_wnorm_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_char_p)]),
     "lip_bdot": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int64, _V]),
     "lip_axpby": (C.c_int, [_V, _V, _V, C.c_float, _V, C.c_float, C.c_int32, C.c_int64, _V]),
     "lip_multi_dot": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _V]),

@@ -62,6 +62,11 @@ struct RunCtx {
   bool sqsum = false;
   float* scratch = nullptr;
   long long scratch_floats = 0;
+  // lip_vjp_wnorm (set together with sqsum: the same ops leave the summed path): Y is the (D,) WEIGHT vector, read only
+  // (wones: every weight is 1 and Y is a placeholder of the right extent that is never read); the weighted square norm of
+  // every per-(probe, example) parameter cotangent is added to wout[p * n + i]
+  bool wnorm = false, wones = false;
+  float* wout = nullptr;
   // summed products (lip_ggn_vp / lip_vjp): a weight gradient that reduces all rows in one block may WRITE
   // y = s acc + alpha v instead of adding to an initialised block (the initialisation then skips its parameters)
   bool fuse = false;
@@ -103,6 +108,11 @@ int rows_reduce(const RunCtx& c, const float* out, long long out_ps, int n_img, 
   r.nseg = n_img; r.red_seg = red0 ? red0_ps : red1_ps;
   r.red0_ps = red0_ps * n_img; r.red1_ps = red1_ps * n_img;
   if (N <= 0 || N > 8192 || (red1 && !xhat)) { set_error("per-example reduce: bad operands"); return LIP_ERR_ARG; }
+  if (c.wnorm) {
+    if (reduce_wnorm_tiles(N) * c.P * n_img > c.scratch_floats) { set_error("weighted-norm reduce: scratch too small"); return LIP_ERR_ARG; }
+    RUN_CHECK(launch_reduce_wnorm(r, c.P, c.wones, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm reduce launch");
+    return LIP_OK;
+  }
   if (c.sqsum) {
     if (reduce_sqsum_scratch(N, (long long)c.P * n_img) > c.scratch_floats) { set_error("square-sum reduce: scratch too small"); return LIP_ERR_ARG; }
     RUN_CHECK(launch_reduce_sqsum(r, c.P, c.scratch, c.scratch_floats, c.st), "square-sum reduce launch");
@@ -211,6 +221,11 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       WgradP p;
       const int rc = make_wgrad(c, op, p);
       if (rc) return rc;
+      if (c.wnorm) {
+        if (wgrad_wnorm_tiles(p.M, p.N, p.OHW) * c.P * op.n_img > c.scratch_floats) { set_error("weighted-norm WGRAD: scratch too small"); return LIP_ERR_ARG; }
+        RUN_CHECK(launch_wgrad_wnorm(p, c.P, op.n_img, c.wones ? nullptr : p.y, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm wgrad launch");
+        return LIP_OK;
+      }
       if (c.sqsum) {
         if (wgrad_sqsum_scratch(p.M, p.N, p.OHW, (long long)c.P * op.n_img) > c.scratch_floats) { set_error("square-sum WGRAD: scratch too small"); return LIP_ERR_ARG; }
         RUN_CHECK(launch_wgrad_sqsum(p, c.P, op.n_img, c.scratch, c.scratch_floats, c.st), "square-sum wgrad launch");
@@ -231,6 +246,11 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       if (c.rows || c.sqsum) {
         p.R = op.OH * op.OW; p.nseg = op.n_img; p.red_seg = p.red0 ? p.red0_ps : p.red1_ps;
         p.red0_ps *= op.n_img; p.red1_ps *= op.n_img;
+      }
+      if (c.wnorm) {
+        if (reduce_wnorm_tiles(p.N) * c.P * op.n_img > c.scratch_floats) { set_error("weighted-norm REDUCE: scratch too small"); return LIP_ERR_ARG; }
+        RUN_CHECK(launch_reduce_wnorm(p, c.P, c.wones, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm reduce launch");
+        return LIP_OK;
       }
       if (c.sqsum) {
         if (reduce_sqsum_scratch(p.N, (long long)c.P * op.n_img) > c.scratch_floats) { set_error("square-sum REDUCE: scratch too small"); return LIP_ERR_ARG; }
@@ -422,6 +442,21 @@ int64_t sqsum_scratch(const lip_engine* e, int pc) {
              (op.red0.space != LIP_SP_NONE || op.red1.space != LIP_SP_NONE))
       k = reduce_sqsum_scratch(op.N, pairs);
     need = std::max(need, k);
+  }
+  return need;
+}
+
+// scratch floats of lip_vjp_wnorm on passes of pc probes: (pairs of a pass) x (output tiles of the op with the most)
+int64_t wnorm_scratch(const lip_engine* e, int pc) {
+  int64_t need = 0;
+  for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
+    int64_t tiles = 0;
+    if (op.kind == LIP_OP_WGRAD)
+      tiles = wgrad_wnorm_tiles(op.seg[0].KH * op.seg[0].KW * op.seg[0].C, op.N, op.OH * op.OW);
+    else if ((op.kind == LIP_OP_IGEMM || op.kind == LIP_OP_REDUCE || op.kind == LIP_OP_POOL_BWD || op.kind == LIP_OP_MAXPOOL_BWD) &&
+             (op.red0.space != LIP_SP_NONE || op.red1.space != LIP_SP_NONE))
+      tiles = reduce_wnorm_tiles(op.N);
+    need = std::max(need, tiles * (int64_t)pc * op.n_img);
   }
   return need;
 }
@@ -631,6 +666,48 @@ int lip_vjp_sqsum(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t 
     c.sqsum = true; c.scratch = scratch; c.scratch_floats = scratch_floats;
     if ((rc = run_tape(c, LIP_TAPE_BACKWARD, false))) return rc;
   }
+  return LIP_OK;
+}
+
+int lip_vjp_wnorm_scratch(lip_engine_t* e, int32_t P, int64_t* floats) {
+  if (!e || !floats || P <= 0) { set_error("lip_vjp_wnorm_scratch: bad argument"); return LIP_ERR_ARG; }
+  if (e->tape[LIP_TAPE_BACKWARD].empty()) { set_error("lip_vjp_wnorm_scratch: backward tape missing"); return LIP_ERR_STATE; }
+  *floats = wnorm_scratch(e, e->max_chunk > 0 ? balanced_chunk(P, e->max_chunk) : P);
+  return LIP_OK;
+}
+
+int lip_vjp_wnorm(lip_engine_t* e, const float* U, const float* w, float* out, int32_t P, int32_t head_mode, float cc,
+                  float* scratch, int64_t scratch_floats, void* stream) {
+  int rc = ready(e, "lip_vjp_wnorm");
+  if (rc) return rc;
+  if (!U || !out || P <= 0 || (head_mode != LIP_HEAD_L && head_mode != LIP_HEAD_IN) || scratch_floats < 0) {
+    set_error("lip_vjp_wnorm: bad argument");
+    return LIP_ERR_ARG;
+  }
+  const int step = balanced_chunk(P, e->max_chunk);
+  const int64_t need = wnorm_scratch(e, step);
+  if (scratch_floats < need || (need > 0 && !scratch)) {
+    set_error("lip_vjp_wnorm: scratch of %lld floats, %lld needed (lip_vjp_wnorm_scratch)", (long long)scratch_floats, (long long)need);
+    return LIP_ERR_ARG;
+  }
+  const int64_t hstride = (int64_t)e->n_img * e->K;
+  hipStream_t st = (hipStream_t)stream;
+  for (int c0 = 0; c0 < P; c0 += step) {
+    const int pc = (P - c0) < step ? (P - c0) : step;
+    // (w == NULL: theta stands in for the weight vector — a (D,) device block whose slices are addressed, never read)
+    RunCtx c{e, nullptr, const_cast<float*>(w ? w : e->theta), const_cast<float*>(U) + (int64_t)c0 * hstride, pc, head_mode, cc, st};
+    c.sqsum = true; c.scratch = scratch; c.scratch_floats = scratch_floats;
+    c.wnorm = true; c.wones = w == nullptr; c.wout = out + (int64_t)c0 * e->n_img;
+    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, false))) return rc;
+  }
+  return LIP_OK;
+}
+
+int lip_debug_wnorm_route_count(void) { return (int)WN_ROUTES; }
+
+int lip_debug_wnorm_routes(int64_t* counts, int32_t n, const char** names) {
+  if (n < 0) { set_error("lip_debug_wnorm_routes: bad argument"); return LIP_ERR_ARG; }
+  wnorm_routes_read(counts, n, names);
   return LIP_OK;
 }
 

@@ -202,6 +202,26 @@ hipError_t launch_reduce_sqsum(const ReduceP& p, int P, float* scratch, long lon
 // y[j] += sum_{g < G} partial[g * len + j], g ascending
 hipError_t launch_sqsum_finish(const float* partial, int G, long long len, float* y, hipStream_t st);
 
+// ---- weighted square norms of lip_vjp_wnorm --------------------------------------------------
+// out[p * n + i] += sum_j w_j (per-(probe, example) partial product)_j^2: the same per-pair tiles and segmented sums as
+// the square-accumulating reductions above, reduced over the parameters instead of over the pairs.  Every launch
+// writes one float per (output tile, pair) to scratch[tile * pairs + pair] (plain stores) and wnorm_finish adds the
+// tiles of a pair, in tile order, into out: no float atomics.  w: the op's slice of the weight vector in the layout of
+// the op's output (null: all ones).  Scratch floats of a launch: `*_wnorm_tiles` x pairs.
+long long wgrad_wnorm_tiles(int M, int N, int OHW);
+hipError_t launch_wgrad_wnorm(const WgradP& p, int P, int n_img, const float* w, float* out, float* scratch,
+                              long long scratch_floats, hipStream_t st);
+// p.red0 / p.red1: which reductions the op has and (unless `ones`) their (N,) weight slices — read, never written
+long long reduce_wnorm_tiles(int N);
+hipError_t launch_reduce_wnorm(const ReduceP& p, int P, bool ones, float* out, float* scratch, long long scratch_floats,
+                               hipStream_t st);
+hipError_t launch_wnorm_finish(const float* partial, int T, long long pairs, float* out, hipStream_t st);
+// launch census of these kernels (lip_debug_wnorm_routes), kept apart from the route census below
+enum WnormRoute { WN_WGRAD_2212 = 0, WN_WGRAD_2222, WN_WGRAD_2211, WN_WGRAD_4112, WN_WGRAD_2111, WN_WGRAD_4111,
+                  WN_WGRAD_DENSE, WN_REDUCE, WN_FINISH, WN_ROUTES };
+void wnorm_route_hit(int id);
+int wnorm_routes_read(int64_t* counts, int n, const char** names);
+
 // ---- route census (lip_debug_routes): one host-side counter per launch route -----------------
 // A route is one kernel instantiation as launched, with the flags that picked it, e.g. "igemm_fast<4,1,1,2>/par/bv4".
 // route_id() formats the name and returns its slot (the table of known routes in lip_mfma.hip, or a new slot appended

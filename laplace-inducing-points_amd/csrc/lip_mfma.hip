@@ -3634,4 +3634,276 @@ hipError_t launch_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch,
                  : run_wgrad_sqsum<4, 1, 1, 1>(p, P, n_img, scratch, scratch_floats, st);
 }
 
+// ------------------------------------------------------------------------------------------
+// weighted square norm of the per-example weight gradient (lip_vjp_wnorm):
+//   out[(p, i)] += sum_{m, c} w[m][c] ( s[c] * sum_{pix of example i} im2col(a_i)[pix][m] g_pi[pix][c] )^2
+// The per-(probe, example) MFMA tile of wgrad_sqsum_kernel (same operands, row geometry and K loop); the other
+// reduction of its squares: the block's w tile is loaded once into registers, after each pair the tile is scaled,
+// squared, multiplied by w and summed over the tile (lanes by shuffles, waves in wave order through LDS) to ONE float,
+// stored to partial[tile][pair] (plain store).  wnorm_finish adds the tiles of a pair in tile order.  No atomics.
+// grid = (output tiles, groups of pairs); w == null: weight 1.
+// ------------------------------------------------------------------------------------------
+struct WnGroupP {
+  const float* w;                       // the op's (M, N) slice of the weight vector, or null (all ones)
+  float* partial;                       // [tiles][pairs]
+  int pairs, per, n_img;
+};
+
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(WM * WN * 64) void wgrad_wnorm_kernel(const WgradP prm, const WnGroupP wn_) {
+  using T = Tile<WM, WN, TM, TN>;
+  constexpr int NT = T::NT, BM = T::BM, BN = T::BN, AE = T::AE, AQ = T::AQ, BE = T::BE;
+  constexpr int LDA = BM + 4, LDB = BN;
+  constexpr int QPR = BM / 4;
+  __shared__ __attribute__((aligned(16))) float As[BK * LDA];
+  __shared__ float Bs[BK * LDB];
+  __shared__ float wsum[WM * WN];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int N = prm.N, M = prm.M;
+  const int tiles_n = (N + BN - 1) / BN;
+  const int tile_n = blockIdx.x % tiles_n, tile_m = blockIdx.x / tiles_n;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const int q0 = blockIdx.y * wn_.per, q1 = min(wn_.pairs, q0 + wn_.per);
+  const int l31 = lane & 31, lh = lane >> 5;
+
+  // the block's weights in the accumulator layout, times the squared column scale; 0 outside the (M, N) matrix
+  f32x16 acc[TM][TN], wt[TM][TN];
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) {
+    const int col = n0 + (wn * TN + tn) * 32 + l31;
+    const float sc = (prm.scale && col < N) ? prm.scale[col] : 1.f;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+      const int mb = m0 + (wm * TM + tm) * 32 + 4 * lh;
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int m = mb + (reg & 3) + 8 * (reg >> 2);
+        float v = 0.f;
+        if (m < M && col < N) v = (wn_.w ? wn_.w[(long long)m * N + col] : 1.f) * (sc * sc);
+        wt[tm][tn][reg] = v;
+      }
+    }
+  }
+
+  const bool vec = (prm.C & 3) == 0;
+  const int my_m = vec ? (m0 + 4 * (tid % QPR)) : (m0 + (tid % BM));
+  int kh = 0, kw = 0, ci = 0;
+  const bool mvalid = my_m < M;
+  if (mvalid) {
+    const int tap = my_m / prm.C;
+    ci = my_m - tap * prm.C;
+    kh = tap / prm.KW;
+    kw = tap - kh * prm.KW;
+  }
+
+  float areg[AE], breg[BE];
+  const float* gbase = prm.g;
+  int rend = 0;
+
+  auto load_tile = [&](int rk0) {
+    if (vec) {
+#pragma unroll
+      for (int j = 0; j < AQ; ++j) {
+        const int k = (tid + j * NT) / QPR;
+        const int r = rk0 + k;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (mvalid && r < rend) {
+          const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
+          const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
+          const int ih = oh * prm.stride + kh - prm.pad_h, iw = ow * prm.stride + kw - prm.pad_w;
+          if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW)
+            v = *reinterpret_cast<const float4*>(prm.a + (unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + ci));
+        }
+        areg[4 * j + 0] = v.x; areg[4 * j + 1] = v.y; areg[4 * j + 2] = v.z; areg[4 * j + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < AE; ++j) {
+        const int k = (tid + j * NT) / BM;
+        const int r = rk0 + k;
+        float v = 0.f;
+        if (mvalid && r < rend) {
+          const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
+          const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
+          const int ih = oh * prm.stride + kh - prm.pad_h, iw = ow * prm.stride + kw - prm.pad_w;
+          if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW)
+            v = prm.a[(unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + ci)];
+        }
+        areg[j] = v;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BE; ++j) {
+      const int e = tid + j * NT;
+      const int k = e / BN, nn = e - k * BN;
+      const int r = rk0 + k, col = n0 + nn;
+      breg[j] = (e < BN * BK && r < rend && col < N) ? gbase[(unsigned)(r * N + col)] : 0.f;
+    }
+  };
+
+  auto store_tile = [&]() {
+    if (vec) {
+#pragma unroll
+      for (int j = 0; j < AQ; ++j) {
+        const int q = tid + j * NT;
+        const int k = q / QPR, mq = q - k * QPR;
+        *reinterpret_cast<float4*>(&As[k * LDA + 4 * mq]) =
+            make_float4(areg[4 * j + 0], areg[4 * j + 1], areg[4 * j + 2], areg[4 * j + 3]);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < AE; ++j) {
+        const int e = tid + j * NT;
+        const int k = e / BM, mm = e - k * BM;
+        As[k * LDA + mm] = areg[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BE; ++j) {
+      const int e = tid + j * NT;
+      if (e >= BN * BK) continue;
+      const int k = e / BN, nn = e - k * BN;
+      Bs[k * LDB + nn] = breg[j];
+    }
+  };
+
+  float* part = wn_.partial + (long long)blockIdx.x * wn_.pairs;
+  for (int q = q0; q < q1; ++q) {
+    const int p = q / wn_.n_img, i = q - p * wn_.n_img;
+    const int rbeg = i * prm.OHW;
+    rend = rbeg + prm.OHW;
+    gbase = prm.g + (long long)p * prm.g_ps;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+    int rk = rbeg;
+    load_tile(rk);
+    while (true) {
+      __syncthreads();                  // (also orders the previous pair's last sweep and wave sums before these LDS stores)
+      store_tile();
+      __syncthreads();
+      rk += BK;
+      const bool more = rk < rend;
+      if (more) load_tile(rk);
+      mfma_sweep<WM, WN, TM, TN, LDA, LDB>(As, Bs, acc, wm, wn, lane);
+      if (!more) break;
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float v = acc[tm][tn][r];
+          s = fmaf(wt[tm][tn][r] * v, v, s);
+        }
+    s = wave_sum(s);
+    if (lane == 0) wsum[wave] = s;
+    __syncthreads();
+    if (tid == 0) {
+      float t = 0.f;
+#pragma unroll
+      for (int k = 0; k < WM * WN; ++k) t += wsum[k];
+      part[q] = t;
+    }
+  }
+}
+
+// Dense weight gradients (OH*OW == 1): the per-example gradient is the outer product of a_i (M) and s * g_pi (N), so the
+// weighted norm is the bilinear form  (a_i^2)^T W (s g_pi)^2 — no tile is formed.  Block (example i, 64 columns):
+// t[c] = s[c]^2 sum_m a_i[m]^2 W[m][c] once (rows in chunks of 256 through LDS, four row lanes added in lane order),
+// then wave k takes probes k, k + 4, ...: sum_c t[c] g_pi[c]^2 by shuffles -> partial[column tile][pair].
+__global__ __launch_bounds__(256) void wgrad_wnorm_dense_kernel(const WgradP prm, const float* __restrict__ w, int P,
+                                                                int n_img, float* __restrict__ partial) {
+  __shared__ float As2[256];
+  __shared__ float Ts[4][64];
+  const int tid = threadIdx.x, cl = tid & 63, rl = tid >> 6;
+  const int N = prm.N, M = prm.M;
+  const int i = blockIdx.x, ct = blockIdx.y;
+  const int col = ct * 64 + cl;
+  const bool on = col < N;
+  const long long img = (long long)prm.IH * prm.IW * prm.C;
+  float t = 0.f;
+  for (int mb = 0; mb < M; mb += 256) {
+    const int m = mb + tid;
+    float a = 0.f;
+    if (m < M) {
+      const int tap = m / prm.C, ci = m - tap * prm.C;
+      const int kh = tap / prm.KW, kw = tap - kh * prm.KW;
+      const int ih = kh - prm.pad_h, iw = kw - prm.pad_w;
+      if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW) a = prm.a[(long long)i * img + ((long long)ih * prm.IW + iw) * prm.C + ci];
+    }
+    As2[tid] = a * a;
+    __syncthreads();
+    const int mend = min(256, M - mb);
+    if (on)
+      for (int mm = rl; mm < mend; mm += 4) t = fmaf(As2[mm], w ? w[(long long)(mb + mm) * N + col] : 1.f, t);
+    __syncthreads();
+  }
+  Ts[rl][cl] = t;
+  __syncthreads();
+  const float sc = (on && prm.scale) ? prm.scale[col] : 1.f;
+  const float tt = on ? (((Ts[0][cl] + Ts[1][cl]) + Ts[2][cl]) + Ts[3][cl]) * (sc * sc) : 0.f;
+  const long long pairs = (long long)P * n_img;
+  for (int p = rl; p < P; p += 4) {
+    const float g = on ? prm.g[(long long)p * prm.g_ps + (long long)i * N + col] : 0.f;
+    const float v = wave_sum(tt * g * g);
+    if (cl == 0) partial[(long long)ct * pairs + (long long)p * n_img + i] = v;
+  }
+}
+
+long long wgrad_wnorm_tiles(int M, int N, int OHW) {
+  if (M <= 0 || N <= 0) return 0;
+  if (OHW == 1) return (N + 63) / 64;
+  int BM, BN;
+  sq_tile(M, N, BM, BN);
+  return (long long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+}
+
+template <int WM, int WN, int TM, int TN>
+static hipError_t run_wgrad_wnorm(const WgradP& p, int P, int n_img, const float* w, float* out, float* scratch,
+                                  long long scratch_floats, int route, hipStream_t st) {
+  using T = Tile<WM, WN, TM, TN>;
+  const long long tiles = (long long)((p.M + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN);
+  const long long pairs = (long long)P * n_img;
+  if (tiles != wgrad_wnorm_tiles(p.M, p.N, p.OHW) || tiles * pairs > scratch_floats) return hipErrorInvalidValue;
+  int G, per;
+  sq_groups(tiles, pairs, G, per);
+  WnGroupP wn;
+  wn.w = w; wn.partial = scratch; wn.pairs = (int)pairs; wn.per = per; wn.n_img = n_img;
+  wnorm_route_hit(route);
+  hipLaunchKernelGGL((wgrad_wnorm_kernel<WM, WN, TM, TN>), dim3((unsigned)tiles, (unsigned)G), dim3(T::NT), 0, st, p, wn);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_wnorm_finish(scratch, (int)tiles, pairs, out, st);
+}
+
+hipError_t launch_wgrad_wnorm(const WgradP& p, int P, int n_img, const float* w, float* out, float* scratch,
+                              long long scratch_floats, hipStream_t st) {
+  if (P <= 0 || n_img <= 0 || p.OHW * n_img != p.R || (long long)P * n_img >= (1ll << 31) || !out || !scratch) return hipErrorInvalidValue;
+  if (p.OHW == 1) {
+    const long long tiles = (p.N + 63) / 64, pairs = (long long)P * n_img;
+    if (tiles * pairs > scratch_floats) return hipErrorInvalidValue;
+    wnorm_route_hit(WN_WGRAD_DENSE);
+    hipLaunchKernelGGL(wgrad_wnorm_dense_kernel, dim3((unsigned)n_img, (unsigned)tiles), dim3(256), 0, st, p, w, P, n_img, scratch);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_wnorm_finish(scratch, (int)tiles, pairs, out, st);
+  }
+  // the tile shapes of launch_wgrad_sqsum (sq_tile)
+  const bool small_m = p.M <= 64;
+  if (p.N > 64) return small_m ? run_wgrad_wnorm<2, 2, 1, 2>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_2212, st)
+                               : run_wgrad_wnorm<2, 2, 2, 2>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_2222, st);
+  if (p.N > 32) return small_m ? run_wgrad_wnorm<2, 2, 1, 1>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_2211, st)
+                               : run_wgrad_wnorm<4, 1, 1, 2>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_4112, st);
+  return small_m ? run_wgrad_wnorm<2, 1, 1, 1>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_2111, st)
+                 : run_wgrad_wnorm<4, 1, 1, 1>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_4111, st);
+}
+
 }  // namespace lip

@@ -197,6 +197,118 @@ hipError_t launch_sqsum_finish(const float* partial, int G, long long len, float
   return hipGetLastError();
 }
 
+// ---- weighted square norm of the segmented reduce (lip_vjp_wnorm) ---------------------------------------------------
+//   out[(p, i)] += sum_c  w0[c] (sum_{r < R} g[p][i][r][c])^2 + w1[c] (sum_r g[p][i][r][c] xhat[i][r][c])^2
+// The block of reduce_sqsum_kernel (cb columns x 256 / cb row lanes, a fixed group of pairs in order); per pair the
+// column sums are squared, weighted and summed over the block's columns (they sit in wave 0: shuffles) to one float,
+// stored to partial[column block][pair].  wnorm_finish adds the column blocks of a pair in order.
+struct WnRedP {
+  const float* w0; const float* w1;     // the (N,) weight slices of red0 / red1, or null (all ones)
+  int has0, has1;
+  float* partial;                       // [column blocks][pairs]
+  int pairs, per, n_img, cb;
+};
+
+__global__ __launch_bounds__(256) void reduce_wnorm_kernel(const ReduceP prm, const WnRedP wn) {
+  __shared__ float s0[256], s1[256];
+  const int N = prm.N, cb = wn.cb, RL = 256 / cb;
+  const int cl = threadIdx.x % cb, rl = threadIdx.x / cb;
+  const int c = blockIdx.x * cb + cl;
+  const int q0 = blockIdx.y * wn.per, q1 = min(wn.pairs, q0 + wn.per);
+  const bool on = c < N;
+  const bool lead = rl == 0 && on;      // (rl == 0: threads 0 .. cb - 1, cb <= 64 — all in wave 0)
+  const float w0 = (lead && wn.has0) ? (wn.w0 ? wn.w0[c] : 1.f) : 0.f;
+  const float w1 = (lead && wn.has1) ? (wn.w1 ? wn.w1[c] : 1.f) : 0.f;
+  float* part = wn.partial + (long long)blockIdx.x * wn.pairs;
+  for (int q = q0; q < q1; ++q) {
+    const int p = q / wn.n_img, i = q - p * wn.n_img;
+    const long long seg = (long long)i * prm.R * N;
+    const float* g = prm.g + (long long)p * prm.g_ps + seg;
+    const float* xh = prm.xhat ? prm.xhat + seg : nullptr;
+    float t0 = 0.f, t1 = 0.f;
+    if (on)
+      for (int r = rl; r < prm.R; r += RL) {
+        const float v = g[(long long)r * N + c];
+        t0 += v;
+        if (xh) t1 = fmaf(v, xh[(long long)r * N + c], t1);
+      }
+    s0[threadIdx.x] = t0; s1[threadIdx.x] = t1;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+      float v = 0.f;
+      if (lead) {
+        float u0 = 0.f, u1 = 0.f;
+        for (int k = 0; k < RL; ++k) { u0 += s0[k * cb + cl]; u1 += s1[k * cb + cl]; }
+        v = fmaf(w0 * u0, u0, w1 * u1 * u1);
+      }
+      v = wave_sum(v);
+      if (threadIdx.x == 0) part[q] = v;
+    }
+    __syncthreads();
+  }
+}
+
+long long reduce_wnorm_tiles(int N) { return N > 0 ? (N + sq_cb(N) - 1) / sq_cb(N) : 0; }
+
+hipError_t launch_reduce_wnorm(const ReduceP& p, int P, bool ones, float* out, float* scratch, long long scratch_floats,
+                               hipStream_t st) {
+  if (!p.red0 && !p.red1) return hipSuccess;
+  const long long pairs = (long long)P * p.nseg;
+  if (P <= 0 || p.nseg <= 0 || p.N <= 0 || p.R <= 0 || pairs >= (1ll << 31) || !out || !scratch) return hipErrorInvalidValue;
+  WnRedP wn;
+  int G, per;
+  sq_red_groups(p.N, pairs, wn.cb, G, per);
+  const long long tiles = (p.N + wn.cb - 1) / wn.cb;
+  if (tiles * pairs > scratch_floats) return hipErrorInvalidValue;
+  wn.pairs = (int)pairs; wn.per = per; wn.n_img = p.nseg;
+  wn.has0 = p.red0 != nullptr; wn.has1 = p.red1 != nullptr;
+  wn.w0 = ones ? nullptr : p.red0; wn.w1 = ones ? nullptr : p.red1;
+  wn.partial = scratch;
+  wnorm_route_hit(WN_REDUCE);
+  hipLaunchKernelGGL(reduce_wnorm_kernel, dim3((unsigned)tiles, (unsigned)G), dim3(256), 0, st, p, wn);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_wnorm_finish(scratch, (int)tiles, pairs, out, st);
+}
+
+// out[q] += sum_t partial[t][q], t ascending, the tiles added in float64 (one rounding per op and pair)
+__global__ __launch_bounds__(256) void wnorm_finish_kernel(const float* __restrict__ partial, int T, long long pairs,
+                                                           float* __restrict__ out) {
+  const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= pairs) return;
+  double s = 0.0;
+  for (int t = 0; t < T; ++t) s += (double)partial[(long long)t * pairs + q];
+  out[q] = (float)((double)out[q] + s);
+}
+
+hipError_t launch_wnorm_finish(const float* partial, int T, long long pairs, float* out, hipStream_t st) {
+  if (pairs <= 0 || T <= 0) return hipSuccess;
+  wnorm_route_hit(WN_FINISH);
+  hipLaunchKernelGGL(wnorm_finish_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, partial, T, pairs, out);
+  return hipGetLastError();
+}
+
+// launch census of the lip_vjp_wnorm kernels (lip_debug_wnorm_routes): a table of its own, apart from the route census
+static const char* const kWnormRoutes[WN_ROUTES] = {
+    "wgrad_wnorm<2,2,1,2>", "wgrad_wnorm<2,2,2,2>", "wgrad_wnorm<2,2,1,1>", "wgrad_wnorm<4,1,1,2>", "wgrad_wnorm<2,1,1,1>",
+    "wgrad_wnorm<4,1,1,1>", "wgrad_wnorm_dense", "reduce_wnorm", "wnorm_finish",
+};
+static std::atomic<long long> g_wnorm_counts[WN_ROUTES];
+
+void wnorm_route_hit(int id) {
+  if (id >= 0 && id < WN_ROUTES) g_wnorm_counts[id].fetch_add(1, std::memory_order_relaxed);
+}
+
+int wnorm_routes_read(int64_t* counts, int n, const char** names) {
+  const int m = n < WN_ROUTES ? n : (int)WN_ROUTES;
+  for (int i = 0; i < m; ++i) {
+    if (counts) counts[i] = g_wnorm_counts[i].load(std::memory_order_relaxed);
+    if (names) names[i] = kWnormRoutes[i];
+  }
+  for (int i = 0; i < WN_ROUTES; ++i) g_wnorm_counts[i].store(0, std::memory_order_relaxed);
+  return m;
+}
+
 // ---- mean pool over pixels: out[p][i][c] = inv * sum_pix in[p][i][pix][c]  (jnp.mean(x,(1,2))) ------
 __global__ __launch_bounds__(256) void pool_fwd_kernel(const PoolP prm) {
   extern __shared__ float sm[];           // [C + 256]

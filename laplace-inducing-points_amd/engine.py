@@ -713,3 +713,35 @@ class LinearizedNet:
         nv.check(self.lib.lip_vjp_sqsum(self.h, nv.ptr(Ub), nv.ptr(out), Ub.shape[0], m, float(c), nv.ptr(scratch),
                                         scratch.numel(), nv.stream_ptr()), "lip_vjp_sqsum")
         return out
+
+    def vjp_wnorm(self, U: torch.Tensor, w: Optional[torch.Tensor] = None, mode: str = "raw", c: float = 1.0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Weighted square norm of the rows of :meth:`vjp_rows` -> (P, n):  ``out[p, i] = sum_d w[d] r_pi[d]**2`` with
+        ``r_pi = J_i^T (c L_i U[p, i])`` ('l') or ``J_i^T U[p, i]`` ('raw'), ADDED into ``out`` when it is given.
+        ``w`` is a (D,) vector in flat-parameter order (None: all ones, the squared row norms).  The squares are
+        weighted and summed where the backward sweep forms each per-(probe, example) cotangent (``lip_vjp_wnorm``): no
+        (P, n, D) rows exist and the result is bitwise reproducible.  One-hot probes e_k with the variances of a diagonal
+        posterior give the linearised predictive variances (:func:`lla.predict_lla_diag`).  The kernels' scratch is a
+        device buffer allocated once per engine, sized for the engine's probe chunk."""
+        if mode not in ("l", "raw"):
+            raise ValueError("mode must be 'l' or 'raw'")
+        Ub = U.reshape(-1, self.n * self.K).to(device=self.device, dtype=torch.float32).contiguous()
+        P = Ub.shape[0]
+        if w is not None:
+            w = w.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            if w.numel() != self.D:
+                raise ValueError(f"w must hold {self.D} weights, got {tuple(w.shape)}")
+        if out is None:
+            out = torch.zeros(P, self.n, device=self.device, dtype=torch.float32)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == P * self.n):
+            raise ValueError(f"out must be a contiguous float32 device block of {P} x {self.n} floats")
+        scratch = getattr(self, "_wn_scratch", None)
+        if scratch is None:
+            floats = C.c_int64(0)
+            nv.check(self.lib.lip_vjp_wnorm_scratch(self.h, int(self.chunk), C.byref(floats)), "lip_vjp_wnorm_scratch")
+            scratch = torch.empty(max(1, floats.value), device=self.device, dtype=torch.float32)
+            self._wn_scratch = scratch
+        m = nv.HEAD_L if mode == "l" else nv.HEAD_IN
+        nv.check(self.lib.lip_vjp_wnorm(self.h, nv.ptr(Ub), nv.ptr(w), nv.ptr(out), P, m, float(c), nv.ptr(scratch),
+                                        scratch.numel(), nv.stream_ptr()), "lip_vjp_wnorm")
+        return out

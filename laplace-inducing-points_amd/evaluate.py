@@ -136,3 +136,22 @@ def auroc_ood(state, id_probs: torch.Tensor, ood_loader: Iterable, Z, alpha, ful
     scores = torch.cat([ood_scores(id_probs), ood_scores(ood_probs)])
     labels = torch.cat([torch.zeros(len(id_probs)), torch.ones(len(ood_probs))])
     return roc_auc(labels, scores)
+
+
+def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, model_type="classifier",
+                        posterior: str = "diag"):
+    """:func:`eval_dataset_extended` without draws: the class probabilities are the probit predictive
+    (``lla.probit_predictive``) of the closed-form output variances — ``posterior="diag"``: the diagonal Laplace
+    posterior (``lla.predict_lla_diag``), ``"inducing"``: the inducing-point posterior (``lla.predict_lla_variances``).
+    -> (NLL, accuracy, Brier, ECE, probs, labels)"""
+    from .lla import predict_lla_diag, predict_lla_variances, probit_predictive
+    predict = {"diag": predict_lla_diag, "inducing": predict_lla_variances}[posterior]
+    all_probs, all_labels = [], []
+    for x_b, y_b in dataloader:
+        probs = probit_predictive(*predict(state, x_b, Z, model_type, alpha, full_set_size=full_set_size))
+        all_probs.append(probs)
+        all_labels.append(y_b.reshape(-1).long().to(probs.device))
+    probs, labels = torch.cat(all_probs), torch.cat(all_labels)
+    nll = -torch.log(torch.gather(probs, -1, labels[:, None]).squeeze(-1)).mean()
+    acc = (probs.argmax(-1) == labels).to(probs.dtype).mean()
+    return float(nll), float(acc), brier_score(probs, labels), ece(probs, labels), probs, labels

@@ -143,6 +143,25 @@ def _cross_gram64(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     return krylov.dot_nt(A.contiguous(), B.contiguous())
 
 
+def _factor_and_core(map_state, Z, model_type, alpha, full_set_size):
+    """The factor Wm (d, D) of the inducing-point GGN and C = (alpha/beta I + Wm Wm^T)^-1 on range(Wm Wm^T) (float64):
+    S = alpha^-1 (I - Wm^T C Wm)."""
+    from .ggn import gram_from_factor, materialize_factor
+    eng_z = get_engine(map_state, Z, model_type)
+    M = Z.shape[0]
+    N = full_set_size or M
+    beta = N / M
+    c = math.exp(-0.5 * float(map_state.params["logvar"]["logvar"])) if model_type == "regressor" else 1.0
+    Wm = materialize_factor(eng_z, c)                                   # (d, D)
+    Gd = gram_from_factor(Wm)
+    # (alpha/beta I + Gd)^-1 restricted to range(Gd): on the null space of Gd (the classifier's factor has rank
+    # M (K-1)) J W vanishes exactly, but its rounding error would be amplified by beta/alpha there
+    lam, Ug = torch.linalg.eigh(0.5 * (Gd + Gd.T))
+    keep = lam > 1e-6 * lam.max().clamp_min(1e-300)
+    Cm = (Ug * torch.where(keep, 1.0 / (alpha / beta + lam.clamp_min(0.0)), torch.zeros_like(lam))) @ Ug.T
+    return Wm, Cm
+
+
 def predict_lla_marginals(map_state, Xnew, Z, model_type, alpha, full_set_size=None, batch: int = 64):
     """The exact linearised predictive of ``predict_lla_dense`` (``src/lla.py:51-82``) — mean f(x; theta_MAP) and the
     K x K covariance J(x) S J(x)^T per test point, S = (alpha I + beta W W^T)^-1 — without anything D x D:
@@ -153,20 +172,8 @@ def predict_lla_marginals(map_state, Xnew, Z, model_type, alpha, full_set_size=N
     covariance).  It is not faster than the sampled route at the CIFAR config (0.86 s against 0.34 s per 256-image
     batch with 200 draws: the float64 products dominate), so it is the reference point, not the default.
     Not a reference function (its scalable predictive is sample-based only); returned like ``predict_lla_dense``."""
-    from .ggn import gram_from_factor, materialize_factor
-    eng_z = get_engine(map_state, Z, model_type)
-    M = Z.shape[0]
-    N = full_set_size or M
-    beta = N / M
-    c = math.exp(-0.5 * float(map_state.params["logvar"]["logvar"])) if model_type == "regressor" else 1.0
-    Wm = materialize_factor(eng_z, c)                                   # (d, D)
-    Gd = gram_from_factor(Wm)
+    Wm, Cm = _factor_and_core(map_state, Z, model_type, alpha, full_set_size)
     d = Wm.shape[0]
-    # (alpha/beta I + Gd)^-1 restricted to range(Gd): on the null space of Gd (the classifier's factor has rank
-    # M (K-1)) J W vanishes exactly, but its rounding error would be amplified by beta/alpha there
-    lam, Ug = torch.linalg.eigh(0.5 * (Gd + Gd.T))
-    keep = lam > 1e-6 * lam.max().clamp_min(1e-300)
-    Cm = (Ug * torch.where(keep, 1.0 / (alpha / beta + lam.clamp_min(0.0)), torch.zeros_like(lam))) @ Ug.T
     means, covs = [], []
     for s0 in range(0, Xnew.shape[0], batch):
         Xb = Xnew[s0:s0 + batch]
@@ -183,6 +190,99 @@ def predict_lla_marginals(map_state, Xnew, Z, model_type, alpha, full_set_size=N
     if model_type == "regressor":
         return MultivariateNormalFullCovariance(loc=f_mean.squeeze(), covariance_matrix=torch.diag(f_cov.reshape(-1)))
     return MultivariateNormalFullCovariance(loc=f_mean.squeeze(), covariance_matrix=f_cov)
+
+
+POLARISATION_MAX_K = 32
+
+
+def polarisation_probes(K: int):
+    """The K (K + 1) / 2 output cotangents e_k + e_k' (k <= k') whose weighted norms determine a K x K quadratic form,
+    and their index pairs: (P, K) float32 rows, (P,) k, (P,) k'."""
+    ks, kps = torch.triu_indices(K, K)
+    E = torch.zeros(ks.numel(), K)
+    E[torch.arange(ks.numel()), ks] += 1.0
+    E[torch.arange(ks.numel()), kps] += 1.0
+    return E, ks, kps
+
+
+def covariance_from_polarisation(q: torch.Tensor, ks: torch.Tensor, kps: torch.Tensor, K: int) -> torch.Tensor:
+    """S (..., K, K) from q[..., j] = (e_k + e_k')^T S (e_k + e_k') over the pairs of :func:`polarisation_probes`:
+    S_kk = q_kk / 4, S_kk' = (q_kk' - S_kk - S_k'k') / 2; float64, symmetric by construction."""
+    q = q.double()
+    diag_pos = (ks == kps).nonzero().squeeze(-1)
+    sd = q[..., diag_pos] / 4.0                                         # (..., K): the pairs (k, k) come in k order
+    off = (q - sd[..., ks] - sd[..., kps]) / 2.0
+    S = torch.zeros(*q.shape[:-1], K, K, dtype=torch.float64, device=q.device)
+    S[..., ks, kps] = off
+    S[..., kps, ks] = off
+    S[..., torch.arange(K), torch.arange(K)] = sd
+    return S
+
+
+def predict_lla_diag(map_state, Xnew, Z, model_type, alpha, full_set_size=None, cov: str = "diag", batch: int = 256):
+    """Closed-form linearised predictive of the diagonal posterior of :func:`posterior_lla_diag`: the mean
+    f(x; theta_MAP) (B, K) and the variances var_k(x) = sum_d sigma_d^2 J(x)[k, d]^2 (B, K), float64 — what
+    :func:`predict_lla_diag_scalable` estimates from draws, without draws.  One weighted-norm backward sweep of K
+    one-hot probes per test batch (:meth:`LinearizedNet.vjp_wnorm`): no Jacobian rows are written.
+    ``cov="full"`` returns the K x K covariances J diag(sigma^2) J^T as a ``MultivariateNormalFullCovariance`` like
+    ``predict_lla_dense``, from the K (K + 1) / 2 probes e_k + e_k' of the same kernel (polarisation; K <= 32).
+    A regressor comes back in the shapes of ``predict_lla_dense``: mean (B,), variances (B,) (``cov="full"``: the
+    (B, B) diagonal matrix).  Not a reference function."""
+    if cov not in ("diag", "full"):
+        raise ValueError("cov must be 'diag' or 'full'")
+    w = posterior_lla_diag(map_state, Z, model_type, alpha, full_set_size=full_set_size).variance()
+    means, outs = [], []
+    for s0 in range(0, Xnew.shape[0], batch):
+        eng = get_engine(map_state, Xnew[s0:s0 + batch], model_type)
+        K = eng.K
+        if cov == "diag":
+            E = torch.eye(K, device=eng.device, dtype=torch.float32)[:, None, :].expand(K, eng.n, K).contiguous()
+            outs.append(eng.vjp_wnorm(E, w, "raw").T.double())                          # (B, K)
+        else:
+            if K > POLARISATION_MAX_K:
+                raise ValueError(f"cov='full' takes K (K + 1) / 2 probes per test batch: refused for K = {K} > "
+                                 f"{POLARISATION_MAX_K} outputs (use cov='diag')")
+            E, ks, kps = polarisation_probes(K)
+            U = E.to(eng.device)[:, None, :].expand(E.shape[0], eng.n, K).contiguous()
+            q = eng.vjp_wnorm(U, w, "raw").T                                            # (B, K (K + 1) / 2)
+            outs.append(covariance_from_polarisation(q, ks.to(eng.device), kps.to(eng.device), K))
+        means.append(eng.outputs().double())
+    f_mean, f_out = torch.cat(means), torch.cat(outs)
+    if cov == "diag":
+        return (f_mean.squeeze(-1), f_out.squeeze(-1)) if model_type == "regressor" else (f_mean, f_out)
+    if model_type == "regressor":
+        return MultivariateNormalFullCovariance(loc=f_mean.squeeze(), covariance_matrix=torch.diag(f_out.reshape(-1)))
+    return MultivariateNormalFullCovariance(loc=f_mean.squeeze(), covariance_matrix=f_out)
+
+
+def predict_lla_variances(map_state, Xnew, Z, model_type, alpha, full_set_size=None, batch: int = 256):
+    """Marginal variances of the inducing-point posterior: the mean f(x; theta_MAP) and the diagonal of the
+    covariances :func:`predict_lla_marginals` returns, (B, K) float64 each, without the (B, K, D) Jacobian rows:
+    var_k = (||J_k||^2 - (J W)_k C (J W)_k^T) / alpha.  ||J_k||^2 is the unweighted norm sweep of K one-hot probes
+    (:meth:`LinearizedNet.vjp_wnorm`, ``w=None``), J W one tangent-forward block of the factor rows through the test
+    batch's engine; the subtraction runs in float64.  Not a reference function."""
+    Wm, Cm = _factor_and_core(map_state, Z, model_type, alpha, full_set_size)
+    means, vars_ = [], []
+    for s0 in range(0, Xnew.shape[0], batch):
+        eng = get_engine(map_state, Xnew[s0:s0 + batch], model_type)
+        K = eng.K
+        E = torch.eye(K, device=eng.device, dtype=torch.float32)[:, None, :].expand(K, eng.n, K).contiguous()
+        jj = eng.vjp_wnorm(E, None, "raw").T.double()                                   # (B, K)
+        JW = eng.jvp(Wm, "raw").permute(1, 2, 0).double()                               # (B, K, d)
+        quad = ((JW @ Cm) * JW).sum(-1)
+        vars_.append((jj - quad) / alpha)
+        means.append(eng.outputs().double())
+    f_mean, f_var = torch.cat(means), torch.cat(vars_)
+    return (f_mean.squeeze(-1), f_var.squeeze(-1)) if model_type == "regressor" else (f_mean, f_var)
+
+
+def probit_predictive(f_mean: torch.Tensor, f_var: torch.Tensor, logvar=None):
+    """Predictive of a Gaussian over the network outputs without draws.  Classifier (``logvar`` None): the probit
+    approximation softmax(f / sqrt(1 + pi / 8 var)) -> class probabilities.  Regressor (``logvar`` = the observation
+    noise log-variance): (mean, var + exp(logvar))."""
+    if logvar is not None:
+        return f_mean, f_var + math.exp(float(logvar))
+    return torch.softmax(f_mean / torch.sqrt(1.0 + (math.pi / 8.0) * f_var), dim=-1)
 
 
 def materialize_covariance(f_cov_vp, N, out_dim, mode="diag"):
