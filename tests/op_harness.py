@@ -50,6 +50,11 @@ class SegSpec:
     a_space: str = "V"
     b_space: str = "V"
     a_odd: bool = False               # per-probe A with an odd probe stride (C % 4 != 0 only)
+    pad_w: int = None                 # padding of the W axis (None: pad, which is then the padding of both axes)
+
+    def __post_init__(self):
+        if self.pad_w is None:
+            self.pad_w = self.pad
 
     @property
     def Ktot(self):
@@ -160,7 +165,7 @@ class Harness:
         for s, sg in enumerate(spec.segs):
             seg = op.seg[s]
             seg.IH, seg.IW, seg.C, seg.KH, seg.KW = sg.IH, sg.IW, sg.C, sg.KH, sg.KW
-            seg.stride, seg.pad_h, seg.pad_w, seg.mode = sg.stride, sg.pad, sg.pad, sg.mode
+            seg.stride, seg.pad_h, seg.pad_w, seg.mode = sg.stride, sg.pad, sg.pad_w, sg.mode
             seg.flags = nv.SEG_B_TRANS if sg.b_trans else 0
             acount = spec.n_img * sg.IH * sg.IW * sg.C
             if spec.kind == nv.OP_WGRAD:               # a: shared activations, b: per-probe cotangent [P][R][N]

@@ -148,19 +148,25 @@ def out_size(I, k, s, pad):
     return (I + 2 * pad - k) // s + 1
 
 
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
 def first_argmax(x, k, s, pad):
-    """max over k x k windows of x (n, IH, IW, C) and the linear pixel index ih * IW + iw of the FIRST maximum in
-    (kh, kw) order — the rule the engine documents; written without the emulator's loops over output pixels."""
+    """max over KH x KW windows of x (n, IH, IW, C) and the linear pixel index ih * IW + iw of the FIRST maximum in
+    (kh, kw) order — the rule the engine documents; written without the emulator's loops over output pixels.
+    k and pad: one number for both axes or an (H axis, W axis) pair."""
     n, IH, IW, C = x.shape
-    OH, OW = out_size(IH, k, s, pad), out_size(IW, k, s, pad)
-    xp = torch.full((n, IH + 2 * pad + k, IW + 2 * pad + k, C), -math.inf, dtype=x.dtype)
-    xp[:, pad:pad + IH, pad:pad + IW] = x
-    pix = torch.full((IH + 2 * pad + k, IW + 2 * pad + k), -1.0, dtype=F64)
-    pix[pad:pad + IH, pad:pad + IW] = (torch.arange(IH)[:, None] * IW + torch.arange(IW)[None, :]).to(F64)
+    (KH, KW), (ph, pw) = _pair(k), _pair(pad)
+    OH, OW = out_size(IH, KH, s, ph), out_size(IW, KW, s, pw)
+    xp = torch.full((n, IH + 2 * ph + KH + s, IW + 2 * pw + KW + s, C), -math.inf, dtype=x.dtype)
+    xp[:, ph:ph + IH, pw:pw + IW] = x
+    pix = torch.full((IH + 2 * ph + KH + s, IW + 2 * pw + KW + s), -1.0, dtype=F64)
+    pix[ph:ph + IH, pw:pw + IW] = (torch.arange(IH)[:, None] * IW + torch.arange(IW)[None, :]).to(F64)
     best = torch.full((n, OH, OW, C), -math.inf, dtype=x.dtype)
     arg = torch.full((n, OH, OW, C), -1.0, dtype=F64)
-    for kh in range(k):
-        for kw in range(k):
+    for kh in range(KH):
+        for kw in range(KW):
             v = xp[:, kh:kh + s * OH:s, kw:kw + s * OW:s]
             q = pix[kh:kh + s * OH:s, kw:kw + s * OW:s][None, :, :, None].expand_as(v)
             better = v > best
@@ -172,27 +178,35 @@ def first_argmax(x, k, s, pad):
 MAPS = {"randn": lambda x: x, "relu": lambda x: x.clamp_min(0), "const": lambda x: torch.full_like(x, 0.75)}
 
 
-def _map(kind, n, I, C):
-    return lambda g: MAPS[kind](torch.randn(n, I, I, C, generator=g, dtype=F64)).float().double().reshape(1, -1)
+def _map(kind, n, IH, IW, C):
+    return lambda g: MAPS[kind](torch.randn(n, IH, IW, C, generator=g, dtype=F64)).float().double().reshape(1, -1)
 
 
-def _argmax_of(kind, n, I, C, k, s, pad):
-    """argmax of a map drawn from a generator of its own (the probes' tangents are independent of it)"""
+def _argmax_of(kind, n, IH, IW, C, k, s, pad):
+    """argmax of a map drawn from a generator of its own (the probes' tangents are independent of it).  f.swapped is
+    the argmax the SAME buffer gives when its two axes are exchanged (IW x IH pixels, KW x KH window, pad_w / pad_h):
+    what a primal pass with the axes mixed up would have cached (tests/test_small_ops_cpu.py: swap sensitivity)."""
+    def x():
+        return MAPS[kind](torch.randn(n, IH, IW, C, generator=torch.Generator().manual_seed(1234), dtype=F64)).float().double()
+
     def f(g):
-        x = MAPS[kind](torch.randn(n, I, I, C, generator=torch.Generator().manual_seed(1234), dtype=F64)).float().double()
-        return first_argmax(x, k, s, pad)[1].reshape(1, -1)
+        return first_argmax(x(), k, s, pad)[1].reshape(1, -1)
+
+    f.swapped = lambda: first_argmax(x().reshape(n, IW, IH, C), _pair(k)[::-1], s, _pair(pad)[::-1])[1].reshape(1, -1)
     return f
 
 
 def maxpool(name, route, which, C, I, k, s, pad, P=1, n=2, avg=False, kind="randn", odd=False, shift=0, dphi=False,
             red0=False, red1=False, mask=True):
-    O = out_size(I, k, s, pad)
-    cin, cout = n * I * I * C, n * O * O * C
+    """I, k, pad: one number for both axes or an (H axis, W axis) pair"""
+    (IH, IW), (KH, KW), (ph, pw) = _pair(I), _pair(k), _pair(pad)
+    OH, OW = out_size(IH, KH, s, ph), out_size(IW, KW, s, pw)
+    cin, cout = n * IH * IW * C, n * OH * OW * C
     tol = {}
     det = True
-    kavg = (k * k + 3, k * k)
+    kavg = (KH * KW + 3, KH * KW)
     if which == "primal":
-        refs = {"a": RefSpec(cin, data=_map(kind, n, I, C)), "out": RefSpec(cout, space="Y", role="out")}
+        refs = {"a": RefSpec(cin, data=_map(kind, n, IH, IW, C)), "out": RefSpec(cout, space="Y", role="out")}
         if not avg:
             refs["aux0"] = RefSpec(cout, space="Y", role="out")
             tol = {"out": "exact", "aux0": "exact"}
@@ -202,27 +216,27 @@ def maxpool(name, route, which, C, I, k, s, pad, P=1, n=2, avg=False, kind="rand
     elif which == "fwd":
         refs = {"a": RefSpec(cin, pp=True, odd=odd, shift=shift), "out": RefSpec(cout, pp=True, space="Y", role="out")}
         if not avg:
-            refs["aux0"] = RefSpec(cout, data=_argmax_of(kind, n, I, C, k, s, pad))
+            refs["aux0"] = RefSpec(cout, data=_argmax_of(kind, n, IH, IW, C, k, s, pad))
         tol = {"out": kavg if avg else "exact"}
         kindop = nv.OP_MAXPOOL_FWD
     else:
         refs = {"a": RefSpec(cout, pp=True, odd=odd, shift=shift), "out": RefSpec(cin, pp=True, space="Y", role="out")}
         if not avg:
-            refs["aux0"] = RefSpec(cout, data=_argmax_of(kind, n, I, C, k, s, pad))
-        cover = ((k + s - 1) // s) ** 2
+            refs["aux0"] = RefSpec(cout, data=_argmax_of(kind, n, IH, IW, C, k, s, pad))
+        cover = ((KH + s - 1) // s) * ((KW + s - 1) // s)
         tol = {"out": kavg if avg else (cover + 2, 1)}
         if dphi:
             refs["dphi"] = RefSpec(cin, data=_relu_mask(cin) if mask else None)
         if red1:
             refs["xhat2"] = RefSpec(cin)
             refs["red1"] = RefSpec(C, pp=True, space="Y", role="acc")
-            tol["red1"] = (n * I * I + 8, n * I * I)
+            tol["red1"] = (n * IH * IW + 8, n * IH * IW)
         if red0:
             refs["red0"] = RefSpec(C, pp=True, space="Y", role="acc")
-            tol["red0"] = (n * I * I + 8, n * I * I)
+            tol["red0"] = (n * IH * IW + 8, n * IH * IW)
         det = not (red0 or red1)
         kindop = nv.OP_MAXPOOL_BWD
-    spec = SmallSpec(kindop, P, n, O, O, C, refs, IH=I, IW=I, KH=k, KW=k, stride=s, pad=pad)
+    spec = SmallSpec(kindop, P, n, OH, OW, C, refs, IH=IH, IW=IW, KH=KH, KW=KW, stride=s, pad=ph, pad_w=pw)
     return Case(name, route, spec, tol, det=det)
 
 
@@ -271,7 +285,35 @@ def _maxpool_cases():
         maxpool("mpb_C12_I33_n41_trip2", "maxpool_bwd/scalar", "bwd", 12, 33, *W321, P=2, n=41, kind="relu", **B),
         maxpool("mpb_C64_I33_P64_trip2", "maxpool_bwd/quad", "bwd", 64, 33, *W321, P=64, n=2, kind="relu", **B),
     ]
-    return cs
+    return cs + _an_maxpool_cases()
+
+
+def _an_maxpool_cases():
+    """non-square maps, windows and paddings ("an_..."): 17 x 12 with a 3 x 2 window, padding (1, 0), stride 2 on the
+    (odd, even) map; 6 x 16 with a 2 x 3 window, padding (0, 1).  Two images each.  Exchanging the two axes in the op
+    descriptor fails the check of every one of them (tests/test_small_ops_cpu.py).  The cached argmax ih * IW + iw of
+    the max pools is bitwise: a swapped IH / IW shows there."""
+    A, Bm = ((17, 12), (3, 2), 2, (1, 0)), ((6, 16), (2, 3), 1, (0, 1))
+    B2 = ((6, 16), (2, 3), 2, (0, 1))
+    B = dict(dphi=True, red0=True, red1=True)
+    return [
+        maxpool("an_mpp_C3_17x12", "maxpool_primal/max", "primal", 3, *A),
+        maxpool("an_mpp_C64_6x16_const", "maxpool_primal/max", "primal", 64, *Bm, kind="const"),
+        maxpool("an_mpp_avg_C10_6x16_s2", "maxpool_primal/avg", "primal", 10, *B2, avg=True),
+        maxpool("an_mpp_avg_C3_17x12", "maxpool_primal/avg", "primal", 3, *A, avg=True),
+        maxpool("an_mpf_C4_17x12_relu", "maxpool_fwd/max", "fwd", 4, *A, P=3, kind="relu"),
+        maxpool("an_mpf_C64_6x16_const", "maxpool_fwd/max", "fwd", 64, *Bm, P=2, kind="const"),
+        maxpool("an_mpf_avg_C3_6x16", "maxpool_fwd/avg", "fwd", 3, *Bm, P=2, avg=True),
+        maxpool("an_mpf_avg_C64_17x12", "maxpool_fwd/avg", "fwd", 64, *A, P=3, avg=True),
+        maxpool("an_mpb_C3_17x12", "maxpool_bwd/scalar", "bwd", 3, *A, P=3, **B),
+        maxpool("an_mpb_C10_6x16_relu", "maxpool_bwd/scalar", "bwd", 10, *Bm, P=2, kind="relu", **B),
+        maxpool("an_mpb_C64_17x12_relu", "maxpool_bwd/quad", "bwd", 64, *A, P=3, kind="relu", **B),
+        maxpool("an_mpb_C64_6x16_const", "maxpool_bwd/quad", "bwd", 64, *Bm, P=3, kind="const", **B),
+        maxpool("an_mpb_avg_C3_17x12", "maxpool_bwd/scalar/avg", "bwd", 3, *A, P=3, avg=True, **B),
+        maxpool("an_mpb_avg_C10_6x16_s2", "maxpool_bwd/scalar/avg", "bwd", 10, *B2, P=1, avg=True, red0=True),
+        maxpool("an_mpb_avg_C64_6x16", "maxpool_bwd/quad/avg", "bwd", 64, *Bm, P=3, avg=True, **B),
+        maxpool("an_mpb_avg_C16_17x12", "maxpool_bwd/quad/avg", "bwd", 16, *A, P=2, avg=True),
+    ]
 
 
 # ------------------------------------------------------------------------------------------------ PRIMAL_POST

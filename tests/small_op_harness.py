@@ -50,11 +50,16 @@ class SmallSpec:
     KW: int = 0
     stride: int = 0
     pad: int = 0
+    pad_w: int = None                 # padding of the W axis (None: pad)
     act: int = 0
     classifier: int = 0
     fscale: float = 0.0
     head_mode: int = 0
     head_c: float = 1.0
+
+    def __post_init__(self):
+        if self.pad_w is None:
+            self.pad_w = self.pad
 
     @property
     def R(self):
@@ -75,7 +80,7 @@ def build_small(h, spec: SmallSpec, seed=0):
     seg.a = _ref(None)
     seg.b = _ref(None)
     seg.IH, seg.IW, seg.C, seg.KH, seg.KW = spec.IH, spec.IW, spec.N, spec.KH, spec.KW
-    seg.stride, seg.pad_h, seg.pad_w = spec.stride, spec.pad, spec.pad
+    seg.stride, seg.pad_h, seg.pad_w = spec.stride, spec.pad, spec.pad_w
     fills, outs = [], []
     for name, r in spec.refs.items():
         Pn = spec.P if r.pp else 1

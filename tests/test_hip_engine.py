@@ -22,6 +22,13 @@ F64 = torch.float64
 
 def _cases():
     g = torch.Generator().manual_seed(0)
+    from aniso_nets import engine_cases
+    cases = _square_cases(g)
+    cases.update(engine_cases(g))            # non-square inputs, after the square ones: their inputs keep their draws
+    return cases
+
+
+def _square_cases(g):
     return {
         "sine_regressor": (SimpleRegressor(8, 4), torch.randn(16, 1, dtype=F64, generator=g), "regressor", 7),
         "xor_classifier": (SimpleClassifier(16, 2, 2), torch.randn(32, 2, dtype=F64, generator=g), "classifier", 5),

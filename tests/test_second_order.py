@@ -31,14 +31,18 @@ def _cases():
         "flatten_mlp": (LargeClassifier((3, 3, 1), [5, 4], 2, 3), torch.rand(3, 3, 3, 1, dtype=F64, generator=g), "classifier"),
         "lenet_avgpool_flatdense": (_mini_lenet(), torch.rand(2, 12, 12, 1, dtype=F64, generator=g), "classifier"),
         "stem_maxpool": (_mini_stem(), torch.rand(2, 9, 9, 3, dtype=F64, generator=g), "classifier"),
+        # non-square inputs: stride 2 on an (even, odd) map (SAME: pad_h = 0, pad_w = 1), a Dense layer on a flattened 2 x 1 map
+        "an_resnet_6x9_stride2": (ResNet1M(3, input_shape=(6, 9, 3), widths=(4, 8), blocks_per_stage=1),
+                                  torch.rand(3, 6, 9, 3, dtype=F64, generator=g), "classifier"),
+        "an_lenet_12x10_flatdense": (_mini_lenet((12, 10, 1)), torch.rand(2, 12, 10, 1, dtype=F64, generator=g), "classifier"),
     }
 
 
-def _mini_lenet():
+def _mini_lenet(shape=(12, 12, 1)):
     """LeNet5's structure (src/scalemodels.py:11-49) at test size: conv + bias + ReLU, 2x2 average pool, Dense on the
     flattened map, Dense."""
     from lip_amd.netspec import NetSpec
-    net = NetSpec((12, 12, 1))
+    net = NetSpec(shape)
     x = net.conv(0, "Conv_0", 3, 5, 1, padding=2, act="relu", use_bias=True)
     x = net.avgpool(x, 2, 2)
     x = net.conv(x, "Conv_1", 4, 3, 1, padding="VALID", act="relu", use_bias=True)

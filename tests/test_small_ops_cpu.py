@@ -6,6 +6,8 @@
   and their derivatives, the column sums.
 * The float64 reference alone keeps ReLU's skipped elements within the cap the GPU test allows.
 * The harness's checks bite: a flipped argmax, a dropped red1, an output one bound off, an unwritten tail element.
+* The anisotropic window-pool rows ("an_...") can tell the two axes apart: the float64 result with IH / IW, KH / KW,
+  pad_h / pad_w and OH / OW exchanged fails check() for every one of them, and every window-pool label has such a row.
 """
 import dataclasses
 
@@ -107,52 +109,54 @@ def _nchw(x):
 
 
 def _window_pool(spec, host, L, outs, ref):
-    P, n, C, I, O, k, s, pad = spec.P, spec.n_img, spec.N, spec.IH, spec.OH, spec.KH, spec.stride, spec.pad
+    P, n, C, s = spec.P, spec.n_img, spec.N, spec.stride
+    IH, IW, OH, OW, k, pad = spec.IH, spec.IW, spec.OH, spec.OW, (spec.KH, spec.KW), (spec.pad, spec.pad_w)
     avg = "aux0" not in spec.refs
     o = _o(outs, "out")
     got = region(ref[o[1]], o)
 
-    def pool(x):                                     # (B, I, I, C) -> (B, O, O, C)
+    def pool(x):                                     # (B, IH, IW, C) -> (B, OH, OW, C)
         x = _nchw(x)
         y = Fn.avg_pool2d(x, k, s, pad, count_include_pad=True) if avg else Fn.max_pool2d(x, k, s, pad)
+        assert y.shape[2:] == (OH, OW)
         return y.permute(0, 2, 3, 1)
 
     if spec.kind == nv.OP_MAXPOOL_PRIMAL:
-        x = _in(host, L, spec, "a").reshape(n, I, I, C)
-        _close(got.reshape(n, O, O, C), pool(x))
+        x = _in(host, L, spec, "a").reshape(n, IH, IW, C)
+        _close(got.reshape(n, OH, OW, C), pool(x))
         if avg:
             return
         oa = _o(outs, "aux0")
-        am = region(ref[oa[1]], oa).reshape(n, O, O, C)
+        am = region(ref[oa[1]], oa).reshape(n, OH, OW, C)
         best, arg = first_argmax(x, k, s, pad)
         assert torch.equal(am, arg), "argmax: not the first maximum in (kh, kw) order"
         # the cached pixel lies in the window and holds the maximum
-        ih, iw = (am // I).long(), (am % I).long()
-        oh_ = torch.arange(O).reshape(1, O, 1, 1)
-        ow_ = torch.arange(O).reshape(1, 1, O, 1)
-        assert ((ih >= oh_ * s - pad) & (ih < oh_ * s - pad + k) & (iw >= ow_ * s - pad) & (iw < ow_ * s - pad + k)).all()
-        val = torch.gather(x.reshape(n, I * I, C), 1, am.long().reshape(n, O * O, C)).reshape(n, O, O, C)
-        assert torch.equal(val, got.reshape(n, O, O, C))
+        ih, iw = (am // IW).long(), (am % IW).long()
+        oh_ = torch.arange(OH).reshape(1, OH, 1, 1)
+        ow_ = torch.arange(OW).reshape(1, 1, OW, 1)
+        assert ((ih >= oh_ * s - pad[0]) & (ih < oh_ * s - pad[0] + k[0]) & (iw >= ow_ * s - pad[1]) & (iw < ow_ * s - pad[1] + k[1])).all()
+        val = torch.gather(x.reshape(n, IH * IW, C), 1, am.long().reshape(n, OH * OW, C)).reshape(n, OH, OW, C)
+        assert torch.equal(val, got.reshape(n, OH, OW, C))
         return
     if avg:
         if spec.kind == nv.OP_MAXPOOL_FWD:
-            x = _in(host, L, spec, "a").reshape(P * n, I, I, C)
-            _close(got.reshape(P * n, O, O, C), pool(x))
+            x = _in(host, L, spec, "a").reshape(P * n, IH, IW, C)
+            _close(got.reshape(P * n, OH, OW, C), pool(x))
             return
-        g = _in(host, L, spec, "a").reshape(P * n, O, O, C)
-        x = torch.zeros(P * n, I, I, C, dtype=F64, requires_grad=True)
+        g = _in(host, L, spec, "a").reshape(P * n, OH, OW, C)
+        x = torch.zeros(P * n, IH, IW, C, dtype=F64, requires_grad=True)
         v, = torch.autograd.grad(pool(x), x, g)
     else:
-        am = _in(host, L, spec, "aux0").reshape(n, O * O, C).long()
+        am = _in(host, L, spec, "aux0").reshape(n, OH * OW, C).long()
         if spec.kind == nv.OP_MAXPOOL_FWD:
-            x = _in(host, L, spec, "a").reshape(P, n, I * I, C)
-            _close(got.reshape(P, n, O * O, C), torch.gather(x, 2, am[None].expand(P, -1, -1, -1)))
+            x = _in(host, L, spec, "a").reshape(P, n, IH * IW, C)
+            _close(got.reshape(P, n, OH * OW, C), torch.gather(x, 2, am[None].expand(P, -1, -1, -1)))
             return
         # VJP of the gather y = x[argmax]: by autograd
-        g = _in(host, L, spec, "a").reshape(P, n, O * O, C)
-        x = torch.zeros(P, n, I * I, C, dtype=F64, requires_grad=True)
+        g = _in(host, L, spec, "a").reshape(P, n, OH * OW, C)
+        x = torch.zeros(P, n, IH * IW, C, dtype=F64, requires_grad=True)
         v, = torch.autograd.grad(torch.gather(x, 2, am[None].expand(P, -1, -1, -1)), x, g)
-    v = v.reshape(P, n * I * I, C)
+    v = v.reshape(P, n * IH * IW, C)
     if "dphi" in spec.refs:
         v = v * _in(host, L, spec, "dphi").reshape(1, -1, C)
     _close(got, v.reshape(P, -1))
@@ -286,3 +290,47 @@ def test_checks_catch_one_bound_off_and_an_unwritten_tail(cpu_harness, name, out
     bad[o[1]].view(torch.int32)[last] = oh.CANARY
     with pytest.raises(AssertionError, match="not written"):
         _check(case, bad, ref, mag, host, outs)
+
+
+# ---------------------------------------------------------------------------------------------- the two axes
+AN_CASES = [c for c in CASES if c.name.startswith("an_")]
+
+
+@pytest.mark.parametrize("case", AN_CASES, ids=lambda c: c.name)
+def test_axis_swap_fails_the_check(cpu_harness, case):  # noqa: F811
+    """the op emulated with the two axes exchanged in its descriptor, on the same buffers, is not accepted as the device
+    output.  A max pool's tangent and cotangent passes read the geometry only through the argmax that the primal pass
+    cached, so for them the exchanged run reads the argmax an exchanged primal pass caches from the same map."""
+    from test_kernel_routes_cpu import swap_axes
+    h = cpu_harness
+    spec = case.spec
+    assert spec.n_img >= 2 and spec.IH != spec.IW
+    op, L, host, outs, ref, mag, got = _rounded(h, case, seed=0)
+    _check(case, got, ref, mag, host, outs)                                    # the rounded reference passes
+    shost = host
+    if spec.kind != nv.OP_MAXPOOL_PRIMAL and "aux0" in spec.refs:
+        shost = {k: v.clone() for k, v in host.items()}
+        i = [n for n, r in spec.refs.items() if r.role in ("in", "idle") and r.space == "V"].index("aux0")
+        base, count, _, _ = L.regions["V"][i]
+        am = spec.refs["aux0"].data.swapped().reshape(-1).float()
+        assert not torch.equal(am, shost["V"][base:base + count])
+        shost["V"][base:base + count] = am
+    swapped = h.emulate(swap_axes(op), shost, spec.P)
+    m = oh.output_mask(host, outs)
+    bad = {k: host[k].clone() for k in host}
+    for k in bad:
+        bad[k][m[k]] = swapped[k][m[k]].float()
+    with pytest.raises(AssertionError):
+        _check(case, bad, ref, mag, host, outs)
+
+
+def test_every_window_pool_label_has_an_anisotropic_row():
+    labels = {c.route for c in CASES if c.route.startswith("maxpool_")}
+    assert len(labels) == 8, sorted(labels)
+    an = {c.route for c in AN_CASES}
+    assert an == labels, sorted(labels - an)
+    specs = [c.spec for c in AN_CASES]
+    assert all(s.n_img >= 2 and s.IH != s.IW and s.KH != s.KW and s.pad != s.pad_w for s in specs)
+    assert {(s.KH, s.KW, s.pad, s.pad_w) for s in specs} == {(3, 2, 1, 0), (2, 3, 0, 1)}
+    assert any(s.stride == 2 and s.IH % 2 == 1 and s.IW % 2 == 0 for s in specs)
+    assert any(c.name.endswith("const") for c in AN_CASES), "no tie map"

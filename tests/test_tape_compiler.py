@@ -27,6 +27,10 @@ CASES = {
     "resnet_gray": (ResNet1M(3, input_shape=(8, 8, 1), widths=(4, 8), blocks_per_stage=1),
                     torch.rand(3, 8, 8, 1, dtype=F64, generator=G), "classifier", None),
 }
+# non-square inputs: per-axis SAME padding (pad_h != pad_w at stride 2 on 10 x 7 and 11 x 8) and the flat kernels of a
+# Dense layer on a non-square map (KH != KW)
+from aniso_nets import compiler_cases  # noqa: E402
+CASES.update(compiler_cases(G))
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -10,12 +10,14 @@ pytestmark = pytest.mark.gpu
 
 
 def _binding(n, hw=32, seed=3):
+    """hw: the side of a square input, or (H, W)"""
     from lip_amd.engine import LinearizedNet
     from lip_amd.scalemodels import ResNet1M
     from lip_amd.toymodels import create_state
-    net = ResNet1M(10, input_shape=(hw, hw, 3))
+    h, w = hw if isinstance(hw, tuple) else (hw, hw)
+    net = ResNet1M(10, input_shape=(h, w, 3))
     st = create_state(net, seed=seed, dtype=torch.float32)
-    Z = torch.rand(n, hw, hw, 3, generator=torch.Generator().manual_seed(5)).cuda()
+    Z = torch.rand(n, h, w, 3, generator=torch.Generator().manual_seed(5)).cuda()
     return st, Z, LinearizedNet(st, Z, "classifier", workspace_bytes=1 << 30, max_chunk=8)
 
 
@@ -93,6 +95,34 @@ def test_ragged_tile_blocks_and_tile_rows(hw):
     err = (y_on - y_off).abs().max().item() / y_off.abs().max().item()
     assert err <= 2e-5, err
     assert not torch.equal(y_on, y_off)
+
+
+def test_non_square_maps():
+    """a 24 x 32 input: maps of 24 x 32, 12 x 16 and 6 x 8, whose tile grids (12 x 16, 6 x 8, 3 x 4) give block rectangles
+    and ragged blocks that differ between the two axes, and weight gradients whose /rowq choice follows TW alone; forced
+    against off for the GGN product and the tangents, and the primal cache bit-identical"""
+    from lip_amd import _native as nv, krylov
+    lib = nv.load()
+    before = lib.lip_get_winograd()
+    try:
+        lib.lip_set_winograd(0)
+        st, Z, eng = _binding(3, hw=(24, 32))
+        V = krylov.fill_rademacher(3, eng.D, 17, "cuda")
+        prim_off = eng.prim.clone()
+        y_off = eng.ggn_vp(V, 1.0, 0.5).clone()
+        u_off = eng.jvp(V).clone()
+        lib.lip_set_winograd(2)
+        prim_on = _binding(3, hw=(24, 32))[2].prim.clone()
+        y_on = eng.ggn_vp(V, 1.0, 0.5).clone()
+        u_on = eng.jvp(V).clone()
+    finally:
+        lib.lip_set_winograd(before)
+    assert torch.equal(prim_on, prim_off)
+    for on, off, what in ((y_on, y_off, "ggn_vp"), (u_on, u_off, "jvp")):
+        assert torch.isfinite(on).all()
+        err = (on - off).abs().max().item() / off.abs().max().item()
+        assert err <= 2e-5, (what, err)
+        assert not torch.equal(on, off), f"{what}: Winograd launches were not taken (bit-identical results)"
 
 
 def test_the_primal_tape_never_takes_the_route():

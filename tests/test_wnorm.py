@@ -354,11 +354,48 @@ WNORM_NETS = {"a": {"wgrad_wnorm<2,2,1,2>", "wgrad_wnorm<4,1,1,2>", "wgrad_wnorm
                     "wgrad_wnorm_dense", "reduce_wnorm", "wnorm_finish"},
               "b": {"wgrad_wnorm<4,1,1,1>", "wgrad_wnorm<2,2,1,1>", "wgrad_wnorm<2,1,1,1>", "wgrad_wnorm_dense",
                     "reduce_wnorm", "wnorm_finish"}}
+# non-square inputs (aniso_nets.per_example_nets): between them every tile and the dense form
+WNORM_NETS["c"] = set(WNORM_NETS["a"])
+WNORM_NETS["d"] = set(WNORM_NETS["b"])
 
 
-@pytest.mark.parametrize("which", ["a", "b"])
+def _net_of(which):
+    if which in ("c", "d"):
+        from aniso_nets import per_example_nets
+        return per_example_nets()[which]
+    return _net_a() if which == "a" else _net_b()
+
+
+@pytest.mark.parametrize("which", ["c", "d"])
+def test_non_square_nets_match_float64_rows_of_the_emulator(which):
+    """every variant on non-square maps, element by element against the float64 weighted norms of the tape emulator's
+    per-example rows (not the engine's own rows)"""
+    from test_kernel_routes import _bind
+    n, P = 3, 2
+    eng, tm, _ = _bind(_net_of(which), n, 7, P)
+    g = torch.Generator().manual_seed(3)
+    U = torch.randn(P, n, eng.K, dtype=F64, generator=g)
+    w = (torch.rand(eng.D, dtype=F64, generator=g) + 0.05).float().double()
+    rows = torch.zeros(P, n, eng.D, dtype=F64)
+    for i in range(n):
+        Ui = torch.zeros_like(U)
+        Ui[:, i] = U[:, i]
+        rows[:, i] = tm.vjp(Ui, nv.HEAD_L, 0.7)
+    _wnorm_census(eng.lib)                                   # clear
+    for wt in (w.float().cuda(), None):
+        v = eng.vjp_wnorm(U.float().cuda(), wt, "l", 0.7)
+        torch.cuda.synchronize()
+        census = _wnorm_census(eng.lib)
+        assert WNORM_NETS[which] <= set(census), f"{sorted(WNORM_NETS[which] - set(census))} not launched ({census})"
+        ref = (rows ** 2) @ (wt.double().cpu() if wt is not None else torch.ones(eng.D, dtype=F64))
+        e = _err(v.reshape(ref.shape), ref)
+        print(f"non-square net {which}, w {'given' if wt is not None else 'None'}: max|v - ref| / max ref = {e:.3g}")
+        assert e <= TOL, e
+
+
+@pytest.mark.parametrize("which", ["a", "b", "c", "d"])
 def test_census_shows_every_variant_and_values_match_rows(which):
-    net = _net_a() if which == "a" else _net_b()
+    net = _net_of(which)
     state = create_state(net, 7, dtype=F64)
     Z = torch.rand(3, *net.tensors[0], dtype=F64, generator=torch.Generator().manual_seed(7))
     eng = LinearizedNet(state, Z, "classifier", workspace_bytes=1 << 28, max_chunk=2)
