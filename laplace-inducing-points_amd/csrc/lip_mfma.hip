@@ -26,6 +26,7 @@
 #include <string.h>
 #include <atomic>
 #include <mutex>
+#include <vector>
 #include "lip_internal.h"
 
 namespace lip {
@@ -1120,17 +1121,53 @@ __global__ __launch_bounds__(256) void igemm_adirect_kernel(const IgemmP prm) {
 //     uses: with them there a group of 16 MFMAs took 5 k cycles);
 //   * output transform: over b inside the wave, over a across the four waves through LDS; wave w then owns output
 //     pixel (w >> 1, w & 1) of every tile and runs the SAME fused epilogue as the direct kernels (row table in LDS).
+//   * set-up: which pixel a staging slot holds, which tile a lane owns and where its patch lies in LDS depend on the
+//     launch geometry alone — they come from a per-geometry table (wino_table_kernel, filled once per stream and
+//     geometry); a block adds its base pixel and tests the borders against per-block scalars.  The block index is taken
+//     apart on the scalar unit.  First buffer_load at instruction ~250 of the kernel (454 with the decode in the kernel);
 // Several K-segments (tangent: conv(da, W) + conv(a, dW_p)) accumulate in the transformed domain: one output transform.
 // Mode-1 segments (data gradient, stride 1) are the same correlation with the kernel flipped — the weight transform does it.
 // Never used for the primal tape (ReLU gates / pooling arg-maxima are taken from the direct sums).
 // ------------------------------------------------------------------------------------------
 typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef int i32x4v __attribute__((ext_vector_type(4)));
 struct WinoX {
   unsigned a_bytes[3]; unsigned u_bytes[3];
-  int BWs, BHs, NI, FR, FC, nbx, nby, NS, n_img, TH, TW;
-  float inv_frfc, inv_fc;
-  FastDiv dnb, dbxy, dnbx;              // N / 32, nbx * nby, nbx
+  const i32x4v* tab;                    // geometry table of the launch (wino_table_kernel)
+  int BWs, BHs, NI, FC9, nbx, n_img, TH, TW, H;   // FC9 = 9 * FC: one footprint row in 16-byte LDS units; H = OHW / OW
+  FastDiv dnb, dbxy, dnbx, dgx;         // N / 32, nbx * nby, nbx, gridDim.x
 };
+
+// Geometry table of the Winograd kernel: everything about a block's footprint and tiles that depends on the launch
+// geometry (block rectangle, map size) but not on the block — the kernel adds one base address per block and tests the
+// borders against per-block scalars instead of decoding 7 slots and a tile per thread in each of its ~10^5 blocks.
+//   [32 rows r][16 ints]: staging slots r + 32 j, j = 0..6, as pairs {pixel offset relative to the block's first
+//       footprint pixel, sni | fr << 8 | fc << 16}; a slot past NS has sni = 255 (never below an image count).  Thread
+//       tid reads row tid >> 3: four 16-byte loads, the eight lanes of a pixel the same addresses;
+//   [32 tiles t][4 ints] from int 512: {pixel offset of the tile's first output pixel relative to the block's, ni | dy << 8
+//       | dx << 16, LDS read base of patch row 0 in 16-byte units, 0}.
+constexpr int WINO_TAB_INTS = 32 * 16 + 32 * 4;
+__global__ __launch_bounds__(256) void wino_table_kernel(int* __restrict__ tab, int BWs, int BHs, int FR, int FC, int NS, int H, int W) {
+  const int t = threadIdx.x;
+  const int r = t >> 3, j = t & 7;
+  int rel = 0, pk = 0xff;
+  const int slot = r + 32 * j;
+  if (j < 7 && slot < NS) {
+    const int sni = slot / (FR * FC), srem = slot - sni * FR * FC;
+    const int fr = srem / FC, fc = srem - fr * FC;
+    rel = (sni * H + fr) * W + fc;
+    pk = sni | (fr << 8) | (fc << 16);
+  }
+  tab[r * 16 + 2 * j] = rel;
+  tab[r * 16 + 2 * j + 1] = pk;
+  if (t < 32) {
+    const int ni = t >> (BWs + BHs), dy = (t >> BWs) & ((1 << BHs) - 1), dx = t & ((1 << BWs) - 1);
+    tab[512 + 4 * t + 0] = (ni * H + 2 * dy) * W + 2 * dx;
+    tab[512 + 4 * t + 1] = ni | (dy << 8) | (dx << 16);
+    tab[512 + 4 * t + 2] = ((ni * FR + 2 * dy) * FC + 2 * dx) * 9;
+    tab[512 + 4 * t + 3] = 0;
+  }
+}
 
 // U[xi = 4a + b][c / 4][n][c % 4] = (G w G^T)[a][b] of the 3x3 kernel w[kh][kw][c][n]  (flip: w[2-kh][2-kw]).
 // Thread (c quad, n): 9 x 4 coalesced dword reads, 16 float4 writes (consecutive n -> consecutive 16 bytes).
@@ -1292,8 +1329,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
   const int a = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, h = lane >> 5;
   const int N = prm.N;
-  const int nb = N / BN;
-  int bid = blockIdx.x, byp = blockIdx.y;
+  // this thread's rows of the geometry table, requested before anything else: staging slots (tid >> 3) + 32 j, tile l31
+  i32x4v st4[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) st4[j] = wx.tab[(tid >> 3) * 4 + j];
+  const i32x4v tile4 = wx.tab[128 + l31];
+  // block index -> (tile block (bi, by, bx), column block cb, probe p): wave-uniform, on the scalar unit
+  int bid = __builtin_amdgcn_readfirstlane((int)blockIdx.x), byp = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
   {   // XCD-contiguous order, as in igemm_fast_kernel
     const int gx = (int)gridDim.x;
     if (gx >= 64) {
@@ -1303,45 +1345,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
       const int g8 = (gx * (int)gridDim.y) & ~7, lin = bid + gx * byp;
       if (lin < g8) {
         const int w = (lin & 7) * (g8 >> 3) + (lin >> 3);
-        byp = w / gx; bid = w - byp * gx;
+        byp = wx.dgx.div(w); bid = w - byp * gx;
       }
     }
   }
-  const int tbid = wx.dnb.div(bid), cb = bid - tbid * nb;
-  const int bxy = wx.nbx * wx.nby;
-  const int bi = wx.dbxy.div(tbid), brem = tbid - bi * bxy;
+  const int tbid = wx.dnb.div(bid), cb = bid - tbid * (int)wx.dnb.d;
+  const int bi = wx.dbxy.div(tbid), brem = tbid - bi * (int)wx.dbxy.d;
   const int by = wx.dnbx.div(brem), bx = brem - by * wx.nbx;
   const int p = byp;
   const int n0 = cb * BN;
   if (tid < 2 * BN) redbuf[tid] = 0.f;
 
-  const int W = prm.OW, H = prm.OHW / prm.OW;
-  const int BW = 1 << wx.BWs, BH = 1 << wx.BHs, FR = wx.FR, FC = wx.FC;
+  const int W = prm.OW, H = wx.H;
+  // per-block scalars: images of the block that exist, first footprint pixel (ih0, iw0) and its offset
+  const int img0 = bi * wx.NI, ni_lim = min(wx.n_img - img0, wx.NI);
+  const int ty0 = by << wx.BHs, tx0 = bx << wx.BWs;
+  const int ih0 = 2 * ty0 - 1, iw0 = 2 * tx0 - 1;
+  const int fbase = (img0 * H + ih0) * W + iw0;
   // this lane's tile
-  const int ni = l31 >> (wx.BWs + wx.BHs), dy = (l31 >> wx.BWs) & (BH - 1), dx = l31 & (BW - 1);
   {
-    const int img = bi * wx.NI + ni, ty = by * BH + dy, tx = bx * BW + dx;
-    const bool tv = img < wx.n_img && ty < wx.TH && tx < wx.TW;
-    if (tid < 32) rowtab[tid] = tv ? (img * H + 2 * ty) * W + 2 * tx : -1;
+    const int ni = tile4[1] & 0xff, dy = (tile4[1] >> 8) & 0xff, dx = tile4[1] >> 16;
+    const bool tv = (ni < ni_lim) & (dy < wx.TH - ty0) & (dx < wx.TW - tx0);                  // (&: no branches in the set-up)
+    if (tid < 32) rowtab[tid] = tv ? (img0 * H + 2 * ty0) * W + 2 * tx0 + tile4[0] : -1;
   }
-  const bool blk_full = (bi * wx.NI + wx.NI <= wx.n_img) && (by * BH + BH <= wx.TH) && (bx * BW + BW <= wx.TW);
+  const bool blk_full = (wx.NI <= ni_lim) & (ty0 + (1 << wx.BHs) <= wx.TH) & (tx0 + (1 << wx.BWs) <= wx.TW);
   // rows of the 4x4 patch this wave's transform row needs:  e = d[r1] + sg d[r2]   (B^T rows: d0-d2, d1+d2, d2-d1, d1-d3)
   const int r1 = (a == 0) ? 0 : (a == 2 ? 2 : 1);
   const int r2 = (a == 0) ? 2 : (a == 1 ? 2 : (a == 2 ? 1 : 3));
   const float sg = (a == 1) ? 1.f : -1.f;
-  const int rq1 = ((ni * FR + 2 * dy + r1) * FC + 2 * dx) * 9 + h;          // LDS read bases in 16-byte units
-  const int rq2 = ((ni * FR + 2 * dy + r2) * FC + 2 * dx) * 9 + h;
-  // staging: thread -> (pixel slot, 16-byte part) x 7
+  const int rq1 = tile4[2] + r1 * wx.FC9 + h;                              // LDS read bases in 16-byte units
+  const int rq2 = tile4[2] + r2 * wx.FC9 + h;
+  // staging: thread -> (pixel slot, 16-byte part) x 7; a pixel outside the map or past the last image is not requested
   const int part = tid & 7;
   int spix[7];
 #pragma unroll
   for (int j = 0; j < 7; ++j) {
-    const int slot = (tid >> 3) + 32 * j;
-    const int sni = (int)(((float)slot + 0.5f) * wx.inv_frfc), srem = slot - sni * FR * FC;     // exact: slot < 256
-    const int fr = (int)(((float)srem + 0.5f) * wx.inv_fc), fc = srem - fr * FC;
-    const int simg = bi * wx.NI + sni, ih = 2 * by * BH - 1 + fr, iw = 2 * bx * BW - 1 + fc;
-    const bool ok = slot < wx.NS && simg < wx.n_img && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-    spix[j] = ok ? (simg * H + ih) * W + iw : -1;
+    const int rel = st4[j >> 1][2 * (j & 1)], pk = st4[j >> 1][2 * (j & 1) + 1];
+    const int sni = pk & 0xff, fr = (pk >> 8) & 0xff, fc = pk >> 16;
+    const bool ok = (sni < ni_lim) & ((unsigned)(ih0 + fr) < (unsigned)H) & ((unsigned)(iw0 + fc) < (unsigned)W);
+    spix[j] = ok ? fbase + rel : -1;
   }
 
   f32x16 acc[4];
@@ -3091,6 +3133,28 @@ static WinoGeom wino_geom(int OH, int OW, long long n_img) {
   return g;
 }
 
+// Geometry tables of the Winograd kernel, one per (device, stream, geometry): filled by wino_table_kernel on the stream
+// that first launches the geometry — the kernels of a stream are ordered, so the fill precedes every reader, with no
+// event, no host synchronisation and nothing shared between two streams that meet a geometry at the same time.  A
+// binding's geometries never change, so the steady state is a look-up.  Kept for the life of the process.  Returns null
+// when the allocation or the fill fails (the caller then leaves the Winograd route).
+static const i32x4v* wino_table(const WinoGeom& g, int H, int W, hipStream_t st) {
+  struct Entry { int dev; hipStream_t st; int BWs, BHs, H, W; int* tab; };
+  static std::vector<Entry> table;
+  static std::mutex mu;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
+  for (const Entry& e : table)      // (NI, FR, FC and NS follow from BWs and BHs)
+    if (e.dev == dev && e.st == st && e.BWs == g.BWs && e.BHs == g.BHs && e.H == H && e.W == W) return reinterpret_cast<const i32x4v*>(e.tab);
+  int* tab = nullptr;
+  if (hipMalloc((void**)&tab, WINO_TAB_INTS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  hipLaunchKernelGGL(wino_table_kernel, dim3(1), dim3(256), 0, st, tab, g.BWs, g.BHs, g.FR, g.FC, g.NS, H, W);
+  if (hipGetLastError() != hipSuccess) { (void)hipFree(tab); return nullptr; }
+  table.push_back(Entry{dev, st, g.BWs, g.BHs, H, W, tab});
+  return reinterpret_cast<const i32x4v*>(tab);
+}
+
 static bool igemm_wino_ok(const IgemmP& p, int P) {
   const int mode = wino_mode();
   if (mode == 0 || precision_mode() != 0 || p.no_ksplit) return false;
@@ -3138,10 +3202,13 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st) {
   }
   for (int s = p.nseg; s < 3; ++s) { wx.a_bytes[s] = 0; wx.u_bytes[s] = 0; }
   const WinoGeom g = wino_geom(OH, p.OW, n_img);
-  wx.BWs = g.BWs; wx.BHs = g.BHs; wx.NI = g.NI; wx.FR = g.FR; wx.FC = g.FC; wx.nbx = g.nbx; wx.nby = g.nby; wx.NS = g.NS;
-  wx.n_img = (int)n_img; wx.TH = g.TH; wx.TW = g.TW;
-  wx.inv_frfc = 1.f / (float)(g.FR * g.FC); wx.inv_fc = 1.f / (float)g.FC;
+  wx.tab = wino_table(g, OH, p.OW, st);
+  if (!wx.tab) return hipErrorOutOfMemory;
+  wx.BWs = g.BWs; wx.BHs = g.BHs; wx.NI = g.NI; wx.FC9 = 9 * g.FC; wx.nbx = g.nbx;
+  wx.n_img = (int)n_img; wx.TH = g.TH; wx.TW = g.TW; wx.H = OH;
+  const long long gx = (long long)g.nbx * g.nby * g.nbi * (p.N / 32);
   wx.dnb = FastDiv((unsigned)(p.N / 32)); wx.dbxy = FastDiv((unsigned)(g.nbx * g.nby)); wx.dnbx = FastDiv((unsigned)g.nbx);
+  wx.dgx = FastDiv((unsigned)gx);
   q.zeros = nullptr; q.dbg = nullptr; q.partial = nullptr;
   const size_t shmem = (size_t)(8192 + 32 + 64) * sizeof(float);
   static bool attr_set = false;
@@ -3155,7 +3222,7 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st) {
   auto al16 = [](const void* ptr, long long ps) { return ptr == nullptr || ((((uintptr_t)ptr) & 15) == 0 && (ps & 3) == 0); };
   static const bool novepi = getenv("LIP_WINO_NOVEPI") != nullptr;
   const bool vepi = !novepi && al16(p.out, p.out_ps) && al16(p.res, p.res_ps) && al16(p.xhat, 0) && al16(p.dphi, 0) && al16(p.xhat2, 0);
-  dim3 grid((unsigned)((long long)g.nbx * g.nby * g.nbi * (p.N / 32)), (unsigned)P, 1);
+  dim3 grid((unsigned)gx, (unsigned)P, 1);
   if (vepi) { LIP_ROUTE("igemm_wino/vepi"); hipLaunchKernelGGL(igemm_wino_kernel<true>, grid, dim3(256), shmem, st, q, wx); }
   else { LIP_ROUTE("igemm_wino"); hipLaunchKernelGGL(igemm_wino_kernel<false>, grid, dim3(256), shmem, st, q, wx); }
   return hipGetLastError();
