@@ -173,6 +173,10 @@ def _wgrad_cases() -> List[Case]:
         # probe-batched tiles (N <= 64, M >= 96; N = 16 keeps the 3 x 3 layers off the Winograd route)
         Case("wg_pb96_288", "wgrad_pb<1,4,3,1>", wgrad(1, 8, 32, 16, 4), det=False),
         Case("wg_pb96_576", "wgrad_pb<1,4,3,1>", wgrad(2, 6, 64, 16, 9, epi={"scale": "shared"}), det=False),
+        # N = 64, M = 576 (the 64-channel 3 x 3 layers of the CIFAR net): the only shape that takes the 96-row tile through
+        # the clause "M % 96 == 0 && M % 128 != 0" of launch_wgrad (N <= 32 takes the probe-batched branch without it);
+        # the 7 x 7 map keeps it off the Winograd route
+        Case("wg_pb96_N64_M576", "wgrad_pb<1,4,3,1>", wgrad(1, 7, 64, 64, 4), det=False),
         Case("wg_pb96_x3", "wgrad_pb<3,1,1,4>/x3", wgrad(1, 8, 32, 16, 4), prec=1, tol="x3", det=False),
         Case("wg_pb128", "wgrad_pb<2,2,2,2>", wgrad(1, 8, 16, 32, 4), det=False),
         Case("wg_pb128_P7N12", "wgrad_pb<2,2,2,2>", wgrad(1, 8, 16, 12, 7), det=False),
@@ -319,6 +323,7 @@ def _an_wgrad_cases() -> List[Case]:
         # probe-batched tiles; stride 2 on an (even, odd) map
         Case("an_wg_pb96_pad10", "wgrad_pb<1,4,3,1>", wgrad(2, 6, 32, 16, 4, W=10, pad=1, pad_w=0), det=False),
         Case("an_wg_pb96_k2x3", "wgrad_pb<1,4,3,1>", wgrad(2, 9, 16, 32, 3, W=5, k=2, kw=3), det=False),
+        Case("an_wg_pb96_N64_M576", "wgrad_pb<1,4,3,1>", wgrad(2, 5, 64, 64, 4, W=9), det=False),
         Case("an_wg_pb128_s2_10x7", "wgrad_pb<2,2,2,2>", wgrad(2, 10, 16, 32, 4, W=7, s=2, pad=0, pad_w=1), det=False),
         # per-probe tiles: wide and tall maps, anisotropic windows with unequal padding
         Case("an_wg_fast_wide_v4", "wgrad_fast<2,2,1,2>/v4", wgrad(2, 6, 4, 128, 2, W=20), det=False),

@@ -18,7 +18,7 @@ ROW_LAUNCH = {"bdot": (8192, 256), "axpby": (2048, 2048), "cg_update": (4096, 10
 KRYLOV_ROUTES = {"dot_nt/quad/part", "dot_nt/quad/atomic", "dot_nt/tile/part", "dot_nt/tile/atomic", "dot_nt/valu/part",
                  "dot_nt/valu/atomic", "rows_combine<4>", "rows_combine<12>", "gemm_nt/ks1", "gemm_nt/ks", "gemm_nn_axpy",
                  "fill_normal", "fill_rademacher"}
-VALU_ONLY = {"dot_nt/valu/part", "dot_nt/valu/atomic"}      # LIP_DOT_NT_VALU, read once per process: never set by a test
+VALU_ONLY = {"dot_nt/valu/part", "dot_nt/valu/atomic"}      # LIP_DOT_NT_VALU, read once per process: tests/test_ab_switches.py
 
 
 @dataclass

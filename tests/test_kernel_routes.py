@@ -3,7 +3,8 @@
 Each row of tests/kernel_route_cases.py is one synthetic IGEMM / WGRAD op run through lip_engine_run_op.  The test
 asserts that the route census of that call is exactly the expected route, then checks every output element against
 the float64 emulator (tests/op_harness.py: bound on Mag, RMS, canaries, accumulation, determinism).  The coverage
-test asserts that the table reaches every route the library lists except the A/B-only ones below.
+test asserts that the table reaches every route the library lists except the A/B-only ones below, and that each of
+those is an expected route of tests/ab_switch_cases.py (run by tests/test_ab_switches.py in child processes).
 """
 import pytest
 import torch
@@ -18,7 +19,8 @@ pytestmark = pytest.mark.gpu
 
 MI355X_CUS = 256
 
-# routes reachable only through an A/B environment switch (read once per process, so never set by a test)
+# routes reachable only through an A/B environment switch (read once per process: tests/test_ab_switches.py runs each of
+# them in a child process of its own, from the table tests/ab_switch_cases.py)
 AB_ONLY = {
     "igemm_fast<4,1,1,2>", "igemm_fast<4,1,1,2>/bv4",      # LIP_NOADIRECT: the 128-row f32 tiles take igemm_adirect
     "igemm_fast<4,1,1,1>", "igemm_fast<4,1,1,1>/bv4",      # (same switch)
@@ -142,6 +144,9 @@ def test_table_reaches_every_route():
     assert AB_ONLY <= every and SQSUM_ROUTES <= every and SMALL_ROUTES <= every and KRYLOV_ROUTES <= every
     assert {r for r in every if "sqsum" in r} == SQSUM_ROUTES
     assert not (table & AB_ONLY), sorted(table & AB_ONLY)
+    from ab_switch_cases import ENTRIES
+    switched = {route for e in ENTRIES for _, route in e.rows}
+    assert AB_ONLY <= switched, f"A/B-only routes without a row in ab_switch_cases.py: {sorted(AB_ONLY - switched)}"
     missing = every - AB_ONLY - SQSUM_ROUTES - SMALL_ROUTES - KRYLOV_ROUTES - table
     assert not missing, f"routes without a case in kernel_route_cases.py: {sorted(missing)}"
     assert table <= every, sorted(table - every)

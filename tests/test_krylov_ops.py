@@ -6,7 +6,8 @@ tests/krylov_harness.py (bases 0..3 floats off a 16-byte boundary, strides, NaN 
 exact integer inputs — the result must EQUAL the float64 reference — and once with random inputs, bounded per element on
 Mag.  The census label of the call is asserted where the launcher chooses a kernel or a reduction mode.  The fills are
 compared with a numpy Philox4x32-10, the refusals of the extern "C" wrappers are called one by one, and the coverage
-test asserts that the table reaches every Krylov label except the two behind the LIP_DOT_NT_VALU switch.
+test asserts that the table reaches every Krylov label except the two behind the LIP_DOT_NT_VALU switch, and that those
+two are expected routes of tests/ab_switch_cases.py (run by tests/test_ab_switches.py in a child process).
 """
 import numpy as np
 import pytest
@@ -64,6 +65,9 @@ def test_table_reaches_every_krylov_route():
     assert table <= KRYLOV_ROUTES
     missing = KRYLOV_ROUTES - table
     assert missing == VALU_ONLY, f"Krylov labels without a case: {sorted(missing - VALU_ONLY)}"
+    from ab_switch_cases import ENTRIES
+    switched = {route for e in ENTRIES for _, route in e.rows}
+    assert VALU_ONLY <= switched, f"labels behind a switch without a row in ab_switch_cases.py: {sorted(VALU_ONLY - switched)}"
     assert not [r for r in every if r.split("/")[0].split("<")[0] in {"dot_nt", "rows_combine", "gemm_nt", "gemm_nn_axpy",
                                                                      "fill_normal", "fill_rademacher"} and r not in KRYLOV_ROUTES]
 
