@@ -170,6 +170,12 @@ int lip_debug_routes(int64_t* counts, int32_t n, const char** names);
 /* Y[p] = scale * sum_i J_i^T H_i J_i V[p] + alpha * V[p]      src/ggn.py:133-144, src/lla.py:21-22
  * (scale carries N/M and, for the regressor, exp(-logvar): src/ggn.py:111-113)           */
 int lip_ggn_vp(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale, float alpha, void* stream);
+/* Y[p] = scale * sum_i J_i^T H_i J_i V[p] + a (.) V[p]: lip_ggn_vp with a VECTOR prior precision A = diag(a) in place of
+ * alpha I (generalises src/lla.py:21-22; one precision per layer is a = alpha_{g(j)}).  a is a (D,) device vector in
+ * flat-parameter order.  Chunking, checks and status codes are those of lip_ggn_vp (not bound: LIP_ERR_STATE before Y is
+ * touched; a null V / Y / a: LIP_ERR_ARG): the sweep runs as lip_ggn_vp's with alpha = 0, then one streaming pass adds
+ * a (.) V over the probe chunk (no float atomics; V is not written).                                            */
+int lip_ggn_vp_diag(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale, const float* a, void* stream);
 /* U[p,i,:] = c * L_i^T J_i V[p]   (mode LIP_HEAD_LT, src/ggn.py:55-62,84-85) or J_i V[p] (LIP_HEAD_OUT) */
 int lip_jvp(lip_engine_t* e, const float* V, float* U, int32_t P, int32_t head_mode, float c, void* stream);
 /* Y[p] = sum_i J_i^T (c * L_i U[p,i,:])  (LIP_HEAD_L, src/ggn.py:64-76,87-91) or raw (LIP_HEAD_IN) */
@@ -212,6 +218,11 @@ int lip_debug_wnorm_routes(int64_t* counts, int32_t n, const char** names);
  * jax.scipy.sparse.linalg.cg (src/stochtrace.py:146,192; src/sample.py:71) and the
  * Hutchinson quadratic forms (src/stochtrace.py:30-34).                                 */
 int lip_bdot(const float* X, const float* Y, float* out /*[P], overwritten*/, int32_t P, int64_t N, void* stream);
+/* out[p] = sum_j w[j] X[p][j] Y[p][j], w (N,): lip_bdot in the metric diag(w) — the prior term v^T A v of the quadratic
+ * forms of lip_ggn_vp_diag's operator (generalises alpha <v, v>, src/lla.py:21-22) without a (P, N) temporary.  X, Y as
+ * for lip_bdot (shared alignment modulo 16 bytes); w at any 4-byte alignment.  Same order of the sums as lip_bdot.  */
+int lip_bdot_w(const float* X, const float* Y, const float* w, float* out /*[P], overwritten*/, int32_t P, int64_t N,
+               void* stream);
 int lip_axpby(float* Y, const float* X, const float* a /*[P] or NULL*/, float a_s, const float* b /*[P] or NULL*/,
               float b_s, int32_t P, int64_t N, void* stream);      /* Y[p] = (a_s*a[p]) X[p] + (b_s*b[p]) Y[p] */
 /* Lanczos basis Q is (P, kmax, ldq): row stride ldq >= N with ldq % 4 == 0 and a 16-byte aligned base, so the

@@ -73,6 +73,7 @@ SIGNATURES = {
     "lip_debug_route_count": (C.c_int, []),
     "lip_debug_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_char_p)]),
     "lip_ggn_vp": (C.c_int, [_V, _V, _V, C.c_int32, C.c_float, C.c_float, _V]),
+    "lip_ggn_vp_diag": (C.c_int, [_V, _V, _V, C.c_int32, C.c_float, _V, _V]),
     "lip_jvp": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V]),
     "lip_vjp": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V]),
     "lip_vjp_rows": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V]),
@@ -83,6 +84,7 @@ SIGNATURES = {
     "lip_debug_wnorm_route_count": (C.c_int, []),
     "lip_debug_wnorm_routes": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_char_p)]),
     "lip_bdot": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int64, _V]),
+    "lip_bdot_w": (C.c_int, [_V, _V, _V, _V, C.c_int32, C.c_int64, _V]),
     "lip_axpby": (C.c_int, [_V, _V, _V, C.c_float, _V, C.c_float, C.c_int32, C.c_int64, _V]),
     "lip_multi_dot": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _V]),
     "lip_multi_axpy_norm": (C.c_int, [_V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _V]),

@@ -591,6 +591,26 @@ int lip_ggn_vp(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale
   return LIP_OK;
 }
 
+int lip_ggn_vp_diag(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale, const float* a, void* stream) {
+  int rc = ready(e, "lip_ggn_vp_diag");
+  if (rc) return rc;
+  if (!V || !Y || !a || P <= 0) { set_error("lip_ggn_vp_diag: bad argument"); return LIP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  for (int c0 = 0, step = balanced_chunk(P, e->max_chunk); c0 < P; c0 += step) {
+    const int pc = (P - c0) < step ? (P - c0) : step;
+    const float* v = V + (int64_t)c0 * e->D;
+    float* y = Y + (int64_t)c0 * e->D;
+    // the sweep of lip_ggn_vp with alpha = 0 (its overwrite plan unchanged), then the prior term over the chunk
+    RunCtx c{e, v, y, nullptr, pc, LIP_HEAD_GGN, scale, st};
+    c.fuse = true; c.alpha = 0.f;
+    if ((rc = init_output(c, e->D))) return rc;
+    if ((rc = run_tape(c, LIP_TAPE_TANGENT, false))) return rc;
+    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, true))) return rc;
+    RUN_CHECK(launch_add_diag(y, v, a, pc, (long long)e->D, st), "add_diag");
+  }
+  return LIP_OK;
+}
+
 int lip_jvp(lip_engine_t* e, const float* V, float* U, int32_t P, int32_t head_mode, float cc, void* stream) {
   int rc = ready(e, "lip_jvp");
   if (rc) return rc;

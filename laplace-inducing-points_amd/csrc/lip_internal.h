@@ -182,6 +182,8 @@ hipError_t launch_scale_copy(float* y, const float* x, float a, long long count,
 // y[p][off + i] = a * x[p][off + i] (x null: 0) for i < len, p < P, row stride ld: the parameters a fused weight gradient
 // does NOT write (biases, BN parameters, layers on the accumulate path)
 hipError_t launch_scale_copy_range(float* y, const float* x, float a, long long off, long long len, int P, long long ld, hipStream_t st);
+// y[p][j] += a[j] * x[p][j], p < P, j < N (rows of N floats): the vector-prior term of lip_ggn_vp_diag
+hipError_t launch_add_diag(float* y, const float* x, const float* a, int P, long long N, hipStream_t st);
 // true when launch_wgrad(p, P) will run the one-block-per-tile kernel that honours WgradP::overwrite
 bool wgrad_will_overwrite(const WgradP& p, int P);
 

@@ -69,6 +69,29 @@ __global__ __launch_bounds__(KT) void bdot_kernel(const float* X, const float* Y
   if (threadIdx.x == 0) atomicAdd(out + p, t);
 }
 
+// ---- out[p] = sum_j w[j] X[p][j] Y[p][j]: bdot_kernel with a weight vector shared by the rows (the prior term
+// v^T diag(a) v of a vector prior precision).  Same split of a row and same order of the sums as bdot_kernel; w is
+// read as quads where it shares the row's alignment modulo 16 bytes and as dwords otherwise (rows of an odd-N block
+// differ from one another) ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(KT) void bdot_w_kernel(const float* X, const float* Y, const float* w, float* out, long long N) {
+  __shared__ float sm[KT / 64];
+  const int p = blockIdx.y;
+  const float* x = X + (long long)p * N;
+  const float* y = Y + (long long)p * N;
+  const RowSplit s = split_row(x, N);
+  const bool w4 = ((((unsigned long long)x) ^ ((unsigned long long)w)) & 15ull) == 0;
+  float acc = 0.f;
+  row_apply(s, N,
+            [&](long long o) {
+              const float4 a = LD4(x, o), b = LD4(y, o);
+              const float4 c = w4 ? LD4(w, o) : make_float4(w[o], w[o + 1], w[o + 2], w[o + 3]);
+              acc += c.x * a.x * b.x + c.y * a.y * b.y + c.z * a.z * b.z + c.w * a.w * b.w;
+            },
+            [&](long long o) { acc += w[o] * x[o] * y[o]; });
+  const float t = block_sum(acc, sm);
+  if (threadIdx.x == 0) atomicAdd(out + p, t);
+}
+
 // ---- Y[p] = ca[p] X[p] + cb[p] Y[p] --------------------------------------------------------------------
 __global__ __launch_bounds__(KT) void axpby_kernel(float* Y, const float* X, const float* a, float a_s,
                                                    const float* b, float b_s, long long N) {
@@ -666,6 +689,16 @@ int lip_bdot(const float* X, const float* Y, float* out, int32_t P, int64_t N, v
   hipStream_t st = (hipStream_t)stream;
   LIP_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float) * P, st));
   hipLaunchKernelGGL(bdot_kernel, dim3(nblk_for(N, CHUNK * 4, 256), P), dim3(KT), 0, st, X, Y, out, (long long)N);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_bdot_w(const float* X, const float* Y, const float* w, float* out, int32_t P, int64_t N, void* stream) {
+  if (!X || !Y || !w || !out || P <= 0 || N <= 0) { set_error("lip_bdot_w: bad argument"); return LIP_ERR_ARG; }
+  if (!same_alignment(X, Y)) { set_error("lip_bdot_w: X and Y must share 16-byte alignment"); return LIP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  LIP_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(float) * P, st));
+  hipLaunchKernelGGL(bdot_w_kernel, dim3(nblk_for(N, CHUNK * 4, 256), P), dim3(KT), 0, st, X, Y, w, out, (long long)N);
   LIP_CHECK_HIP(hipGetLastError());
   return LIP_OK;
 }

@@ -810,4 +810,45 @@ hipError_t launch_scale_copy(float* y, const float* x, float a, long long count,
   return hipGetLastError();
 }
 
+// ---- y[p] += a (.) x[p]: the prior term of lip_ggn_vp_diag (a vector prior precision A = diag(a) in place of
+// alpha I, src/lla.py:21-22), added after a sweep that ran with alpha = 0.  A row whose three operands share their
+// alignment modulo 16 bytes streams as scalar head | float4 body | scalar tail; any other row runs on dwords (rows of an
+// odd-D block differ from one another, so the choice is per row).  Grid-stride in both axes, no atomics: every element
+// has one writer. ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void add_diag_kernel(float* __restrict__ Y, const float* __restrict__ X,
+                                                       const float* __restrict__ a, long long N, int P) {
+  const long long t0 = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+  for (int p = blockIdx.y; p < P; p += gridDim.y) {
+    float* y = Y + (long long)p * N;
+    const float* x = X + (long long)p * N;
+    const unsigned long long ya = (unsigned long long)y, xa = (unsigned long long)x, aa = (unsigned long long)a;
+    if ((((ya ^ xa) | (ya ^ aa)) & 15ull) == 0) {
+      long long h = (4 - (long long)((ya >> 2) & 3)) & 3;      // scalars up to the first 16-byte boundary
+      if (h > N) h = N;
+      const long long G = (N - h) >> 2;
+      for (long long g = t0; g < G; g += step) {
+        const long long o = h + 4 * g;
+        const float4 xv = *reinterpret_cast<const float4*>(x + o), av = *reinterpret_cast<const float4*>(a + o);
+        float4 yv = *reinterpret_cast<const float4*>(y + o);
+        yv.x += av.x * xv.x; yv.y += av.y * xv.y; yv.z += av.z * xv.z; yv.w += av.w * xv.w;
+        *reinterpret_cast<float4*>(y + o) = yv;
+      }
+      if (blockIdx.x == 0) {
+        for (long long i = threadIdx.x; i < h; i += 256) y[i] += a[i] * x[i];
+        for (long long i = h + 4 * G + threadIdx.x; i < N; i += 256) y[i] += a[i] * x[i];
+      }
+    } else {
+      for (long long i = t0; i < N; i += step) y[i] += a[i] * x[i];
+    }
+  }
+}
+
+hipError_t launch_add_diag(float* y, const float* x, const float* a, int P, long long N, hipStream_t st) {
+  if (P <= 0 || N <= 0) return hipSuccess;
+  const long long blocks = (N + 1023) / 1024;                   // one quad per thread and pass
+  hipLaunchKernelGGL(add_diag_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024), (unsigned)(P < 1024 ? P : 1024)), dim3(256),
+                     0, st, y, x, a, N, P);
+  return hipGetLastError();
+}
+
 }  // namespace lip

@@ -549,6 +549,7 @@ class LinearizedNet:
 
     Block operators on (P, D) row-major float32 device tensors:
       ``ggn_vp(V, scale, alpha)`` -> (P, D)      Y = scale * sum_i J_i^T H_i J_i V + alpha V
+      ``ggn_vp_diag(V, scale, a)`` -> (P, D)     the same with a (D,) prior-precision vector: ... + a (.) V
       ``jvp(V, mode, c)``         -> (P, n, K)   c * L^T J V   ('lt')   or   J V   ('raw')
       ``vjp(U, mode, c)``         -> (P, D)      J^T (c * L U) ('l')    or   J^T U ('raw')
     """
@@ -656,6 +657,18 @@ class LinearizedNet:
         Y = out if out is not None else torch.empty_like(Vb)
         nv.check(self.lib.lip_ggn_vp(self.h, nv.ptr(Vb), nv.ptr(Y), Vb.shape[0], float(scale), float(alpha),
                                      nv.stream_ptr()), "lip_ggn_vp")
+        return Y
+
+    def ggn_vp_diag(self, V: torch.Tensor, scale: float, a: torch.Tensor, out: Optional[torch.Tensor] = None):
+        """:meth:`ggn_vp` with a vector prior precision: Y = scale * sum_i J_i^T H_i J_i V + a (.) V, ``a`` a (D,) vector
+        in flat-parameter order (``lip_ggn_vp_diag``).  V is not written."""
+        Vb = self._block(V, self.D)
+        a = a.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        if a.numel() != self.D:
+            raise ValueError(f"a must hold {self.D} precisions, got {tuple(a.shape)}")
+        Y = out if out is not None else torch.empty_like(Vb)
+        nv.check(self.lib.lip_ggn_vp_diag(self.h, nv.ptr(Vb), nv.ptr(Y), Vb.shape[0], float(scale), nv.ptr(a),
+                                          nv.stream_ptr()), "lip_ggn_vp_diag")
         return Y
 
     def run_op(self, op: "nv.Op", P: int, V: Optional[torch.Tensor] = None, Y: Optional[torch.Tensor] = None,

@@ -146,6 +146,21 @@ def attach_quadratic_forms(op: "BlockOperator", eng, scale: float, alpha: float 
     return op
 
 
+def attach_quadratic_forms_diag(op: "BlockOperator", eng, scale: float, a: torch.Tensor) -> "BlockOperator":
+    """:func:`attach_quadratic_forms` for a vector prior precision: v^T (scale GGN + diag(a)) v.  The GGN term is the same
+    tangent-forward sweep; the prior term sum_j a_j v_j^2 is one weighted dot (``lip_bdot_w``), no (P, D) temporary."""
+    from . import krylov
+    c = math.sqrt(scale)
+
+    def quadratic_forms(V):
+        Vb = V.to(device=eng.device, dtype=torch.float32).contiguous()
+        U = eng.jvp(Vb, "lt", c).double().reshape(Vb.shape[0], -1)
+        return (U * U).sum(1) + krylov.bdot_w(Vb, Vb, a).double()
+
+    op.quadratic_forms = quadratic_forms
+    return op
+
+
 def _logvar(state):
     return float(torch.as_tensor(state.params["logvar"]["logvar"]).detach().cpu())
 
@@ -259,6 +274,24 @@ def gram_from_factor(Wm: torch.Tensor) -> torch.Tensor:
         tail = Wm[:, body:].double()
         G += tail @ tail.T
     return G
+
+
+def grouped_grams(Wm: torch.Tensor, prior) -> torch.Tensor:
+    """(G, d, d) float64: G_g = Wm[:, S_g] Wm[:, S_g]^T, the Gram of the factor restricted to the columns of group g of a
+    :class:`prior.GroupedPrior`.  They do not depend on the precisions: det(A + beta W W^T) = prod_g alpha_g^{D_g} *
+    det(I_d + beta sum_g G_g / alpha_g), so the layer-wise evidence and its gradient are d x d algebra after this one
+    pass.  One float64-accumulated product per segment on the column slice (``lip_dot_nt_f64`` takes the row stride D);
+    the segments partition the columns, so the factor is read once in total; ``.sum(0)`` is :func:`gram_from_factor`."""
+    from . import krylov
+    d, D = Wm.shape
+    if prior.D != D:
+        raise ValueError(f"the prior covers {prior.D} parameters, the factor has {D} columns")
+    out = torch.zeros(prior.G, d, d, device=Wm.device, dtype=torch.float64)
+    for g in range(prior.G):
+        for o, n in prior.segments(g):
+            blk = Wm[:, o:o + n]
+            out[g] += krylov.dot_nt(blk, blk)
+    return 0.5 * (out + out.transpose(1, 2))
 
 
 def compute_ggn_vp(state, Z, model_type, full_set_size=None, mode: str = "matfree"):

@@ -34,6 +34,18 @@ def bdot(X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def bdot_w(X: torch.Tensor, Y: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """out[p] = sum_j w[j] X[p][j] Y[p][j] for a (N,) weight vector w: :func:`bdot` in the metric diag(w), no (P, N)
+    temporary (``lip_bdot_w``)"""
+    lib = nv.load()
+    P, N = _chk(X).shape
+    if _chk(w).numel() != N:
+        raise ValueError(f"bdot_w: w must hold {N} weights, got {tuple(w.shape)}")
+    out = torch.empty(P, device=X.device, dtype=torch.float32)
+    nv.check(lib.lip_bdot_w(nv.ptr(X), nv.ptr(_chk(Y)), nv.ptr(w), nv.ptr(out), P, N, nv.stream_ptr()), "lip_bdot_w")
+    return out
+
+
 def axpby(Y, X, a: Optional[torch.Tensor] = None, a_s: float = 1.0, b: Optional[torch.Tensor] = None, b_s: float = 1.0):
     """in place: Y[p] = (a_s a[p]) X[p] + (b_s b[p]) Y[p]"""
     lib = nv.load()

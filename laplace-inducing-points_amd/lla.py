@@ -15,17 +15,24 @@ import torch
 from .distributions import MultivariateNormalDiag, MultivariateNormalFullCovariance
 from .engine import LinearizedNet
 from .ggn import BlockOperator, compute_ggn_dense, compute_ggn_diag, compute_ggn_vp, get_engine
+from .prior import check_dim, is_grouped
 from .sample import sample, sample_diag
 from .utils import flatten_nn_params
 
 
 def compute_curvature_approx(map_state, Z, model_type, alpha, full_set_size=None):
-    """``src/lla.py:11-23``: v -> GGN v + alpha v (alpha fused into the engine call)."""
+    """``src/lla.py:11-23``: v -> GGN v + alpha v (alpha fused into the engine call).  With a
+    :class:`prior.GroupedPrior` for ``alpha``: v -> GGN v + a (.) v (``lip_ggn_vp_diag``)."""
     vp = compute_ggn_vp(map_state, Z, model_type=model_type, full_set_size=full_set_size)
     eng = vp.engine
     M = Z.shape[0]
     N = full_set_size or M
     scale = N / M * (math.exp(-float(map_state.params["logvar"]["logvar"])) if model_type == "regressor" else 1.0)
+    if is_grouped(alpha):
+        from .ggn import attach_quadratic_forms_diag
+        a = check_dim(alpha, eng.D).vector(eng.device)
+        return attach_quadratic_forms_diag(BlockOperator(lambda V: eng.ggn_vp_diag(V, scale, a), (eng.D,), (eng.D,), eng,
+                                                         "curvature_vp[grouped]"), eng, scale, a)
     from .ggn import attach_quadratic_forms
     return attach_quadratic_forms(BlockOperator(lambda V: eng.ggn_vp(V, scale, float(alpha)), (eng.D,), (eng.D,), eng, "curvature_vp"),
                                   eng, scale, float(alpha))
@@ -120,6 +127,8 @@ def posterior_lla_diag(map_state, Z, model_type, alpha, full_set_size=None) -> M
     diag = compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size)
     flat_params, _ = flatten_nn_params(map_state.params)
     loc = flat_params.detach().to(device=diag.device, dtype=diag.dtype)
+    if is_grouped(alpha):
+        return MultivariateNormalDiag(loc, variance=1.0 / (check_dim(alpha, diag.numel()).vector(diag.device) + diag))
     return MultivariateNormalDiag(loc, variance=1.0 / (float(alpha) + diag))
 
 
@@ -145,14 +154,24 @@ def _cross_gram64(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
 
 def _factor_and_core(map_state, Z, model_type, alpha, full_set_size):
     """The factor Wm (d, D) of the inducing-point GGN and C = (alpha/beta I + Wm Wm^T)^-1 on range(Wm Wm^T) (float64):
-    S = alpha^-1 (I - Wm^T C Wm)."""
-    from .ggn import gram_from_factor, materialize_factor
+    S = alpha^-1 (I - Wm^T C Wm).
+    With a :class:`prior.GroupedPrior` (A = diag(a)): Gt = sum_g G_g / alpha_g = Wm A^-1 Wm^T, C = (I/beta + Gt)^-1 on
+    range(Gt) with the same eigenvalue cut, S = A^-1 - A^-1 Wm^T C Wm A^-1 (Woodbury); the factor then comes back with
+    its columns scaled, Wm A^-1, the only form the predictives use (one (d, D) block is held, not two)."""
+    from .ggn import gram_from_factor, grouped_grams, materialize_factor
     eng_z = get_engine(map_state, Z, model_type)
     M = Z.shape[0]
     N = full_set_size or M
     beta = N / M
     c = math.exp(-0.5 * float(map_state.params["logvar"]["logvar"])) if model_type == "regressor" else 1.0
     Wm = materialize_factor(eng_z, c)                                   # (d, D)
+    if is_grouped(alpha):
+        grams = grouped_grams(Wm, check_dim(alpha, eng_z.D))
+        Gt = (grams / alpha.values.to(grams.device)[:, None, None]).sum(0)
+        lam, Ug = torch.linalg.eigh(0.5 * (Gt + Gt.T))
+        keep = lam > 1e-6 * lam.max().clamp_min(1e-300)
+        Cm = (Ug * torch.where(keep, 1.0 / (1.0 / beta + lam.clamp_min(0.0)), torch.zeros_like(lam))) @ Ug.T
+        return Wm * (1.0 / alpha.vector(Wm.device, torch.float64)).float(), Cm
     Gd = gram_from_factor(Wm)
     # (alpha/beta I + Gd)^-1 restricted to range(Gd): on the null space of Gd (the classifier's factor has rank
     # M (K-1)) J W vanishes exactly, but its rounding error would be amplified by beta/alpha there
@@ -175,15 +194,24 @@ def predict_lla_marginals(map_state, Xnew, Z, model_type, alpha, full_set_size=N
     Wm, Cm = _factor_and_core(map_state, Z, model_type, alpha, full_set_size)
     d = Wm.shape[0]
     means, covs = [], []
+    ia = (1.0 / alpha.vector(Wm.device, torch.float64)).float() if is_grouped(alpha) else None     # Wm is Wm A^-1 then
     for s0 in range(0, Xnew.shape[0], batch):
         Xb = Xnew[s0:s0 + batch]
         eng = get_engine(map_state, Xb, model_type)
         K = eng.K
         E = torch.eye(K, device=eng.device, dtype=torch.float32)[:, None, :].expand(K, eng.n, K).contiguous()
         J = eng.vjp_rows(E, "raw").permute(1, 0, 2)                     # (B, K, D)
-        JJ = torch.stack([_cross_gram64(J[i], J[i]) for i in range(J.shape[0])])
-        JW = _cross_gram64(J.reshape(-1, eng.D), Wm).reshape(eng.n, K, d)
-        cov = (JJ - JW @ Cm @ JW.transpose(-1, -2)) / alpha
+        if ia is None:
+            JJ = torch.stack([_cross_gram64(J[i], J[i]) for i in range(J.shape[0])])
+            JW = _cross_gram64(J.reshape(-1, eng.D), Wm).reshape(eng.n, K, d)
+            cov = (JJ - JW @ Cm @ JW.transpose(-1, -2)) / alpha
+        else:
+            # J S J^T = J A^-1 J^T - (J A^-1 Wm^T) C (.)^T: the rows scaled by 1 / a for the first product, the second
+            # against the scaled factor
+            Ja = J * ia
+            JJ = torch.stack([_cross_gram64(Ja[i], J[i]) for i in range(J.shape[0])])
+            JW = _cross_gram64(J.reshape(-1, eng.D), Wm).reshape(eng.n, K, d)
+            cov = JJ - JW @ Cm @ JW.transpose(-1, -2)
         means.append(eng.outputs().double())
         covs.append(0.5 * (cov + cov.transpose(-1, -2)))
     f_mean, f_cov = torch.cat(means), torch.cat(covs)
@@ -263,14 +291,19 @@ def predict_lla_variances(map_state, Xnew, Z, model_type, alpha, full_set_size=N
     batch's engine; the subtraction runs in float64.  Not a reference function."""
     Wm, Cm = _factor_and_core(map_state, Z, model_type, alpha, full_set_size)
     means, vars_ = [], []
+    ia = None
+    if is_grouped(alpha):
+        # var_k = ||J_k||^2 in the A^-1 metric - (J A^-1 Wm^T)_k C (.)^T: the weighted-norm sweep with w = 1 / a and the
+        # tangent-forward block of the factor scaled by 1 / a (what _factor_and_core returned, built once per call)
+        ia = (1.0 / alpha.vector(Wm.device, torch.float64)).float()
     for s0 in range(0, Xnew.shape[0], batch):
         eng = get_engine(map_state, Xnew[s0:s0 + batch], model_type)
         K = eng.K
         E = torch.eye(K, device=eng.device, dtype=torch.float32)[:, None, :].expand(K, eng.n, K).contiguous()
-        jj = eng.vjp_wnorm(E, None, "raw").T.double()                                   # (B, K)
+        jj = eng.vjp_wnorm(E, ia, "raw").T.double()                                     # (B, K)
         JW = eng.jvp(Wm, "raw").permute(1, 2, 0).double()                               # (B, K, d)
         quad = ((JW @ Cm) * JW).sum(-1)
-        vars_.append((jj - quad) / alpha)
+        vars_.append((jj - quad) / alpha if ia is None else jj - quad)
         means.append(eng.outputs().double())
     f_mean, f_var = torch.cat(means), torch.cat(vars_)
     return (f_mean.squeeze(-1), f_var.squeeze(-1)) if model_type == "regressor" else (f_mean, f_var)

@@ -32,6 +32,7 @@ import torch
 from . import krylov
 from .ggn import (FACTOR_BYTES_LIMIT, BlockOperator, build_WTW, compute_ggn_diag, compute_ggn_vp, compute_W_vps,
                   gram_from_factor, materialize_factor)
+from .prior import check_dim, is_grouped
 from .utils import flatten_nn_params
 
 REFERENCE_CLIP_MIN = 1.0
@@ -115,7 +116,7 @@ class _SamplerParts:
         self.Wm = self.Qm = None
         if self.d * eng.D * 4 <= FACTOR_BYTES_LIMIT:
             c = math.sqrt(1.0) * (math.exp(-0.5 * float(state.params["logvar"]["logvar"])) if model_type == "regressor" else 1.0)
-            self.Wm = materialize_factor(eng, c)
+            self.Wm = self._whiten(materialize_factor(eng, c))
             G64 = gram_from_factor(self.Wm)
             G64 = torch.triu(G64) + torch.triu(G64, 1).T                                                 # :227
         else:
@@ -158,6 +159,10 @@ class _SamplerParts:
                 self.Qm = orthonormal_factor(self.Wm, evp, Ug, kept)
         else:
             raise ValueError("method must be 'lanczos' or 'eigh'")
+
+    def _whiten(self, Wm: torch.Tensor) -> torch.Tensor:
+        """hook of :class:`_GroupedSamplerParts`; the scalar prior uses the factor as it is"""
+        return Wm
 
     def f_small(self, U: torch.Tensor) -> torch.Tensor:
         """f(alpha I + beta W^T W) applied to the rows of U (S, d) float64 — the reference's small-space Lanczos (:117-128)."""
@@ -214,6 +219,43 @@ class _SamplerParts:
         return _nn_axpy(T, B, V, 1.0 / math.sqrt(self.alpha), out=V)
 
 
+class _GroupedSamplerParts(_SamplerParts):
+    """The parts for a :class:`prior.GroupedPrior`, A = diag(a) + beta W W^T, by whitening: in the coordinates
+    A_0^(1/2) theta (A_0 = diag(a)) the prior is the identity, so everything is built as for ``alpha = 1`` on the factor
+    Wt = W^T A_0^(-1/2) (columns scaled by a^(-1/2), once) — Gram, eigenpairs, ``Qm``, stiff-direction split — and
+
+        x = A_0^(-1/2) (I + beta Wt^T Wt)^(-1/2) eps,    cov(x) = A_0^(-1/2) (I + beta Wt^T Wt)^-1 A_0^(-1/2) = A^-1 .
+
+    ``method="eigh"`` on a materialised factor only: the small-space Lanczos, the eigenvalue clip and the matrix-free
+    fallback are tied to the scalar formula and refuse a grouped prior."""
+
+    def __init__(self, state, Z, D, prior, model_type, full_set_size, clip_min, method):
+        if method != "eigh":
+            raise ValueError(f"a GroupedPrior is sampled with method='eigh' only (got method={method!r}; "
+                             "reference_compat=True selects the small-space Lanczos)")
+        if clip_min is not None:
+            raise ValueError("clip_min (the reference's eigenvalue clip) is defined for a scalar alpha only, not for a "
+                             "GroupedPrior")
+        from .ggn import get_engine
+        eng = get_engine(state, Z, model_type)
+        if eng.n * eng.K * eng.D * 4 > FACTOR_BYTES_LIMIT:
+            raise ValueError("a GroupedPrior needs the materialised factor (d * D * 4 bytes <= FACTOR_BYTES_LIMIT): the "
+                             "matrix-free fallback takes a scalar alpha only")
+        self.prior = check_dim(prior, eng.D)
+        self.isq = prior.vector(eng.device, torch.float64).rsqrt().float()                # a^(-1/2), (D,)
+        super().__init__(state, Z, D, 1.0, model_type, full_set_size, None, "eigh")
+
+    def _whiten(self, Wm):
+        # on a copy: the materialised factor is left as it came (the unscaled block is released when this returns)
+        return Wm * self.isq
+
+    def apply(self, V):
+        return super().apply(V).mul_(self.isq)               # the base class returns a fresh block
+
+    def apply_(self, V):
+        return super().apply_(V).mul_(self.isq)
+
+
 def _nn_axpy(T, B, V, beta, out=None):
     """beta V + T B, the second pass of a block of draws.  Measured on MI355X at (256 x 450)(450 x 1.08 M)
     (``scripts/sampler_gemm_bench.py``, round 3): the build's own NN kernel ``lip_gemm_nn_axpy`` 2.91 ms out of place and
@@ -246,10 +288,12 @@ def _cached_parts(state, Z, D, alpha, model_type, full_set_size, clip_min, metho
     if _drop_parts_of not in _g._EVICTION_HOOKS:
         _g._EVICTION_HOOKS.append(_drop_parts_of)
     eng = _g.get_engine(state, Z, model_type)
-    key = (eng.cache_key, float(alpha), full_set_size, clip_min, method)
+    grouped = is_grouped(alpha)
+    key = (eng.cache_key, alpha.key() if grouped else float(alpha), full_set_size, clip_min, method)
     parts = _PARTS_CACHE.pop(key, None)
     if parts is None or parts.eng is not eng:
-        parts = _SamplerParts(state, Z, D, alpha, model_type, full_set_size, clip_min, method)
+        parts = (_GroupedSamplerParts if grouped else _SamplerParts)(state, Z, D, alpha, model_type, full_set_size, clip_min,
+                                                                    method)
         while len(_PARTS_CACHE) >= _PARTS_CACHE_MAX:
             _PARTS_CACHE.pop(next(iter(_PARTS_CACHE)))
     _PARTS_CACHE[key] = parts
@@ -271,7 +315,8 @@ def inv_matsqrt_vp(state, Z, D, alpha, model_type, full_set_size=None, key=None,
     """``src/sample.py:55-145``.  Returns a block operator v -> A^(-1/2) v on (D,) or (S, D).
     (``key`` / ``num_proj_steps`` select the reference's alternating-projection branch, which it
     disables itself — ``:150`` forces ``key=None`` because the branch returns NaN)
-    ``reference_compat``: see :func:`_compat`."""
+    ``reference_compat``: see :func:`_compat`.  ``alpha`` may be a :class:`prior.GroupedPrior` (``method="eigh"``, a
+    factor that fits ``FACTOR_BYTES_LIMIT``, no clip: :class:`_GroupedSamplerParts`; anything else raises ``ValueError``)."""
     clip_min, method = _compat(reference_compat, clip_min, method)
     parts = _cached_parts(state, Z, D, alpha, model_type, full_set_size, clip_min, method)
     eng = parts.eng
@@ -306,12 +351,16 @@ def sample_diag(state, Z, D, alpha, key, model_type, num_samples=1, full_set_siz
     if diag.numel() != D:
         raise ValueError(f"D = {D} does not match the network's {diag.numel()} parameters")
     out = krylov.fill_normal(num_samples, D, _seed(key) * 1000003, diag.device)
+    if is_grouped(alpha):
+        return out.mul_(torch.rsqrt(diag + check_dim(alpha, D).vector(diag.device)))
     return out.mul_(torch.rsqrt(diag + float(alpha)))
 
 
 def range_deflation(state, Z, D, alpha, model_type, full_set_size=None) -> "krylov.RangeDeflation":
     """The invariant subspace range(W) of A = alpha I + beta W W^T as the D-space Krylov routes use it: the sampler's
     orthonormalised factor (rows q_k, A q_k = (alpha + beta lambda_k) q_k).  Needs the factor to fit in HBM."""
+    if is_grouped(alpha):
+        raise ValueError("range deflation takes a scalar alpha only: range(W) is not invariant under diag(a) + beta W W^T")
     parts = _cached_parts(state, Z, D, alpha, model_type, full_set_size, None, "eigh")
     if parts.Qm is None:
         raise ValueError("range deflation needs the materialised factor (d * D * 4 bytes <= FACTOR_BYTES_LIMIT)")
@@ -328,6 +377,8 @@ def sample_lanczos(state, Z, D, alpha, key, model_type, num_samples=1, full_set_
     ``deflate=True``: range(W) is taken out of the recurrence and handled exactly (``krylov.RangeDeflation``) — the
     float32 product's rounding noise lives in that subspace and is as large as alpha at the CIFAR config's alpha =
     0.005, which is what made the plain recurrence lose accuracy with MORE steps there."""
+    if is_grouped(alpha):
+        raise ValueError("sample_lanczos takes a scalar alpha only (a GroupedPrior is sampled by sample(method='eigh'))")
     vp = compute_ggn_vp(state, Z, model_type, full_set_size=full_set_size)
     eng = vp.engine
     M = Z.shape[0]

@@ -8,6 +8,11 @@
 W^T W does not depend on alpha, so after ONE Gram (d engine rows + a float64 GEMM) and ONE eigendecomposition the
 value and the exact gradient w.r.t. log alpha are O(d) scalar formulas — the reference rebuilds the Gram with
 d x (M VJP + M JVP) network passes inside every ``jax.grad`` call (``:32,56``).
+
+Layer-wise precisions (``*_layerwise``, not reference functions): with A = diag(a), a_j = alpha_{g(j)},
+det(A + r W W^T) = prod_g alpha_g^{D_g} det(I_d + r sum_g G_g / alpha_g) with the per-group Grams G_g of
+``ggn.grouped_grams`` — again independent of the precisions, so ONE pass over the materialised factor is followed by
+d x d float64 algebra per evaluation (a Cholesky factorisation) for the value and the exact gradient in all log alpha_g.
 """
 from __future__ import annotations
 
@@ -17,7 +22,8 @@ from typing import Optional, Tuple
 
 import torch
 
-from .ggn import build_WTW, compute_W_vps
+from .ggn import build_WTW, compute_W_vps, get_engine, grouped_grams, materialize_factor
+from .prior import GroupedPrior
 from .utils import count_model_params, flatten_nn_params
 
 
@@ -99,3 +105,80 @@ def fit_alpha(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alp
         upd, st = opt.update(-g, st)
         la += upd
     return math.exp(la), history
+
+
+# ---- layer-wise precisions ------------------------------------------------------------------------------------------
+def grouped_spectrum(X, state, model_type, prior: GroupedPrior):
+    """``(grams (G, d, d) float64, sizes (G,), theta_sqnorms (G,) float64)`` of the factor built at N/M = 1 like
+    :func:`_spectrum`: what the layer-wise evidence needs of the network, for the group table of ``prior`` (its values
+    are not used)."""
+    eng = get_engine(state, X, model_type)
+    if prior.D != eng.D:
+        raise ValueError(f"the prior covers {prior.D} parameters, the network has {eng.D}")
+    c = math.exp(-0.5 * float(state.params["logvar"]["logvar"])) if model_type == "regressor" else 1.0
+    grams = grouped_grams(materialize_factor(eng, c), prior)
+    flat_p, _ = flatten_nn_params(state.params)
+    return grams, prior.sizes, prior.group_sqnorms(flat_p).to(grams.device)
+
+
+def lml_layerwise(log_alphas, grams: torch.Tensor, theta_sqnorms: torch.Tensor, rescale: float):
+    """``(value, grad)``: value = -1/2 sum_g alpha_g ||theta_g||^2 - 1/2 logdet(I_d + rescale sum_g G_g / alpha_g) (the
+    convention of :func:`_lml_from_spectrum`, in which the D_g log alpha_g terms cancel) and its gradient (G,) float64
+    in log alpha_g:  -1/2 alpha_g ||theta_g||^2 + 1/2 (rescale / alpha_g) tr((I + rescale Gt)^-1 G_g).
+    Float64 torch on the device of ``grams`` (CPU included); one Cholesky factorisation of the d x d matrix."""
+    grams = grams.double()
+    la = torch.as_tensor(log_alphas, dtype=torch.float64, device=grams.device).reshape(-1)
+    t2 = torch.as_tensor(theta_sqnorms, dtype=torch.float64, device=grams.device).reshape(-1)
+    alphas = torch.exp(la)
+    d = grams.shape[-1]
+    Mx = torch.eye(d, dtype=torch.float64, device=grams.device) + rescale * (grams / alphas[:, None, None]).sum(0)
+    L = torch.linalg.cholesky(0.5 * (Mx + Mx.T))
+    logdet = 2.0 * torch.log(torch.diagonal(L)).sum()
+    value = -0.5 * (alphas * t2).sum() - 0.5 * logdet
+    Minv = torch.cholesky_inverse(L)
+    traces = (Minv[None] * grams).sum((1, 2))                              # tr(M^-1 G_g): both symmetric
+    grad = -0.5 * alphas * t2 + 0.5 * (rescale / alphas) * traces
+    return float(value), grad
+
+
+def log_marginal_likelihood_layerwise(prior: GroupedPrior, X, state, model_type: str, full_set_size: Optional[int] = None) -> float:
+    """log p(D | alpha_1 .. alpha_G) up to precision-independent constants, at the precisions of ``prior``"""
+    N = full_set_size or X.shape[0]
+    grams, _, t2 = grouped_spectrum(X, state, model_type, prior)
+    return lml_layerwise(torch.log(prior.values), grams, t2, N / X.shape[0])[0]
+
+
+def _adam_update(opt: Adam, grad: torch.Tensor, opt_state):
+    """:meth:`Adam.update` applied per component of a float64 vector (the scalar class is left alone)"""
+    c = opt_state["count"] + 1
+    mu = opt.b1 * opt_state["mu"] + (1 - opt.b1) * grad
+    nu = opt.b2 * opt_state["nu"] + (1 - opt.b2) * grad * grad
+    mu_hat, nu_hat = mu / (1 - opt.b1 ** c), nu / (1 - opt.b2 ** c)
+    return -opt.lr * mu_hat / (torch.sqrt(nu_hat) + opt.eps), dict(count=c, mu=mu, nu=nu)
+
+
+def fit_log_alphas(grams, theta_sqnorms, rescale: float, log_alphas0, alpha_lr: float = 5e-2, steps: int = 200):
+    """The hyper-steps of :func:`fit_alpha` on all log alpha_g at once, from the Grams: ``(log_alphas, history)`` with
+    history = [(alphas (G,) float64 on the CPU, value)] before each step.  With G = 1 it walks :func:`fit_alpha`'s
+    trajectory."""
+    la = torch.as_tensor(log_alphas0, dtype=torch.float64, device=grams.device).reshape(-1).clone()
+    opt = Adam(alpha_lr)
+    st = dict(count=0, mu=torch.zeros_like(la), nu=torch.zeros_like(la))
+    history = []
+    for _ in range(steps):
+        v, g = lml_layerwise(la, grams, theta_sqnorms, rescale)
+        history.append((torch.exp(la).cpu(), v))
+        upd, st = _adam_update(opt, -g, st)
+        la = la + upd
+    return la, history
+
+
+def fit_alpha_layerwise(X, state, model_type, full_set_size=None, groups="layer", alpha0: float = 1.0,
+                        alpha_lr: float = 5e-2, steps: int = 200):
+    """:func:`fit_alpha` with one precision per group (``groups`` as in :class:`prior.GroupedPrior`) for a fixed theta:
+    ``(GroupedPrior, history)``.  The per-group Grams are built once; every step is d x d algebra."""
+    N = full_set_size or X.shape[0]
+    prior = GroupedPrior(state.params, alpha0, groups)
+    grams, _, t2 = grouped_spectrum(X, state, model_type, prior)
+    la, history = fit_log_alphas(grams, t2, N / X.shape[0], torch.log(prior.values), alpha_lr, steps)
+    return prior.with_values(torch.exp(la).cpu()), history
