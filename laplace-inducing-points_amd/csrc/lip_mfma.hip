@@ -1619,54 +1619,57 @@ static hipError_t run_igemm_first(const IgemmP& p, int P, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------
-// weight gradient
+// weight gradient: the generic kernels (wgrad_kernel, wgrad_sqsum_kernel, wgrad_wnorm_kernel) share one im2col
+// gather and one K loop, WgradTap + wgrad_accumulate_rows; each keeps its own row ranges and epilogue.
 // ------------------------------------------------------------------------------------------
+// This thread's column m of the im2col matrix (fixed across the K loop) as a kernel tap:
+// vector path (C % 4 == 0, float4 gathers) m = m0 + 4*(tid % (BM/4)); scalar m0 + tid % BM
+struct WgradTap {
+  bool vec, mvalid;
+  int kh, kw, ci;
+};
+
+template <int BM>
+__device__ __forceinline__ WgradTap wgrad_tap(const WgradP& prm, int m0, int tid) {
+  WgradTap t;
+  t.vec = (prm.C & 3) == 0;
+  const int my_m = t.vec ? (m0 + 4 * (tid % (BM / 4))) : (m0 + (tid % BM));
+  t.kh = t.kw = t.ci = 0;
+  t.mvalid = my_m < prm.M;
+  if (t.mvalid) {
+    const int tap = my_m / prm.C;
+    t.ci = my_m - tap * prm.C;
+    t.kh = tap / prm.KW;
+    t.kw = tap - t.kh * prm.KW;
+  }
+  return t;
+}
+
+typedef __attribute__((address_space(3))) float lds_float;
+typedef __attribute__((address_space(3))) f32x4v lds_f32x4v;
+
+// acc += im2col(a)[rows rbeg..rend)^T g[rows rbeg..rend), columns n0..n0+BN) of the cotangent block at gbase; the
+// caller zeroes acc.  Register-staged K tiles: gather tile k+1 while the MFMAs sweep tile k from LDS.
+// As_[BK * (BM + 4)] (16-byte aligned) and Bs_[BK * BN] are the calling kernel's __shared__ tiles.  They are addressed
+// through LDS-typed pointers: with generic ones this function is optimised before the kernel's arrays are known, the
+// k-step offsets of the sweep's LDS reads end up in registers instead of the instructions' offset fields, and the 8
+// extra VGPRs cost four of the eighteen instantiations a wave per SIMD.
 template <int WM, int WN, int TM, int TN>
-__global__ __launch_bounds__(WM * WN * 64) void wgrad_kernel(const WgradP prm) {
+__device__ __forceinline__ void wgrad_accumulate_rows(const WgradP& prm, const WgradTap& tap, const float* gbase, int rbeg,
+                                                      int rend, int n0, float* As_, float* Bs_, f32x16 (&acc)[TM][TN]) {
+  lds_float* As = (lds_float*)As_;
+  lds_float* Bs = (lds_float*)Bs_;
   using T = Tile<WM, WN, TM, TN>;
   constexpr int NT = T::NT, BM = T::BM, BN = T::BN, AE = T::AE, AQ = T::AQ, BE = T::BE;
   constexpr int LDA = BM + 4, LDB = BN;
   constexpr int QPR = BM / 4;              // float4 per LDS row
-  __shared__ __attribute__((aligned(16))) float As[BK * LDA];
-  __shared__ float Bs[BK * LDB];
-
+  static_assert(!T::BPART, "every thread loads and stores whole B elements");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int N = prm.N, M = prm.M;
-  const int tiles_n = (N + BN - 1) / BN;
-  const int tile_n = blockIdx.x % tiles_n, tile_m = blockIdx.x / tiles_n;
-  const int p = blockIdx.y;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-  int rows_per = (prm.R + prm.ksplit - 1) / prm.ksplit;
-  rows_per = (rows_per + BK - 1) / BK * BK;
-  if (prm.seg_rows) rows_per = prm.seg_rows;           // per-example rows: block z reduces example z only
-  const int rbeg = blockIdx.z * rows_per;
-  const int rend = min(prm.R, rbeg + rows_per);
-  if (rbeg >= rend) return;
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
-
-  const bool vec = (prm.C & 3) == 0;
-  // this thread's m (fixed across the K loop): vector path m = m0 + 4*(tid % QPR); scalar m0 + tid % BM
-  const int my_m = vec ? (m0 + 4 * (tid % QPR)) : (m0 + (tid % BM));
-  int kh = 0, kw = 0, ci = 0;
-  const bool mvalid = my_m < M;
-  if (mvalid) {
-    const int tap = my_m / prm.C;
-    ci = my_m - tap * prm.C;
-    kh = tap / prm.KW;
-    kw = tap - kh * prm.KW;
-  }
-
+  const int N = prm.N;
+  const bool vec = tap.vec, mvalid = tap.mvalid;
+  const int kh = tap.kh, kw = tap.kw, ci = tap.ci;
   float areg[AE], breg[BE];
-  const float* gbase = prm.g + (long long)p * prm.g_ps;
 
   auto load_tile = [&](int rk0) {
     if (vec) {
@@ -1715,8 +1718,7 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_kernel(const WgradP prm) {
       for (int j = 0; j < AQ; ++j) {
         const int q = tid + j * NT;
         const int k = q / QPR, mq = q - k * QPR;
-        *reinterpret_cast<float4*>(&As[k * LDA + 4 * mq]) =
-            make_float4(areg[4 * j + 0], areg[4 * j + 1], areg[4 * j + 2], areg[4 * j + 3]);
+        *(lds_f32x4v*)&As[k * LDA + 4 * mq] = f32x4v{areg[4 * j + 0], areg[4 * j + 1], areg[4 * j + 2], areg[4 * j + 3]};
       }
     } else {
 #pragma unroll
@@ -1737,15 +1739,51 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_kernel(const WgradP prm) {
   int rk = rbeg;
   load_tile(rk);
   while (true) {
-    __syncthreads();
+    __syncthreads();                    // (a caller that loops: also orders its last LDS reads before these stores)
     store_tile();
     __syncthreads();
     rk += BK;
     const bool more = rk < rend;
     if (more) load_tile(rk);
-    mfma_sweep<WM, WN, TM, TN, LDA, LDB>(As, Bs, acc, wm, wn, lane);
+    mfma_sweep<WM, WN, TM, TN, LDA, LDB>((const float*)As, (const float*)Bs, acc, wm, wn, lane);
     if (!more) break;
   }
+}
+
+// per-probe weight cotangent: block (tile, p, z) reduces rows [z * rows_per, ...) of probe p (split-K, or one example
+// per z when seg_rows is set) and adds s * acc into y
+template <int WM, int WN, int TM, int TN>
+__global__ __launch_bounds__(WM * WN * 64) void wgrad_kernel(const WgradP prm) {
+  using T = Tile<WM, WN, TM, TN>;
+  constexpr int BM = T::BM, BN = T::BN;
+  __shared__ __attribute__((aligned(16))) float As[BK * (BM + 4)];
+  __shared__ float Bs[BK * BN];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const int N = prm.N, M = prm.M;
+  const int tiles_n = (N + BN - 1) / BN;
+  const int tile_n = blockIdx.x % tiles_n, tile_m = blockIdx.x / tiles_n;
+  const int p = blockIdx.y;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+
+  int rows_per = (prm.R + prm.ksplit - 1) / prm.ksplit;
+  rows_per = (rows_per + BK - 1) / BK * BK;
+  if (prm.seg_rows) rows_per = prm.seg_rows;           // per-example rows: block z reduces example z only
+  const int rbeg = blockIdx.z * rows_per;
+  const int rend = min(prm.R, rbeg + rows_per);
+  if (rbeg >= rend) return;
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+
+  const WgradTap tap = wgrad_tap<BM>(prm, m0, tid);
+  wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, rbeg, rend, n0, As, Bs, acc);
 
   const int l31 = lane & 31, lh = lane >> 5;
   float* ybase = prm.y + (long long)p * prm.y_ps + (prm.seg_rows ? (long long)blockIdx.z * prm.seg_ys : 0);
@@ -3292,8 +3330,27 @@ static int auto_ksplit(long long blocks, int occ, int R, int tile_elems, int mfm
   return best;
 }
 
+// The tile of the generic weight-gradient kernels (wgrad, wgrad_sqsum, wgrad_wnorm) for an (M, N) weight matrix:
+// f(Tile<...>(), index of the tile in the order of WnormRoute's WN_WGRAD_2212 .. WN_WGRAD_4111).
+template <class F>
+static auto with_wgrad_tile(int M, int N, F&& f) {
+  static_assert(WN_WGRAD_2212 == 0 && WN_WGRAD_2222 == 1 && WN_WGRAD_2211 == 2 && WN_WGRAD_4112 == 3 &&
+                WN_WGRAD_2111 == 4 && WN_WGRAD_4111 == 5, "tile order");
+  const bool small_m = M <= 64;
+  if (N > 64) return small_m ? f(Tile<2, 2, 1, 2>(), 0) : f(Tile<2, 2, 2, 2>(), 1);
+  if (N > 32) return small_m ? f(Tile<2, 2, 1, 1>(), 2) : f(Tile<4, 1, 1, 2>(), 3);
+  return small_m ? f(Tile<2, 1, 1, 1>(), 4) : f(Tile<4, 1, 1, 1>(), 5);
+}
+
+static long long wgrad_tile_count(int M, int N) {
+  return with_wgrad_tile(M, N, [&](auto t, int) {
+    using T = decltype(t);
+    return (long long)((M + T::BM - 1) / T::BM) * ((N + T::BN - 1) / T::BN);
+  });
+}
+
 template <int WM, int WN, int TM, int TN>
-static hipError_t run_wgrad(const WgradP& p0, int P, hipStream_t st) {
+static hipError_t run_wgrad(Tile<WM, WN, TM, TN>, const WgradP& p0, int P, hipStream_t st) {
   using T = Tile<WM, WN, TM, TN>;
   const long long tiles = (long long)((p0.M + T::BM - 1) / T::BM) * ((p0.N + T::BN - 1) / T::BN);
   WgradP p = p0;
@@ -3393,36 +3450,34 @@ hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st) {
   // (64-row per-probe tiles for M = 288 were measured slower than 128-row ones: 54.6 vs 52.4 ms per step — removed;
   //  a 96 x 256 probe-batched tile <1,4,3,2> — the transposed im2col gather shared by eight probes instead of four — ran
   //  the M = 288 / 576 launches at 105 instead of 113 TFLOP/s: removed)
-  const bool small_m = p.M <= 64;
-  if (p.N > 64) return small_m ? run_wgrad<2, 2, 1, 2>(p, P, st) : run_wgrad<2, 2, 2, 2>(p, P, st);
-  if (p.N > 32) return small_m ? run_wgrad<2, 2, 1, 1>(p, P, st) : run_wgrad<4, 1, 1, 2>(p, P, st);
-  return small_m ? run_wgrad<2, 1, 1, 1>(p, P, st) : run_wgrad<4, 1, 1, 1>(p, P, st);
+  return with_wgrad_tile(p.M, p.N, [&](auto tile, int) { return run_wgrad(tile, p, P, st); });
 }
 
 
 // ------------------------------------------------------------------------------------------
 // square-accumulating per-example weight gradient (lip_vjp_sqsum):
 //   y[m][c] += sum_{(p, i) in the block's group} ( s[c] * sum_{pix of example i} im2col(a_i)[pix][m] g_pi[pix][c] )^2
-// Operands and row geometry of the per-example (seg_rows) path of wgrad_kernel: the K loop of a pair covers the
-// OH*OW rows of example i only.  After each pair the M x N tile is scaled, squared in registers and added to a
+// Per (probe p, example i) pair, wgrad_accumulate_rows over the OH*OW rows of example i (the row range of
+// wgrad_kernel's seg_rows path).  After each pair the M x N tile is scaled, squared in registers and added to a
 // second register set; the MFMA accumulators are then cleared for the next pair.  grid = (output tiles, groups):
 // block (t, g) takes pairs [g*per, (g+1)*per) in order and stores one partial per group (plain stores, no atomics);
 // sqsum_finish adds the partials in group order, so the result is bitwise reproducible.  f32 MFMA in every
 // precision mode.
 // ------------------------------------------------------------------------------------------
-struct SqGroupP {
-  float* partial;                       // [groups][M*N], or null: one group, add into y
+struct PairGroupP {                     // pair q = p * n_img + i; block group g takes pairs [g*per, min(pairs, (g+1)*per))
   int pairs, per, n_img;
+};
+
+struct SqGroupP : PairGroupP {
+  float* partial;                       // [groups][M*N], or null: one group, add into y
 };
 
 template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(WM * WN * 64) void wgrad_sqsum_kernel(const WgradP prm, const SqGroupP sq) {
   using T = Tile<WM, WN, TM, TN>;
-  constexpr int NT = T::NT, BM = T::BM, BN = T::BN, AE = T::AE, AQ = T::AQ, BE = T::BE;
-  constexpr int LDA = BM + 4, LDB = BN;
-  constexpr int QPR = BM / 4;
-  __shared__ __attribute__((aligned(16))) float As[BK * LDA];
-  __shared__ float Bs[BK * LDB];
+  constexpr int BM = T::BM, BN = T::BN;
+  __shared__ __attribute__((aligned(16))) float As[BK * (BM + 4)];
+  __shared__ float Bs[BK * BN];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -3448,111 +3503,18 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_sqsum_kernel(const WgradP 
     scv[tn] = (prm.scale && col < N) ? prm.scale[col] : 1.f;
   }
 
-  const bool vec = (prm.C & 3) == 0;
-  const int my_m = vec ? (m0 + 4 * (tid % QPR)) : (m0 + (tid % BM));
-  int kh = 0, kw = 0, ci = 0;
-  const bool mvalid = my_m < M;
-  if (mvalid) {
-    const int tap = my_m / prm.C;
-    ci = my_m - tap * prm.C;
-    kh = tap / prm.KW;
-    kw = tap - kh * prm.KW;
-  }
-
-  float areg[AE], breg[BE];
-  const float* gbase = prm.g;
-  int rend = 0;
-
-  auto load_tile = [&](int rk0) {
-    if (vec) {
-#pragma unroll
-      for (int j = 0; j < AQ; ++j) {
-        const int k = (tid + j * NT) / QPR;
-        const int r = rk0 + k;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (mvalid && r < rend) {
-          const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
-          const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
-          const int ih = oh * prm.stride + kh - prm.pad_h, iw = ow * prm.stride + kw - prm.pad_w;
-          if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW)
-            v = *reinterpret_cast<const float4*>(prm.a + (unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + ci));
-        }
-        areg[4 * j + 0] = v.x; areg[4 * j + 1] = v.y; areg[4 * j + 2] = v.z; areg[4 * j + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < AE; ++j) {
-        const int k = (tid + j * NT) / BM;
-        const int r = rk0 + k;
-        float v = 0.f;
-        if (mvalid && r < rend) {
-          const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
-          const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
-          const int ih = oh * prm.stride + kh - prm.pad_h, iw = ow * prm.stride + kw - prm.pad_w;
-          if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW)
-            v = prm.a[(unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + ci)];
-        }
-        areg[j] = v;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < BE; ++j) {
-      const int e = tid + j * NT;
-      const int k = e / BN, nn = e - k * BN;
-      const int r = rk0 + k, col = n0 + nn;
-      breg[j] = (e < BN * BK && r < rend && col < N) ? gbase[(unsigned)(r * N + col)] : 0.f;
-    }
-  };
-
-  auto store_tile = [&]() {
-    if (vec) {
-#pragma unroll
-      for (int j = 0; j < AQ; ++j) {
-        const int q = tid + j * NT;
-        const int k = q / QPR, mq = q - k * QPR;
-        *reinterpret_cast<float4*>(&As[k * LDA + 4 * mq]) =
-            make_float4(areg[4 * j + 0], areg[4 * j + 1], areg[4 * j + 2], areg[4 * j + 3]);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < AE; ++j) {
-        const int e = tid + j * NT;
-        const int k = e / BM, mm = e - k * BM;
-        As[k * LDA + mm] = areg[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < BE; ++j) {
-      const int e = tid + j * NT;
-      if (e >= BN * BK) continue;
-      const int k = e / BN, nn = e - k * BN;
-      Bs[k * LDB + nn] = breg[j];
-    }
-  };
-
+  const WgradTap tap = wgrad_tap<BM>(prm, m0, tid);
   for (int q = q0; q < q1; ++q) {
     const int p = q / sq.n_img, i = q - p * sq.n_img;
-    const int rbeg = i * prm.OHW;
-    rend = rbeg + prm.OHW;
-    gbase = prm.g + (long long)p * prm.g_ps;
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
-    int rk = rbeg;
-    load_tile(rk);
-    while (true) {
-      __syncthreads();                  // (also orders the previous pair's last sweep before these LDS stores)
-      store_tile();
-      __syncthreads();
-      rk += BK;
-      const bool more = rk < rend;
-      if (more) load_tile(rk);
-      mfma_sweep<WM, WN, TM, TN, LDA, LDB>(As, Bs, acc, wm, wn, lane);
-      if (!more) break;
-    }
+    // its leading barrier also orders the previous pair's last sweep before these LDS stores
+    wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, i * prm.OHW, (i + 1) * prm.OHW, n0,
+                                          As, Bs, acc);
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -3636,13 +3598,6 @@ __global__ __launch_bounds__(256) void wgrad_sqsum_dense_kernel(const WgradP prm
   }
 }
 
-static void sq_tile(int M, int N, int& BM, int& BN) {
-  const bool small_m = M <= 64;
-  if (N > 64) { BM = small_m ? 64 : 128; BN = 128; }
-  else if (N > 32) { BM = small_m ? 64 : 128; BN = 64; }
-  else { BM = small_m ? 64 : 128; BN = 32; }
-}
-
 // groups of (probe, example) pairs for a launch of `blocks_per_group` blocks per group: fill SQ_TARGET_BLOCKS.
 // Returns the group bound min(pairs, ceil(SQ_TARGET_BLOCKS / blocks)) — monotone in `pairs`, so the scratch sized for
 // the largest pass serves every smaller one — and the launch's G <= bound after rounding to whole groups.
@@ -3657,14 +3612,14 @@ static long long sq_groups(long long blocks_per_group, long long pairs, int& G, 
 
 long long wgrad_sqsum_scratch(int M, int N, int OHW, long long pairs) {
   if (OHW == 1 || M <= 0 || N <= 0 || pairs <= 0) return 0;
-  int BM, BN, G, per;
-  sq_tile(M, N, BM, BN);
-  const long long bound = sq_groups((long long)((M + BM - 1) / BM) * ((N + BN - 1) / BN), pairs, G, per);
+  int G, per;
+  const long long bound = sq_groups(wgrad_tile_count(M, N), pairs, G, per);
   return bound > 1 ? bound * M * N : 0;
 }
 
 template <int WM, int WN, int TM, int TN>
-static hipError_t run_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch, long long scratch_floats, hipStream_t st) {
+static hipError_t run_wgrad_sqsum(Tile<WM, WN, TM, TN>, const WgradP& p, int P, int n_img, float* scratch,
+                                  long long scratch_floats, hipStream_t st) {
   using T = Tile<WM, WN, TM, TN>;
   const long long tiles = (long long)((p.M + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN);
   const long long pairs = (long long)P * n_img;
@@ -3692,38 +3647,30 @@ hipError_t launch_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch,
     return hipGetLastError();
   }
   // ((C & 3) == 0 reads the activations as float4: the engine checked their 16-byte alignment)
-  const bool small_m = p.M <= 64;
-  if (p.N > 64) return small_m ? run_wgrad_sqsum<2, 2, 1, 2>(p, P, n_img, scratch, scratch_floats, st)
-                               : run_wgrad_sqsum<2, 2, 2, 2>(p, P, n_img, scratch, scratch_floats, st);
-  if (p.N > 32) return small_m ? run_wgrad_sqsum<2, 2, 1, 1>(p, P, n_img, scratch, scratch_floats, st)
-                               : run_wgrad_sqsum<4, 1, 1, 2>(p, P, n_img, scratch, scratch_floats, st);
-  return small_m ? run_wgrad_sqsum<2, 1, 1, 1>(p, P, n_img, scratch, scratch_floats, st)
-                 : run_wgrad_sqsum<4, 1, 1, 1>(p, P, n_img, scratch, scratch_floats, st);
+  return with_wgrad_tile(p.M, p.N,
+                         [&](auto tile, int) { return run_wgrad_sqsum(tile, p, P, n_img, scratch, scratch_floats, st); });
 }
 
 // ------------------------------------------------------------------------------------------
 // weighted square norm of the per-example weight gradient (lip_vjp_wnorm):
 //   out[(p, i)] += sum_{m, c} w[m][c] ( s[c] * sum_{pix of example i} im2col(a_i)[pix][m] g_pi[pix][c] )^2
-// The per-(probe, example) MFMA tile of wgrad_sqsum_kernel (same operands, row geometry and K loop); the other
+// The per-(probe, example) MFMA tile of wgrad_sqsum_kernel (the same wgrad_accumulate_rows call); the other
 // reduction of its squares: the block's w tile is loaded once into registers, after each pair the tile is scaled,
 // squared, multiplied by w and summed over the tile (lanes by shuffles, waves in wave order through LDS) to ONE float,
 // stored to partial[tile][pair] (plain store).  wnorm_finish adds the tiles of a pair in tile order.  No atomics.
 // grid = (output tiles, groups of pairs); w == null: weight 1.
 // ------------------------------------------------------------------------------------------
-struct WnGroupP {
+struct WnGroupP : PairGroupP {
   const float* w;                       // the op's (M, N) slice of the weight vector, or null (all ones)
   float* partial;                       // [tiles][pairs]
-  int pairs, per, n_img;
 };
 
 template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(WM * WN * 64) void wgrad_wnorm_kernel(const WgradP prm, const WnGroupP wn_) {
   using T = Tile<WM, WN, TM, TN>;
-  constexpr int NT = T::NT, BM = T::BM, BN = T::BN, AE = T::AE, AQ = T::AQ, BE = T::BE;
-  constexpr int LDA = BM + 4, LDB = BN;
-  constexpr int QPR = BM / 4;
-  __shared__ __attribute__((aligned(16))) float As[BK * LDA];
-  __shared__ float Bs[BK * LDB];
+  constexpr int BM = T::BM, BN = T::BN;
+  __shared__ __attribute__((aligned(16))) float As[BK * (BM + 4)];
+  __shared__ float Bs[BK * BN];
   __shared__ float wsum[WM * WN];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -3754,112 +3701,19 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_wnorm_kernel(const WgradP 
     }
   }
 
-  const bool vec = (prm.C & 3) == 0;
-  const int my_m = vec ? (m0 + 4 * (tid % QPR)) : (m0 + (tid % BM));
-  int kh = 0, kw = 0, ci = 0;
-  const bool mvalid = my_m < M;
-  if (mvalid) {
-    const int tap = my_m / prm.C;
-    ci = my_m - tap * prm.C;
-    kh = tap / prm.KW;
-    kw = tap - kh * prm.KW;
-  }
-
-  float areg[AE], breg[BE];
-  const float* gbase = prm.g;
-  int rend = 0;
-
-  auto load_tile = [&](int rk0) {
-    if (vec) {
-#pragma unroll
-      for (int j = 0; j < AQ; ++j) {
-        const int k = (tid + j * NT) / QPR;
-        const int r = rk0 + k;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (mvalid && r < rend) {
-          const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
-          const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
-          const int ih = oh * prm.stride + kh - prm.pad_h, iw = ow * prm.stride + kw - prm.pad_w;
-          if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW)
-            v = *reinterpret_cast<const float4*>(prm.a + (unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + ci));
-        }
-        areg[4 * j + 0] = v.x; areg[4 * j + 1] = v.y; areg[4 * j + 2] = v.z; areg[4 * j + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < AE; ++j) {
-        const int k = (tid + j * NT) / BM;
-        const int r = rk0 + k;
-        float v = 0.f;
-        if (mvalid && r < rend) {
-          const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
-          const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
-          const int ih = oh * prm.stride + kh - prm.pad_h, iw = ow * prm.stride + kw - prm.pad_w;
-          if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW)
-            v = prm.a[(unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + ci)];
-        }
-        areg[j] = v;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < BE; ++j) {
-      const int e = tid + j * NT;
-      const int k = e / BN, nn = e - k * BN;
-      const int r = rk0 + k, col = n0 + nn;
-      breg[j] = (e < BN * BK && r < rend && col < N) ? gbase[(unsigned)(r * N + col)] : 0.f;
-    }
-  };
-
-  auto store_tile = [&]() {
-    if (vec) {
-#pragma unroll
-      for (int j = 0; j < AQ; ++j) {
-        const int q = tid + j * NT;
-        const int k = q / QPR, mq = q - k * QPR;
-        *reinterpret_cast<float4*>(&As[k * LDA + 4 * mq]) =
-            make_float4(areg[4 * j + 0], areg[4 * j + 1], areg[4 * j + 2], areg[4 * j + 3]);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < AE; ++j) {
-        const int e = tid + j * NT;
-        const int k = e / BM, mm = e - k * BM;
-        As[k * LDA + mm] = areg[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < BE; ++j) {
-      const int e = tid + j * NT;
-      if (e >= BN * BK) continue;
-      const int k = e / BN, nn = e - k * BN;
-      Bs[k * LDB + nn] = breg[j];
-    }
-  };
-
+  const WgradTap tap = wgrad_tap<BM>(prm, m0, tid);
   float* part = wn_.partial + (long long)blockIdx.x * wn_.pairs;
   for (int q = q0; q < q1; ++q) {
     const int p = q / wn_.n_img, i = q - p * wn_.n_img;
-    const int rbeg = i * prm.OHW;
-    rend = rbeg + prm.OHW;
-    gbase = prm.g + (long long)p * prm.g_ps;
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
-    int rk = rbeg;
-    load_tile(rk);
-    while (true) {
-      __syncthreads();                  // (also orders the previous pair's last sweep and wave sums before these LDS stores)
-      store_tile();
-      __syncthreads();
-      rk += BK;
-      const bool more = rk < rend;
-      if (more) load_tile(rk);
-      mfma_sweep<WM, WN, TM, TN, LDA, LDB>(As, Bs, acc, wm, wn, lane);
-      if (!more) break;
-    }
+    // its leading barrier also orders the previous pair's last sweep and wave sums before these LDS stores
+    wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, i * prm.OHW, (i + 1) * prm.OHW, n0,
+                                          As, Bs, acc);
     float s = 0.f;
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
@@ -3928,18 +3782,16 @@ __global__ __launch_bounds__(256) void wgrad_wnorm_dense_kernel(const WgradP prm
 long long wgrad_wnorm_tiles(int M, int N, int OHW) {
   if (M <= 0 || N <= 0) return 0;
   if (OHW == 1) return (N + 63) / 64;
-  int BM, BN;
-  sq_tile(M, N, BM, BN);
-  return (long long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+  return wgrad_tile_count(M, N);
 }
 
 template <int WM, int WN, int TM, int TN>
-static hipError_t run_wgrad_wnorm(const WgradP& p, int P, int n_img, const float* w, float* out, float* scratch,
-                                  long long scratch_floats, int route, hipStream_t st) {
+static hipError_t run_wgrad_wnorm(Tile<WM, WN, TM, TN>, int route, const WgradP& p, int P, int n_img, const float* w, float* out,
+                                  float* scratch, long long scratch_floats, hipStream_t st) {
   using T = Tile<WM, WN, TM, TN>;
   const long long tiles = (long long)((p.M + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN);
   const long long pairs = (long long)P * n_img;
-  if (tiles != wgrad_wnorm_tiles(p.M, p.N, p.OHW) || tiles * pairs > scratch_floats) return hipErrorInvalidValue;
+  if (tiles * pairs > scratch_floats) return hipErrorInvalidValue;
   int G, per;
   sq_groups(tiles, pairs, G, per);
   WnGroupP wn;
@@ -3963,14 +3815,9 @@ hipError_t launch_wgrad_wnorm(const WgradP& p, int P, int n_img, const float* w,
     if (e != hipSuccess) return e;
     return launch_wnorm_finish(scratch, (int)tiles, pairs, out, st);
   }
-  // the tile shapes of launch_wgrad_sqsum (sq_tile)
-  const bool small_m = p.M <= 64;
-  if (p.N > 64) return small_m ? run_wgrad_wnorm<2, 2, 1, 2>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_2212, st)
-                               : run_wgrad_wnorm<2, 2, 2, 2>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_2222, st);
-  if (p.N > 32) return small_m ? run_wgrad_wnorm<2, 2, 1, 1>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_2211, st)
-                               : run_wgrad_wnorm<4, 1, 1, 2>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_4112, st);
-  return small_m ? run_wgrad_wnorm<2, 1, 1, 1>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_2111, st)
-                 : run_wgrad_wnorm<4, 1, 1, 1>(p, P, n_img, w, out, scratch, scratch_floats, WN_WGRAD_4111, st);
+  return with_wgrad_tile(p.M, p.N, [&](auto tile, int route) {
+    return run_wgrad_wnorm(tile, route, p, P, n_img, w, out, scratch, scratch_floats, st);
+  });
 }
 
 }  // namespace lip
