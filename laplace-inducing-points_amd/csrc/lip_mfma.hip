@@ -46,6 +46,59 @@ struct Tile {
   static constexpr bool BPART = (BN * BK) % NT != 0;
 };
 
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+}
+template <int NQ>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NQ]) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+}
+
+// Workgroups go round-robin over the 8 XCDs (each with its own L2).  xcd_contiguous maps linear block index x of `total`
+// blocks to the position that gives every XCD a CONTIGUOUS run of the first g8 = total & ~7 of them (the up to 7 blocks
+// past g8 keep their place), so blocks that share operand lines find them in one L2.
+template <class I>
+__device__ __forceinline__ I xcd_contiguous(I x, I total) {
+  const I g8 = total & ~(I)7;
+  return x < g8 ? (x & 7) * (g8 >> 3) + (x >> 3) : x;
+}
+
+// The (bid, byp) = (tile, probe) order of the conv GEMM grids (gx tiles x gy probes).  Measured on igemm_fast_kernel:
+// neighbouring row tiles both gather their halo rows; with the contiguous order on the 32-column tile (400 tiles per
+// probe) HBM reads went 6.62 -> 5.18 GB per launch, time -1 %.  Not for the parity-class grid of igemm_fast_kernel (its
+// order is by class: 4.72 -> 6.5 GB and +50 % time when remapped).
+//   gx >= 64, many row tiles per probe (large feature maps): an XCD keeps the SAME tile range for every probe, so the
+//     primal operands of those rows (activations, x-hat, act') stay in its L2 across the probes;
+//   gx < 64, few row tiles per probe (small feature maps, large per-probe weight slices): an XCD works through whole
+//     probes, so a probe's weight slice is fetched into one L2 only (128-column tile: 3.3 -> 2.4 GB per launch; on the
+//     32- and 64-column tiles this order was measured worse: 6.9 -> 8.4 and 3.7 -> 4.5 GB).
+// `dgx` divides by gx (FastDiv where the caller keeps the index arithmetic on the scalar unit).
+struct PlainDiv {
+  int d;
+  __device__ __forceinline__ int div(int x) const { return x / d; }
+};
+template <class Div>
+__device__ __forceinline__ void xcd_block_order(int& bid, int& byp, int gx, int gy, const Div& dgx) {
+  if (gx >= 64) {
+    bid = xcd_contiguous(bid, gx);
+  } else {
+    const int w = xcd_contiguous(bid + gx * byp, gx * gy);
+    byp = dgx.div(w); bid = w - byp * gx;
+  }
+}
+__device__ __forceinline__ void xcd_block_order(int& bid, int& byp) {
+  xcd_block_order(bid, byp, (int)gridDim.x, (int)gridDim.y, PlainDiv{(int)gridDim.x});
+}
+
 // One BK-deep MFMA sweep over the LDS tiles.
 template <int WM, int WN, int TM, int TN, int LDA, int LDB>
 __device__ __forceinline__ void mfma_sweep(const float* __restrict__ As, const float* __restrict__ Bs,
@@ -373,12 +426,7 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_kernel(const IgemmP prm) {
   for (int i = tid; i < 2 * BN; i += NT) redbuf[i] = 0.f;
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  zero_acc(acc);
 
   // rows owned by this thread in the vector A-load path: quad q = tid + j*NT -> (m = q>>2, kq = q&3)
   int vi[AQ], voh[AQ], vow[AQ];
@@ -543,6 +591,146 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_kernel(const IgemmP prm) {
 typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float float2u __attribute__((ext_vector_type(2), aligned(4)));
 
+// B operand of one K-tile (16 x BN of the [K][N] weights) over NT threads, BW floats per load instruction: load unit
+// e = tid + j NT -> (k = e / (BN / BW), column quad nq = e % (BN / BW)).  The element offsets are loop invariant; units
+// past column N read the zero page.
+template <int BN, int NT, int BW>
+struct BStage {
+  static constexpr int BE = BN * BK / NT, NB = BE / BW, UPR = BN / BW;      // UPR: load units per k-row
+  int tid;
+  unsigned bidx[NB];
+  bool bok[NB];
+  __device__ __forceinline__ BStage(int tid_, int n0, int N) : tid(tid_) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const int e = tid + j * NT;
+      const int k = e / UPR, nq = e - k * UPR;
+      bok[j] = (n0 + BW * nq) < N;
+      bidx[j] = (unsigned)(k * N + n0 + BW * nq);
+    }
+  }
+  __device__ __forceinline__ void load(const float* bbase, const float* zeros, float (&breg)[BE]) const {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const float* src = bok[j] ? (bbase + bidx[j]) : zeros;
+      if (BW == 4) {
+        const float4u v = *reinterpret_cast<const float4u*>(src);
+        breg[4 * j + 0] = v[0]; breg[4 * j + 1] = v[1]; breg[4 * j + 2] = v[2]; breg[4 * j + 3] = v[3];
+      } else if (BW == 2) {
+        const float2u v = *reinterpret_cast<const float2u*>(src);
+        breg[2 * j + 0] = v[0]; breg[2 * j + 1] = v[1];
+      } else {
+        breg[j] = *src;
+      }
+    }
+  }
+  // into the k-major LDS image Bs[k][BN]
+  __device__ __forceinline__ void store_kmajor(const float (&breg)[BE], float* Bsb) const {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const int e = tid + j * NT;
+      const int k = e / UPR, nq = e - k * UPR;
+      float* dst = &Bsb[k * BN + BW * nq];
+      if (BW == 4) *reinterpret_cast<float4*>(dst) = make_float4(breg[4 * j + 0], breg[4 * j + 1], breg[4 * j + 2], breg[4 * j + 3]);
+      else if (BW == 2) *reinterpret_cast<float2*>(dst) = make_float2(breg[2 * j + 0], breg[2 * j + 1]);
+      else *dst = breg[j];
+    }
+  }
+};
+
+// PAR: taps of a stride-2 transposed segment that can match a parity class: k = (parity + pad) & 1, step 2
+__device__ __forceinline__ int par_first_tap(const SegP& s, int par, int off) { return s.mask ? ((par + off) & 1) : 0; }
+
+// K-tile cursor of igemm_fast_kernel and igemm_adirect_kernel over the segments, kernel taps and 16-channel tiles of a
+// launch, for the NR output rows a thread gathers.  Per kernel tap the gathered row offsets / validity are computed once
+// (set_tap) and reused for the C / 16 K-tiles of the tap.  `kofs` is the thread's channel offset inside a row.
+// PAR: the rows belong to parity class (ph, pw); taps no row of the class can match are skipped.
+template <int NR, bool PAR>
+struct SegCursor {
+  const IgemmP& prm;
+  const int p, kofs, ph, pw;
+  int vi[NR], voh[NR], vow[NR];           // image and output pixel of row j; vi < 0: past the last row
+  int rowoff[NR];
+  bool rowok[NR];
+  int seg = 0, kh = 0, kw = 0, c0 = 0;
+  const float* abase = nullptr;
+  const float* bbase = nullptr;
+  int sIH = 0, sIW = 0, sC = 0, sKH = 0, sKW = 0, smul = 0, ssgn = 0, soffh = 0, soffw = 0, smask = 0, ssh = 0;
+  int kw0 = 0, kstep = 1;                 // PAR: first matching tap column and tap step of the segment
+  const float* bseg = nullptr;
+
+  __device__ __forceinline__ SegCursor(const IgemmP& prm_, int p_, int kofs_, int ph_ = 0, int pw_ = 0)
+      : prm(prm_), p(p_), kofs(kofs_), ph(ph_), pw(pw_) {}
+
+  // row j of this thread is row r of the launch (PAR: of the class)
+  __device__ __forceinline__ void set_row(int j, int r) {
+    if (r < (PAR ? prm.Rc : prm.R)) {
+      if (PAR) {
+        const int i = prm.dOHW2.div(r), rem = r - i * prm.OHW2;
+        const int a = prm.dOW2.div(rem);
+        vi[j] = i; voh[j] = 2 * a + ph; vow[j] = 2 * (rem - a * prm.OW2) + pw;
+      } else {
+        const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
+        vi[j] = i; voh[j] = prm.dOW.div(rem); vow[j] = rem - voh[j] * prm.OW;
+      }
+    } else {
+      vi[j] = -1; voh[j] = 0; vow[j] = 0;
+    }
+  }
+  __device__ __forceinline__ void begin_segment() {
+    if (PAR) {
+      while (seg < prm.nseg - 1 && (par_first_tap(prm.seg[seg], ph, prm.seg[seg].off_h) >= prm.seg[seg].KH ||
+                                    par_first_tap(prm.seg[seg], pw, prm.seg[seg].off_w) >= prm.seg[seg].KW)) ++seg;
+    }
+    const SegP& s = prm.seg[seg];
+    abase = s.a + (long long)p * s.a_ps;
+    bbase = s.b + (long long)p * s.b_ps;
+    sIH = s.IH; sIW = s.IW; sC = s.C; sKH = s.KH; sKW = s.KW;
+    smul = s.mul; ssgn = s.sgn; soffh = s.off_h; soffw = s.off_w; smask = s.mask; ssh = s.sh;
+    kh = 0; kw = 0; c0 = 0;
+    if (PAR) {
+      kstep = s.mask ? 2 : 1;
+      kh = par_first_tap(s, ph, s.off_h); kw0 = par_first_tap(s, pw, s.off_w); kw = kw0;
+      bseg = bbase;
+      bbase = bseg + (long long)((kh * sKW + kw) * sC) * prm.N;
+    }
+  }
+  __device__ __forceinline__ void set_tap() {
+    const int th = ssgn * kh + soffh, tw = ssgn * kw + soffw;      // scalar
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int t0h = voh[j] * smul + th, t0w = vow[j] * smul + tw;
+      const int ih = t0h >> ssh, iw = t0w >> ssh;
+      rowok[j] = (vi[j] >= 0) && (((t0h | t0w) & smask) == 0) && ((unsigned)ih < (unsigned)sIH) &&
+                 ((unsigned)iw < (unsigned)sIW);
+      rowoff[j] = rowok[j] ? ((vi[j] * sIH + ih) * sIW + iw) * sC + kofs : 0;
+    }
+  }
+  // this thread's channels of row j in the K-tile under the cursor; masked rows read the zero page: no exec branch
+  // around the load, so vmcnt waits can be counted
+  __device__ __forceinline__ const float* a_src(int j) const {
+    return rowok[j] ? (abase + c0 + (unsigned)rowoff[j]) : prm.zeros;
+  }
+  // move to the next K-tile (callers never advance past the last tile)
+  __device__ __forceinline__ void advance() {
+    c0 += BK;
+    bbase += BK * prm.N;
+    if (c0 == sC) {
+      c0 = 0;
+      if (PAR) {
+        kw += kstep;
+        if (kw >= sKW) { kw = kw0; kh += kstep; }
+        if (kh >= sKH) { ++seg; begin_segment(); }
+        else bbase = bseg + (long long)((kh * sKW + kw) * sC) * prm.N;
+      } else {
+        if (++kw == sKW) { kw = 0; ++kh; }
+        if (kh == sKH) { ++seg; begin_segment(); }
+      }
+      set_tap();
+    }
+  }
+};
+
 template <int WM, int WN, int TM, int TN, bool SPLIT = false, bool PAR = false, bool BV = false, bool KS = false>
 __global__ __launch_bounds__(WM * WN * 64) void igemm_fast_kernel(const IgemmP prm) {
   static_assert(!KS || (!PAR && !SPLIT), "split-K: plain row order, exact f32");
@@ -567,31 +755,10 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_fast_kernel(const IgemmP p
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int N = prm.N, R = PAR ? prm.Rc : prm.R;
+  const int N = prm.N;
   const int tiles_n = (N + BN - 1) / BN;
-  // Workgroups go round-robin over the 8 XCDs (each with its own L2): give every XCD a CONTIGUOUS run of row tiles, so
-  // the halo rows two neighbouring tiles both gather come out of one L2.  Measured on the 32-column tile (400 tiles per
-  // probe): HBM reads 6.62 -> 5.18 GB per launch, time -1 %.  Not for the parity-class grid (its order is by class:
-  // 4.72 -> 6.5 GB and +50 % time when remapped).
   int bid = blockIdx.x, byp = blockIdx.y;
-  if (!PAR) {
-    const int gx = (int)gridDim.x;
-    if (gx >= 64) {
-      // many row tiles per probe (large feature maps): an XCD keeps the SAME tile range for every probe, so the
-      // primal operands of those rows (activations, x-hat, act') stay in its L2 across the probes
-      const int g8 = gx & ~7;
-      if (bid < g8) bid = (bid & 7) * (g8 >> 3) + (bid >> 3);
-    } else {
-      // few row tiles per probe (small feature maps, large per-probe weight slices): an XCD works through whole
-      // probes, so a probe's weight slice is fetched into one L2 only (128-column tile: 3.3 -> 2.4 GB per launch;
-      // on the 32- and 64-column tiles this order was measured worse: 6.9 -> 8.4 and 3.7 -> 4.5 GB)
-      const int g8 = (gx * (int)gridDim.y) & ~7, lin = bid + gx * byp;
-      if (lin < g8) {
-        const int w = (lin & 7) * (g8 >> 3) + (lin >> 3);
-        byp = w / gx; bid = w - byp * gx;
-      }
-    }
-  }
+  if (!PAR) xcd_block_order(bid, byp);
   const int tile_n = bid % tiles_n;
   int tile_m = bid / tiles_n, ph = 0, pw = 0;
   if (PAR) {                    // 4 parity classes x tiles-per-class row tiles
@@ -604,113 +771,22 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_fast_kernel(const IgemmP p
   for (int i = tid; i < 2 * BN; i += NT) redbuf[i] = 0.f;
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  zero_acc(acc);
 
   // thread -> (row m_j, k-quad kq): quad q = tid + j*NT, m_j = q >> 2, kq = tid & 3 (NT % 4 == 0)
   const int kq4 = (tid & 3) * 4;
-  int vi[AQ], voh[AQ], vow[AQ];
+  SegCursor<AQ, PAR> cur(prm, p, kq4, ph, pw);
 #pragma unroll
-  for (int j = 0; j < AQ; ++j) {
-    const int r = r0 + ((tid + j * NT) >> 2);
-    if (r < R) {
-      if (PAR) {
-        const int i = prm.dOHW2.div(r), rem = r - i * prm.OHW2;
-        const int a = prm.dOW2.div(rem);
-        vi[j] = i; voh[j] = 2 * a + ph; vow[j] = 2 * (rem - a * prm.OW2) + pw;
-      } else {
-        const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
-        vi[j] = i; voh[j] = prm.dOW.div(rem); vow[j] = rem - voh[j] * prm.OW;
-      }
-    } else {
-      vi[j] = -1; voh[j] = 0; vow[j] = 0;
-    }
-  }
-  // loop-invariant B element offsets: e = tid + j*NT -> (k = e / BN, nn = e % BN)
-  unsigned bidx[NB];
-  bool bok[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const int e = tid + j * NT;
-    if (BW > 1) {
-      const int k = e / (BN / BW), nq = e - k * (BN / BW);
-      bok[j] = (n0 + BW * nq) < N;
-      bidx[j] = (unsigned)(k * N + n0 + BW * nq);
-    } else {
-      const int k = e / BN, nn = e - k * BN;
-      bok[j] = (n0 + nn) < N;
-      bidx[j] = (unsigned)(k * N + n0 + nn);
-    }
-  }
+  for (int j = 0; j < AQ; ++j) cur.set_row(j, r0 + ((tid + j * NT) >> 2));
+  const BStage<BN, NT, BW> bst(tid, n0, N);
 
-  int rowoff[AQ];
-  bool rowok[AQ];
-
-  // segment scalars + K cursor
-  int seg = 0, kh = 0, kw = 0, c0 = 0;
-  const float* abase = nullptr;
-  const float* bbase = nullptr;
-  int sIH = 0, sIW = 0, sC = 0, sKH = 0, sKW = 0, smul = 0, ssgn = 0, soffh = 0, soffw = 0, smask = 0, ssh = 0;
-  int kw0 = 0, kstep = 1;                 // PAR: first matching tap column and tap step of the segment
-  const float* bseg = nullptr;
-
-  // PAR: taps of a stride-2 transposed segment that can match the class: k = (parity + pad) & 1, step 2
-  auto first_tap = [&](const SegP& s, int par, int off) { return s.mask ? ((par + off) & 1) : 0; };
-  auto begin_segment = [&]() {
-    if (PAR) {
-      while (seg < prm.nseg - 1 && (first_tap(prm.seg[seg], ph, prm.seg[seg].off_h) >= prm.seg[seg].KH ||
-                                    first_tap(prm.seg[seg], pw, prm.seg[seg].off_w) >= prm.seg[seg].KW)) ++seg;
-    }
-    const SegP& s = prm.seg[seg];
-    abase = s.a + (long long)p * s.a_ps;
-    bbase = s.b + (long long)p * s.b_ps;
-    sIH = s.IH; sIW = s.IW; sC = s.C; sKH = s.KH; sKW = s.KW;
-    smul = s.mul; ssgn = s.sgn; soffh = s.off_h; soffw = s.off_w; smask = s.mask; ssh = s.sh;
-    kh = 0; kw = 0; c0 = 0;
-    if (PAR) {
-      kstep = s.mask ? 2 : 1;
-      kh = first_tap(s, ph, s.off_h); kw0 = first_tap(s, pw, s.off_w); kw = kw0;
-      bseg = bbase;
-      bbase = bseg + (long long)((kh * sKW + kw) * sC) * N;
-    }
-  };
-  auto set_tap = [&]() {
-    const int th = ssgn * kh + soffh, tw = ssgn * kw + soffw;      // scalar
-#pragma unroll
-    for (int j = 0; j < AQ; ++j) {
-      const int t0h = voh[j] * smul + th, t0w = vow[j] * smul + tw;
-      const int ih = t0h >> ssh, iw = t0w >> ssh;
-      rowok[j] = (vi[j] >= 0) && (((t0h | t0w) & smask) == 0) && ((unsigned)ih < (unsigned)sIH) &&
-                 ((unsigned)iw < (unsigned)sIW);
-      rowoff[j] = rowok[j] ? ((vi[j] * sIH + ih) * sIW + iw) * sC + kq4 : 0;
-    }
-  };
   auto load_tile = [&](float (&areg)[AE], float (&breg)[BE]) {
-    const float* ap = abase + c0;
 #pragma unroll
     for (int j = 0; j < AQ; ++j) {
-      // masked rows read the zero page: no exec branch around the load, so vmcnt waits can be counted
-      const float* src = rowok[j] ? (ap + (unsigned)rowoff[j]) : prm.zeros;
-      const float4 v = *reinterpret_cast<const float4*>(src);
+      const float4 v = *reinterpret_cast<const float4*>(cur.a_src(j));
       areg[4 * j + 0] = v.x; areg[4 * j + 1] = v.y; areg[4 * j + 2] = v.z; areg[4 * j + 3] = v.w;
     }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const float* src = bok[j] ? (bbase + bidx[j]) : prm.zeros;
-      if (BW == 4) {
-        const float4u v = *reinterpret_cast<const float4u*>(src);
-        breg[4 * j + 0] = v[0]; breg[4 * j + 1] = v[1]; breg[4 * j + 2] = v[2]; breg[4 * j + 3] = v[3];
-      } else if (BW == 2) {
-        const float2u v = *reinterpret_cast<const float2u*>(src);
-        breg[2 * j + 0] = v[0]; breg[2 * j + 1] = v[1];
-      } else {
-        breg[j] = *src;
-      }
-    }
+    bst.load(cur.bbase, prm.zeros, breg);
   };
   auto store_tile = [&](const float (&areg)[AE], const float (&breg)[BE], float* Asb, float* Bsb) {
     if (SPLIT) {
@@ -743,46 +819,15 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_fast_kernel(const IgemmP p
         for (int t = 0; t < 4; ++t) Asb[(kq4 + t) * LDA + m] = areg[4 * j + t];
       }
     }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int e = tid + j * NT;
-      if (BW == 4) {
-        const int k = e / (BN / 4), nq = e - k * (BN / 4);
-        *reinterpret_cast<float4*>(&Bsb[k * LDB + 4 * nq]) =
-            make_float4(breg[4 * j + 0], breg[4 * j + 1], breg[4 * j + 2], breg[4 * j + 3]);
-      } else if (BW == 2) {
-        const int k = e / (BN / 2), nq = e - k * (BN / 2);
-        *reinterpret_cast<float2*>(&Bsb[k * LDB + 2 * nq]) = make_float2(breg[2 * j + 0], breg[2 * j + 1]);
-      } else {
-        const int k = e / BN, nn = e - k * BN;
-        Bsb[k * LDB + nn] = breg[j];
-      }
-    }
+    bst.store_kmajor(breg, Bsb);
   };
-  // move to the next K-tile (callers never advance past the last tile)
-  auto advance = [&]() {
-    c0 += BK;
-    bbase += BK * N;
-    if (c0 == sC) {
-      c0 = 0;
-      if (PAR) {
-        kw += kstep;
-        if (kw >= sKW) { kw = kw0; kh += kstep; }
-        if (kh >= sKH) { ++seg; begin_segment(); }
-        else bbase = bseg + (long long)((kh * sKW + kw) * sC) * N;
-      } else {
-        if (++kw == sKW) { kw = 0; ++kh; }
-        if (kh == sKH) { ++seg; begin_segment(); }
-      }
-      set_tap();
-    }
-  };
+  auto advance = [&]() { cur.advance(); };
 
   int ktiles = 0;
   for (int q = 0; q < prm.nseg; ++q) {
     const SegP& s = prm.seg[q];
     if (PAR) {
-      const int st = s.mask ? 2 : 1, h0 = first_tap(s, ph, s.off_h), w0 = first_tap(s, pw, s.off_w);
+      const int st = s.mask ? 2 : 1, h0 = par_first_tap(s, ph, s.off_h), w0 = par_first_tap(s, pw, s.off_w);
       const int nh = h0 < s.KH ? (s.KH - h0 + st - 1) / st : 0, nw = w0 < s.KW ? (s.KW - w0 + st - 1) / st : 0;
       ktiles += nh * nw * (s.C / BK);
     } else {
@@ -797,13 +842,13 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_fast_kernel(const IgemmP p
     const int z = (int)blockIdx.z, ks = (int)gridDim.z;
     const int t0 = (int)((long long)ktiles * z / ks), t1 = (int)((long long)ktiles * (z + 1) / ks);
     int t = t0;
-    while (seg < prm.nseg - 1 && t >= prm.seg[seg].Ktot / BK) { t -= prm.seg[seg].Ktot / BK; ++seg; }
-    begin_segment();
-    const int tpt = sC / BK, tap = t / tpt;
-    c0 = (t - tap * tpt) * BK; kh = tap / sKW; kw = tap - kh * sKW;
-    bbase += (long long)t * BK * N;
+    while (cur.seg < prm.nseg - 1 && t >= prm.seg[cur.seg].Ktot / BK) { t -= prm.seg[cur.seg].Ktot / BK; ++cur.seg; }
+    cur.begin_segment();
+    const int tpt = cur.sC / BK, tap = t / tpt;
+    cur.c0 = (t - tap * tpt) * BK; cur.kh = tap / cur.sKW; cur.kw = tap - cur.kh * cur.sKW;
+    cur.bbase += (long long)t * BK * N;
     ktiles = t1 - t0;
-    set_tap();
+    cur.set_tap();
     pipelined_k_loop<AE, BE, ASZ, BSZ>(
         ktiles, As, Bs, load_tile, store_tile, advance,
         [&](const float* Asb, const float* Bsb) { mfma_sweep<WM, WN, TM, TN, LDA, LDB>(Asb, Bsb, acc, wm, wn, lane); });
@@ -815,8 +860,8 @@ __global__ __launch_bounds__(WM * WN * 64) void igemm_fast_kernel(const IgemmP p
     return;
   }
   if (!PAR || ktiles > 0) {               // PAR: a class no tap can reach (lone 1x1 stride-2) is all zeros
-    begin_segment();
-    set_tap();
+    cur.begin_segment();
+    cur.set_tap();
     pipelined_k_loop<AE, BE, ASZ, BSZ>(
         ktiles, As, Bs, load_tile, store_tile, advance,
         [&](const float* Asb, const float* Bsb) {
@@ -905,29 +950,16 @@ __global__ __launch_bounds__(256) void igemm_adirect_kernel(const IgemmP prm) {
   constexpr int AR = 8 * TM;                                  // A operand registers per K-tile: 8 channels of TM rows
   constexpr int BE = BN * BK / NT;                            // B floats per thread per K-tile (2 or 4)
   constexpr int BW = BV ? (BE >= 4 ? 4 : BE) : 1;
-  constexpr int NB = BE / BW;
   constexpr int LDB = BN, BSZ = BK * LDB;
   __shared__ __attribute__((aligned(16))) float Bs[2 * BSZ];
   __shared__ float redbuf[2 * BN];
 
   const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
-  const int N = prm.N, R = prm.R;
+  const int N = prm.N;
   const int tiles_n = (N + BN - 1) / BN;
   int bid = blockIdx.x, byp = blockIdx.y;
-  {   // XCD-contiguous order, as in igemm_fast_kernel
-    const int gx = (int)gridDim.x;
-    if (gx >= 64) {
-      const int g8 = gx & ~7;
-      if (bid < g8) bid = (bid & 7) * (g8 >> 3) + (bid >> 3);
-    } else {
-      const int g8 = (gx * (int)gridDim.y) & ~7, lin = bid + gx * byp;
-      if (lin < g8) {
-        const int w = (lin & 7) * (g8 >> 3) + (lin >> 3);
-        byp = w / gx; bid = w - byp * gx;
-      }
-    }
-  }
+  xcd_block_order(bid, byp);
   const int tile_n = bid % tiles_n, tile_m = bid / tiles_n;
   const int p = byp;
   const int r0 = tile_m * BM, n0 = tile_n * BN;
@@ -935,115 +967,27 @@ __global__ __launch_bounds__(256) void igemm_adirect_kernel(const IgemmP prm) {
   for (int i = tid; i < 2 * BN; i += NT) redbuf[i] = 0.f;
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  zero_acc(acc);
 
   // this lane's TM rows and its 8-channel half
-  int vi[TM], voh[TM], vow[TM];
+  SegCursor<TM, false> cur(prm, p, 8 * lh);
 #pragma unroll
-  for (int tm = 0; tm < TM; ++tm) {
-    const int r = r0 + (wm * TM + tm) * 32 + l31;
-    if (r < R) {
-      const int i = prm.dOHW.div(r), rem = r - i * prm.OHW;
-      vi[tm] = i; voh[tm] = prm.dOW.div(rem); vow[tm] = rem - voh[tm] * prm.OW;
-    } else {
-      vi[tm] = -1; voh[tm] = 0; vow[tm] = 0;
-    }
-  }
-  unsigned bidx[NB];
-  bool bok[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const int e = tid + j * NT;
-    if (BW > 1) {
-      const int k = e / (BN / BW), nq = e - k * (BN / BW);
-      bok[j] = (n0 + BW * nq) < N;
-      bidx[j] = (unsigned)(k * N + n0 + BW * nq);
-    } else {
-      const int k = e / BN, nn = e - k * BN;
-      bok[j] = (n0 + nn) < N;
-      bidx[j] = (unsigned)(k * N + n0 + nn);
-    }
-  }
+  for (int tm = 0; tm < TM; ++tm) cur.set_row(tm, r0 + (wm * TM + tm) * 32 + l31);
+  const BStage<BN, NT, BW> bst(tid, n0, N);
 
-  int rowoff[TM];
-  bool rowok[TM];
-  int seg = 0, kh = 0, kw = 0, c0 = 0;
-  const float* abase = nullptr;
-  const float* bbase = nullptr;
-  int sIH = 0, sIW = 0, sC = 0, sKH = 0, sKW = 0, smul = 0, ssgn = 0, soffh = 0, soffw = 0, smask = 0, ssh = 0;
-
-  auto begin_segment = [&]() __attribute__((always_inline)) {
-    const SegP& s = prm.seg[seg];
-    abase = s.a + (long long)p * s.a_ps;
-    bbase = s.b + (long long)p * s.b_ps;
-    sIH = s.IH; sIW = s.IW; sC = s.C; sKH = s.KH; sKW = s.KW;
-    smul = s.mul; ssgn = s.sgn; soffh = s.off_h; soffw = s.off_w; smask = s.mask; ssh = s.sh;
-    kh = 0; kw = 0; c0 = 0;
-  };
-  auto set_tap = [&]() __attribute__((always_inline)) {
-    const int th = ssgn * kh + soffh, tw = ssgn * kw + soffw;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-      const int t0h = voh[tm] * smul + th, t0w = vow[tm] * smul + tw;
-      const int ih = t0h >> ssh, iw = t0w >> ssh;
-      rowok[tm] = (vi[tm] >= 0) && (((t0h | t0w) & smask) == 0) && ((unsigned)ih < (unsigned)sIH) && ((unsigned)iw < (unsigned)sIW);
-      rowoff[tm] = rowok[tm] ? ((vi[tm] * sIH + ih) * sIW + iw) * sC + 8 * lh : 0;
-    }
-  };
   auto load_tile = [&](float (&areg)[AR], float (&breg)[BE]) __attribute__((always_inline)) {
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
-      const float* src = rowok[tm] ? (abase + c0 + (unsigned)rowoff[tm]) : prm.zeros;      // masked rows read the zero page
+      const float* src = cur.a_src(tm);
       const float4 v0 = *reinterpret_cast<const float4*>(src);
       const float4 v1 = *reinterpret_cast<const float4*>(src + 4);
       areg[8 * tm + 0] = v0.x; areg[8 * tm + 1] = v0.y; areg[8 * tm + 2] = v0.z; areg[8 * tm + 3] = v0.w;
       areg[8 * tm + 4] = v1.x; areg[8 * tm + 5] = v1.y; areg[8 * tm + 6] = v1.z; areg[8 * tm + 7] = v1.w;
     }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const float* bs = bok[j] ? (bbase + bidx[j]) : prm.zeros;
-      if (BW == 4) {
-        const float4u v = *reinterpret_cast<const float4u*>(bs);
-        breg[4 * j + 0] = v[0]; breg[4 * j + 1] = v[1]; breg[4 * j + 2] = v[2]; breg[4 * j + 3] = v[3];
-      } else if (BW == 2) {
-        const float2u v = *reinterpret_cast<const float2u*>(bs);
-        breg[2 * j + 0] = v[0]; breg[2 * j + 1] = v[1];
-      } else {
-        breg[j] = *bs;
-      }
-    }
+    bst.load(cur.bbase, prm.zeros, breg);
   };
-  auto store_b = [&](const float (&breg)[BE], float* Bsb) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int e = tid + j * NT;
-      if (BW == 4) {
-        const int k = e / (BN / 4), nq = e - k * (BN / 4);
-        *reinterpret_cast<float4*>(&Bsb[k * LDB + 4 * nq]) = make_float4(breg[4 * j + 0], breg[4 * j + 1], breg[4 * j + 2], breg[4 * j + 3]);
-      } else if (BW == 2) {
-        const int k = e / (BN / 2), nq = e - k * (BN / 2);
-        *reinterpret_cast<float2*>(&Bsb[k * LDB + 2 * nq]) = make_float2(breg[2 * j + 0], breg[2 * j + 1]);
-      } else {
-        const int k = e / BN, nn = e - k * BN;
-        Bsb[k * LDB + nn] = breg[j];
-      }
-    }
-  };
-  auto advance = [&]() __attribute__((always_inline)) {
-    c0 += BK;
-    bbase += BK * N;
-    if (c0 == sC) {
-      c0 = 0;
-      if (++kw == sKW) { kw = 0; ++kh; }
-      if (kh == sKH) { ++seg; begin_segment(); }
-      set_tap();
-    }
-  };
+  auto store_b = [&](const float (&breg)[BE], float* Bsb) __attribute__((always_inline)) { bst.store_kmajor(breg, Bsb); };
+  auto advance = [&]() __attribute__((always_inline)) { cur.advance(); };
   auto sweep = [&](const float (&areg)[AR], const float* Bsb) __attribute__((always_inline)) {
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
@@ -1062,8 +1006,8 @@ __global__ __launch_bounds__(256) void igemm_adirect_kernel(const IgemmP prm) {
   for (int q = 0; q < prm.nseg; ++q) T += prm.seg[q].Ktot / BK;
 
   float a0[AR], a1[AR], a2[AR], b0[BE], b1[BE], b2[BE];
-  begin_segment();
-  set_tap();
+  cur.begin_segment();
+  cur.set_tap();
   load_tile(a0, b0);
   store_b(b0, Bs);
   if (T > 1) { advance(); load_tile(a1, b1); }
@@ -1336,19 +1280,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
   const i32x4v tile4 = wx.tab[128 + l31];
   // block index -> (tile block (bi, by, bx), column block cb, probe p): wave-uniform, on the scalar unit
   int bid = __builtin_amdgcn_readfirstlane((int)blockIdx.x), byp = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
-  {   // XCD-contiguous order, as in igemm_fast_kernel
-    const int gx = (int)gridDim.x;
-    if (gx >= 64) {
-      const int g8 = gx & ~7;
-      if (bid < g8) bid = (bid & 7) * (g8 >> 3) + (bid >> 3);
-    } else {
-      const int g8 = (gx * (int)gridDim.y) & ~7, lin = bid + gx * byp;
-      if (lin < g8) {
-        const int w = (lin & 7) * (g8 >> 3) + (lin >> 3);
-        byp = wx.dgx.div(w); bid = w - byp * gx;
-      }
-    }
-  }
+  xcd_block_order(bid, byp, (int)gridDim.x, (int)gridDim.y, wx.dgx);
   const int tbid = wx.dnb.div(bid), cb = bid - tbid * (int)wx.dnb.d;
   const int bi = wx.dbxy.div(tbid), brem = tbid - bi * (int)wx.dbxy.d;
   const int by = wx.dnbx.div(brem), bx = brem - by * wx.nbx;
@@ -1387,10 +1319,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
   }
 
   f32x16 acc[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+  zero_acc(acc);
 
   f32x4v sreg[7], bq[2][4];
   // (buffer loads are cast to float vectors whole: element access through __builtin_bit_cast(float, v[j]) on the
@@ -1578,10 +1507,7 @@ __global__ __launch_bounds__(256) void igemm_first_kernel(const IgemmP prm, int 
     const float e0v = prm.e0 ? prm.e0[(long long)p * prm.e0_ps + l31] : 0.f;
     const float e1v = has_e1 ? prm.e1[(long long)p * prm.e1_ps + l31] : 0.f;
     f32x16 acc[TM];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[tm][q] = 0.f;
+    zero_acc(acc);
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk)
 #pragma unroll
@@ -1597,6 +1523,100 @@ __global__ __launch_bounds__(256) void igemm_first_kernel(const IgemmP prm, int 
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) b[kk] = bn[kk];
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// process-wide state of the launchers: device zero page, CU count, scratch planes, tile override and the precision /
+// split-K / Winograd modes
+// ------------------------------------------------------------------------------------------
+// 256 bytes of device zeros (per device): the source of masked gather rows in the fast kernels.
+static const float* zero_page() {
+  static float* pages[64] = {nullptr};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+  if (!pages[dev]) {
+    float* ptr = nullptr;
+    if (hipMalloc((void**)&ptr, 256) != hipSuccess) return nullptr;
+    if (hipMemset(ptr, 0, 256) != hipSuccess) return nullptr;
+    pages[dev] = ptr;
+  }
+  return pages[dev];
+}
+
+static int tile_override() {
+  static int v = -2;
+  if (v == -2) { const char* e = getenv("LIP_TILE"); v = e ? atoi(e) : -1; }
+  return v;
+}
+
+static int cu_count() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    hipDeviceProp_t pr;
+    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
+            ? pr.multiProcessorCount : 256;
+  }
+  return n;
+}
+
+// Scratch planes of the split-K launches, one buffer per (device, stream) — kernels of one stream are ordered, so the
+// shares of launch i are consumed by its finishing pass before launch i+1 overwrites them; a second stream or device
+// gets its own buffer.  Grown on demand (after draining that stream), kept for the life of the process.  Returns null
+// when the table of 16 entries is full or the allocation fails (the caller then launches unsplit).
+static float* ksplit_scratch(size_t floats, hipStream_t st) {
+  struct Entry { int dev; hipStream_t st; float* buf; size_t cap; };
+  static Entry table[16];
+  static int used = 0;
+  static std::mutex mu;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
+  Entry* e = nullptr;
+  for (int i = 0; i < used; ++i)
+    if (table[i].dev == dev && table[i].st == st) { e = &table[i]; break; }
+  if (!e) {
+    if (used == 16) return nullptr;
+    e = &table[used++];
+    e->dev = dev; e->st = st; e->buf = nullptr; e->cap = 0;
+  }
+  if (e->cap < floats) {
+    if (e->buf) { (void)hipStreamSynchronize(st); (void)hipFree(e->buf); e->buf = nullptr; e->cap = 0; }
+    if (hipMalloc((void**)&e->buf, floats * sizeof(float)) != hipSuccess) return nullptr;
+    e->cap = floats;
+  }
+  return e->buf;
+}
+
+// 0: exact f32 MFMA (default); 1: split-precision bf16x3 operands (lip_set_precision / LIP_PRECISION=bf16x3)
+static int g_precision = -1;
+int precision_mode() {
+  if (g_precision < 0) {
+    const char* e = getenv("LIP_PRECISION");
+    g_precision = (e && (e[0] == 'b' || e[0] == '1')) ? 1 : 0;
+  }
+  return g_precision;
+}
+void set_precision_mode(int m) { g_precision = m ? 1 : 0; }
+
+// split-K of under-filled implicit GEMMs: -1 = not set (environment LIP_NOKSPLIT decides), 0 = off, 1 = on
+static int g_split_k = -1;
+void set_split_k_mode(int on) { g_split_k = on ? 1 : 0; }
+static bool split_k_enabled() {
+  if (g_split_k < 0) g_split_k = getenv("LIP_NOKSPLIT") ? 0 : 1;
+  return g_split_k == 1;
+}
+
+// Winograd route of the 3x3 / stride-1 layers: -1 = not set (environment: LIP_NOWINO -> off), 0 = off, 1 = on (default:
+// every eligible launch), 2 = on (kept for the tests that force the route; same launches as 1 since the fill rule went)
+static int g_wino = -1;
+void set_wino_mode(int m) { g_wino = (m < 0 || m > 2) ? 1 : m; }
+int wino_mode() {
+  if (g_wino < 0) {
+    const char* f = getenv("LIP_WINO");
+    g_wino = getenv("LIP_NOWINO") ? 0 : ((f && f[0] == 'f') ? 2 : 1);
+  }
+  return g_wino;
 }
 
 static bool igemm_first_ok(const IgemmP& p, int P) {
@@ -1775,12 +1795,7 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_kernel(const WgradP prm) {
   if (rbeg >= rend) return;
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  zero_acc(acc);
 
   const WgradTap tap = wgrad_tap<BM>(prm, m0, tid);
   wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, rbeg, rend, n0, As, Bs, acc);
@@ -1856,18 +1871,12 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_fast_kernel(const WgradP p
   const int N = prm.N, M = prm.M;
   const int NC = PB ? prm.P * N : N;           // GEMM columns of this launch
   const int tiles_n = (NC + BN - 1) / BN;
-  // Workgroups go round-robin over the 8 XCDs: remap the (tile, probe) index so that every XCD works through a
-  // CONTIGUOUS run of it — the row tiles of one probe (which all stream the same cotangent rows) and the column tiles
-  // over one activation slab then share an L2 instead of fetching the operand once per XCD.
-  int bx = blockIdx.x, by = PB ? 0 : (int)blockIdx.y;
-  {
-    const int gx = (int)gridDim.x, tot = gx * (PB ? 1 : (int)gridDim.y), g8 = tot & ~7;
-    const int lin = bx + gx * by;
-    if (lin < g8) {
-      const int w = (lin & 7) * (g8 >> 3) + (lin >> 3);
-      by = w / gx; bx = w - by * gx;
-    }
-  }
+  // every XCD works through a CONTIGUOUS run of the (tile, probe) index — the row tiles of one probe (which all stream
+  // the same cotangent rows) and the column tiles over one activation slab then share an L2 instead of fetching the
+  // operand once per XCD.
+  const int gx = (int)gridDim.x;
+  const int w = xcd_contiguous((int)blockIdx.x + (PB ? 0 : gx * (int)blockIdx.y), gx * (PB ? 1 : (int)gridDim.y));
+  const int by = w / gx, bx = w - by * gx;
   // PB: row tile fastest, so the (three) row tiles of one column tile — same cotangent columns — are neighbours
   const int tiles_m = (int)gridDim.x / tiles_n;
   const int tile_n = PB ? bx / tiles_m : bx % tiles_n, tile_m = PB ? bx - tile_n * tiles_m : bx / tiles_n;
@@ -1882,12 +1891,7 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_fast_kernel(const WgradP p
   if (rbeg >= rend) return;
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  zero_acc(acc);
 
   // quad j of this thread: m = m0 + 4 * (q % QPR) -> tap (kh, kw) and channel ci; row q / QPR of the K-step.  Without
   // AGEN all AQ quads share the m-quad (the compiler folds the copies), rows krow0 + j * NT / QPR
@@ -2163,10 +2167,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           for (int q = 0; q < 16; ++q) add[tm][q] = 0.f;
       }
       f32x16 acc[TM];
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[tm][q] = 0.f;
+      zero_acc(acc);
 #pragma unroll
       for (int kk = 0; kk < KK; ++kk)
 #pragma unroll
@@ -2188,17 +2189,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-static int cu_count();
-
 static bool wgrad_skinny_ok(const WgradP& p) {
   static const bool off = getenv("LIP_NOSKINNY") != nullptr || getenv("LIP_GENERIC") != nullptr;       // A/B switch
   return !off && precision_mode() == 0 && p.seg_rows == 0 && p.ksplit <= 1 && p.R <= 64 && p.OHW == 1 && p.pad_h == 0 &&
          p.pad_w == 0 && p.KH == p.IH && p.KW == p.IW && (long long)p.R * p.M < (1ll << 31) && p.M >= 32 && p.N <= (1 << 20);
 }
 
-static bool wgrad_wino_ok(const WgradP& p, int P);
-static int wgrad_wino_splits(const WgradP& p, int P);
-bool wgrad_will_overwrite(const WgradP& p, int P) { return wgrad_skinny_ok(p) || (wgrad_wino_ok(p, P) && wgrad_wino_splits(p, P) == 1); }
 
 template <int TM, int KK>
 static hipError_t run_wgrad_skinny(const WgradP& p0, int P, hipStream_t st) {
@@ -2388,19 +2384,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
   const int C = prm.C, N = prm.N, W = prm.W, H = prm.H;
   const int ctn = C >> 5, ntn = N >> 5;
   int bid = blockIdx.x, byp = blockIdx.y;
-  {   // XCD-contiguous order: the blocks of one probe (they stream the same cotangent) share an L2
-    const int gx = (int)gridDim.x;
-    if (gx >= 64) {
-      const int g8 = gx & ~7;
-      if (bid < g8) bid = (bid & 7) * (g8 >> 3) + (bid >> 3);
-    } else {
-      const int g8 = (gx * (int)gridDim.y) & ~7, lin = bid + gx * byp;
-      if (lin < g8) {
-        const int w = (lin & 7) * (g8 >> 3) + (lin >> 3);
-        byp = w / gx; bid = w - byp * gx;
-      }
-    }
-  }
+  xcd_block_order(bid, byp);      // the blocks of one probe (they stream the same cotangent) share an L2
   const int nt = bid % ntn; bid /= ntn;
   const int ct = bid % ctn;
   const int z = bid / ctn;                          // share of the tiles
@@ -2416,10 +2400,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
   const unsigned row_bytes = (unsigned)(W * N * 4);
 
   f32x16 acc[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+  zero_acc(acc);
 
   const int m0 = z * prm.gps, m1 = m0 + prm.gps;
   f32x4v areg[2][4];
@@ -2502,10 +2483,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
   }
 }
 
-static int cu_count();
-static float* ksplit_scratch(size_t floats, hipStream_t st);
-int wino_mode();
-
 // shares of the tiles per (probe, c tile, n tile): 1 when the launch fills the chip without splitting
 static int wgrad_wino_splits(const WgradP& p, int P) {
   const long long blocks = (long long)(p.C / 32) * (p.N / 32) * P;
@@ -2534,6 +2511,8 @@ static bool wgrad_wino_ok(const WgradP& p, int P) {
   if (16ll * (T + 16ll * 64) * p.C * 4 >= (1ll << 31)) return false;
   return true;
 }
+
+bool wgrad_will_overwrite(const WgradP& p, int P) { return wgrad_skinny_ok(p) || (wgrad_wino_ok(p, P) && wgrad_wino_splits(p, P) == 1); }
 
 static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st) {
   WgWinoP q;
@@ -2598,12 +2577,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmNtP prm) {
   if (ktiles <= 0) return;
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  zero_acc(acc);
 
   // quad q = tid + j * NT -> (row = q >> 2, k-quad kq4 = 4 * (tid & 3)), j = 0, 1
   const int kq4 = (tid & 3) * 4;
@@ -2715,23 +2689,14 @@ __global__ __launch_bounds__(256) void gemm_nn_axpy_kernel(const GemmNnP prm) {
   // block -> (column tile, row tile), row tile fastest, and every XCD a contiguous run of blocks: the row tiles of a
   // column tile read the same 128-column slab of B and should find it in one L2
   const int tiles_m = (prm.m + BM - 1) / BM;
-  long long bid = blockIdx.x;
-  {
-    const long long g8 = (long long)gridDim.x & ~7ll;
-    if (bid < g8) bid = (bid & 7) * (g8 >> 3) + (bid >> 3);
-  }
+  const long long bid = xcd_contiguous((long long)blockIdx.x, (long long)gridDim.x);
   const int m0 = (int)(bid % tiles_m) * BM;
   const long long n0 = (bid / tiles_m) * BN;
   const int ktiles = (prm.k + BK - 1) / BK;
   const bool cols_full = n0 + BN <= prm.N;                                       // uniform over the block
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+  zero_acc(acc);
 
   // All loads are unconditional on clamped addresses (a conditional load costs a branch and a full wait per element:
   // the first version of this kernel, 3.13 ms against 2.97 now and hipBLASLt's 2.84 on (256 x 450)(450 x 1.08 M)).
@@ -2943,39 +2908,6 @@ int routes_read(int64_t* counts, int n, const char** names) {
 // ------------------------------------------------------------------------------------------
 // launchers: pick the tile shape from the problem shape
 // ------------------------------------------------------------------------------------------
-// 256 bytes of device zeros (per device): the source of masked gather rows in the fast kernels.
-static const float* zero_page() {
-  static float* pages[64] = {nullptr};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  if (!pages[dev]) {
-    float* ptr = nullptr;
-    if (hipMalloc((void**)&ptr, 256) != hipSuccess) return nullptr;
-    if (hipMemset(ptr, 0, 256) != hipSuccess) return nullptr;
-    pages[dev] = ptr;
-  }
-  return pages[dev];
-}
-
-// 0: exact f32 MFMA (default); 1: split-precision bf16x3 operands (lip_set_precision / LIP_PRECISION=bf16x3)
-static int g_precision = -1;
-int precision_mode() {
-  if (g_precision < 0) {
-    const char* e = getenv("LIP_PRECISION");
-    g_precision = (e && (e[0] == 'b' || e[0] == '1')) ? 1 : 0;
-  }
-  return g_precision;
-}
-void set_precision_mode(int m) { g_precision = m ? 1 : 0; }
-
-// split-K of under-filled implicit GEMMs: -1 = not set (environment LIP_NOKSPLIT decides), 0 = off, 1 = on
-static int g_split_k = -1;
-void set_split_k_mode(int on) { g_split_k = on ? 1 : 0; }
-static bool split_k_enabled() {
-  if (g_split_k < 0) g_split_k = getenv("LIP_NOKSPLIT") ? 0 : 1;
-  return g_split_k == 1;
-}
-
 static bool igemm_fast_ok(const IgemmP& p) {
   for (int s = 0; s < p.nseg; ++s) {
     const SegP& q = p.seg[s];
@@ -2983,36 +2915,6 @@ static bool igemm_fast_ok(const IgemmP& p) {
     if ((((uintptr_t)q.a) & 15) || (q.a_ps & 3)) return false;
   }
   return true;
-}
-
-static int cu_count();
-
-// Scratch planes of the split-K launches, one buffer per (device, stream) — kernels of one stream are ordered, so the
-// shares of launch i are consumed by its finishing pass before launch i+1 overwrites them; a second stream or device
-// gets its own buffer.  Grown on demand (after draining that stream), kept for the life of the process.  Returns null
-// when the table of 16 entries is full or the allocation fails (the caller then launches unsplit).
-static float* ksplit_scratch(size_t floats, hipStream_t st) {
-  struct Entry { int dev; hipStream_t st; float* buf; size_t cap; };
-  static Entry table[16];
-  static int used = 0;
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  Entry* e = nullptr;
-  for (int i = 0; i < used; ++i)
-    if (table[i].dev == dev && table[i].st == st) { e = &table[i]; break; }
-  if (!e) {
-    if (used == 16) return nullptr;
-    e = &table[used++];
-    e->dev = dev; e->st = st; e->buf = nullptr; e->cap = 0;
-  }
-  if (e->cap < floats) {
-    if (e->buf) { (void)hipStreamSynchronize(st); (void)hipFree(e->buf); e->buf = nullptr; e->cap = 0; }
-    if (hipMalloc((void**)&e->buf, floats * sizeof(float)) != hipSuccess) return nullptr;
-    e->cap = floats;
-  }
-  return e->buf;
 }
 
 template <int WM, int WN, int TM, int TN>
@@ -3127,35 +3029,6 @@ static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
     hipLaunchKernelGGL((igemm_kernel<WM, WN, TM, TN>), grid, dim3(T::NT), 0, st, p);
   }
   return hipGetLastError();
-}
-
-static int tile_override() {
-  static int v = -2;
-  if (v == -2) { const char* e = getenv("LIP_TILE"); v = e ? atoi(e) : -1; }
-  return v;
-}
-
-static int cu_count() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-            ? pr.multiProcessorCount : 256;
-  }
-  return n;
-}
-
-// Winograd route of the 3x3 / stride-1 layers: -1 = not set (environment: LIP_NOWINO -> off), 0 = off, 1 = on (default:
-// every eligible launch), 2 = on (kept for the tests that force the route; same launches as 1 since the fill rule went)
-static int g_wino = -1;
-void set_wino_mode(int m) { g_wino = (m < 0 || m > 2) ? 1 : m; }
-int wino_mode() {
-  if (g_wino < 0) {
-    const char* f = getenv("LIP_WINO");
-    g_wino = getenv("LIP_NOWINO") ? 0 : ((f && f[0] == 'f') ? 2 : 1);
-  }
-  return g_wino;
 }
 
 struct WinoGeom { int BWs, BHs, NI, FR, FC, nbx, nby, nbi, NS, TH, TW; };
@@ -3506,12 +3379,7 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_sqsum_kernel(const WgradP 
   const WgradTap tap = wgrad_tap<BM>(prm, m0, tid);
   for (int q = q0; q < q1; ++q) {
     const int p = q / sq.n_img, i = q - p * sq.n_img;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+    zero_acc(acc);
     // its leading barrier also orders the previous pair's last sweep before these LDS stores
     wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, i * prm.OHW, (i + 1) * prm.OHW, n0,
                                           As, Bs, acc);
@@ -3705,12 +3573,7 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_wnorm_kernel(const WgradP 
   float* part = wn_.partial + (long long)blockIdx.x * wn_.pairs;
   for (int q = q0; q < q1; ++q) {
     const int p = q / wn_.n_img, i = q - p * wn_.n_img;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+    zero_acc(acc);
     // its leading barrier also orders the previous pair's last sweep and wave sums before these LDS stores
     wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, i * prm.OHW, (i + 1) * prm.OHW, n0,
                                           As, Bs, acc);

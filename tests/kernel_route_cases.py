@@ -105,6 +105,17 @@ def _igemm_cases() -> List[Case]:
         # transposed stride 2 onto an ODD map: no parity-class order
         Case("tconv_odd", "igemm_fast<2,2,1,1>/bv4", conv(1, 4, 16, 64, 2, s=2, mode=1, OH=7)),
         Case("tconv_odd_generic", "igemm<2,2,1,1>", conv(1, 4, 17, 48, 2, s=2, mode=1, OH=7)),
+        # ---- K cursor of igemm_adirect_kernel (n = 1, 32 x 32 output, P = 64 as IG["4,1,1,1"]; T = K-tiles): the prologue
+        # branches T <= 3, the largest T that never enters the 6-way unrolled main loop, two trips of it, the segment
+        # switch inside advance() and the stride-2 mask path without the parity order
+        Case("adirect_T1", "igemm_adirect<4,1,1,1>/bv4", conv(1, 32, 16, 32, 64, k=1), cu=True),
+        Case("adirect_T2", "igemm_adirect<4,1,1,2>", conv(1, 32, 32, 63, 64, k=1, a_pp=True), cu=True),
+        Case("adirect_T3", "igemm_adirect<4,1,1,2>/bv4", conv(1, 32, 48, 64, 64, k=1), cu=True),
+        Case("adirect_T8", "igemm_adirect<4,1,1,1>/bv4", conv(1, 32, 32, 32, 64, k=2), cu=True),       # 31 x 31 output, R = 961
+        Case("adirect_T15", "igemm_adirect<4,1,1,1>/bv4", conv(1, 32, 16, 32, 64, k=3, kw=5), cu=True),
+        Case("adirect_nseg2", "igemm_adirect<4,1,1,2>/bv4",
+             conv(1, 32, 16, 64, 64, nseg=2, b_pp=True, epi={"e0": "probe", "dphi": "shared"}), cu=True),
+        Case("adirect_tconv_odd", "igemm_adirect<4,1,1,1>/bv4", conv(1, 16, 16, 32, 64, s=2, mode=1, OH=31), cu=True),
         # multi-segment and transposed B
         Case("fast_nseg2", "igemm_fast<2,2,1,2>/bv4", conv(1, 8, 16, 96, 2, nseg=2, b_pp=True)),
         Case("fast_nseg3_par", "igemm_fast<2,2,1,1>/par/bv4", conv(1, 4, 16, 64, 2, s=2, mode=1, OH=8, nseg=3)),
