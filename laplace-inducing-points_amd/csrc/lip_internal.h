@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <mutex>
+#include <type_traits>
+#include <utility>
 #include "lip.h"
 
 namespace lip {
@@ -253,6 +256,66 @@ int routes_read(int64_t* counts, int n, const char** names);
     static const char* const lip_pn_[5] = {"quad", "quad_wide", "fixed", "atomic", "mixed"};  \
     LIP_ROUTE_KEYED(path, 5, kernel "/%s", lip_pn_[path]);              \
   } while (0)
+
+// ---- environment switches ----------------------------------------------------------------------
+// Every LIP_* variable the library reads, one field each.  switches() reads them all on its first call and never again:
+// "once per process" is a contract (tests/test_ab_switches.py starts one child process per setting because of it).
+// Unless a field says otherwise it is true when the variable is set to anything.  All but the first four are A/B switches.
+struct Switches {
+  bool precision_x3;   // LIP_PRECISION: first letter b or 1 -> the precision mode starts as 1 (bf16x3 operands), else 0 (exact f32)
+  bool noksplit;       // LIP_NOKSPLIT: split-K of under-filled implicit GEMMs starts off
+  bool nowino;         // LIP_NOWINO: the Winograd mode starts as 0 (off); overrides LIP_WINO
+  bool wino_f;         // LIP_WINO: first letter f -> the Winograd mode starts as 2, else 1
+  bool generic;        // LIP_GENERIC: igemm / wgrad instead of every specialised direct kernel (the Winograd test precedes it)
+  bool nofirst;        // LIP_NOFIRST: no first-layer kernels (igemm_first, wgrad_first)
+  bool noskinny;       // LIP_NOSKINNY: no wgrad_skinny on the dense layers
+  bool nopb;           // LIP_NOPB: no probe-batched weight gradient (wgrad_pb)
+  bool nopb96;         // LIP_NOPB96: no 96-row probe-batched tile for N = 64, M = 576
+  bool wgrad3;         // LIP_WGRAD3: the three-wave wgrad_pb<3,1,1,4> also in f32 mode
+  bool nopar;          // LIP_NOPAR: plain row order for even-grid stride-2 data gradients
+  bool nobv4;          // LIP_NOBV4: dword instead of dwordx4 B / cotangent loads (igemm_fast, igemm_adirect, wgrad_fast)
+  bool noadirect;      // LIP_NOADIRECT: igemm_fast<4,1,*,*> instead of igemm_adirect
+  bool wino_novepi;    // LIP_WINO_NOVEPI: the scalar Winograd epilogue on aligned operands
+  bool nosmallp;       // LIP_NOSMALLP: the 128-row tiles also at few probes
+  int smallp_factor;   // LIP_SMALLP_FACTOR: few probes = fewer 128-row blocks than this many per CU (default 2)
+  int wgw_minblocks;   // LIP_WGW_MINBLOCKS: fewest (probe, c tile, n tile) blocks that take wgrad_wino (default 2)
+  int tile;            // LIP_TILE: experiment tiles of launch_igemm, 1..4 (default -1: none)
+  bool dbg;            // LIP_DBG: cycle stamps of igemm_fast, reported on stderr after a stream synchronisation (never timed)
+  bool dot_nt_valu;    // LIP_DOT_NT_VALU: the VALU / LDS kernel of lip_dot_nt_f64
+  bool dot_nt_noquad;  // LIP_DOT_NT_NOQUAD: lip_dot_nt_f64 with one tile per block, the waves splitting K
+};
+const Switches& switches();
+
+// ---- one record per (device, stream) ---------------------------------------------------------------
+// with(st, f) finds or creates the record of (current device, st) and returns f(record), run under the table's lock.
+// It returns a value-initialised result (a null pointer) when hipGetDevice fails or all CAP records belong to other
+// (device, stream) pairs; records live for the life of the process.
+template <class Rec, int CAP = 16>
+class PerStream {
+  struct Slot { int dev; hipStream_t st; Rec rec; };
+  Slot slots_[CAP];
+  int used_ = 0;
+  std::mutex mu_;
+ public:
+  template <class F> auto with(hipStream_t st, F&& f) -> decltype(f(std::declval<Rec&>())) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return {};
+    std::lock_guard<std::mutex> lock(mu_);
+    for (int i = 0; i < used_; ++i)
+      if (slots_[i].dev == dev && slots_[i].st == st) return f(slots_[i].rec);
+    if (used_ == CAP) return {};
+    Slot& s = slots_[used_++];
+    s.dev = dev; s.st = st; s.rec = Rec();
+    return f(s.rec);
+  }
+};
+
+// f(std::true_type()) or f(std::false_type()): a run-time flag as a template argument.  LIP_ROUTE inside a generic
+// lambda caches one slot per instantiation, so a name formatted from the flag types is the route of the kernel launched.
+template <class F> auto with_flag(bool on, F&& f) {
+  if (on) return f(std::true_type());
+  return f(std::false_type());
+}
 
 void set_error(const char* fmt, ...);
 int precision_mode();

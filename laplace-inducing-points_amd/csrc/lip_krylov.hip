@@ -515,20 +515,11 @@ __global__ __launch_bounds__(1024) void dot_nt_reduce_kernel(const double* __res
 // i's partial tiles are reduced before launch i + 1 overwrites them; a second stream or thread gets its own buffer.
 // Null when the table is full or the allocation fails — the caller then takes the float64-atomics path.
 static double* dot_nt_scratch(hipStream_t st) {
-  struct Entry { int dev; hipStream_t st; double* buf; };
-  static Entry table[16];
-  static int used = 0;
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  for (int i = 0; i < used; ++i)
-    if (table[i].dev == dev && table[i].st == st) return table[i].buf;
-  if (used == 16) return nullptr;
-  double* buf = nullptr;
-  if (hipMalloc((void**)&buf, sizeof(double) * DT_SCRATCH_TILES * DT_B * DT_B) != hipSuccess) return nullptr;
-  table[used++] = Entry{dev, st, buf};
-  return buf;
+  static PerStream<double*> table;
+  return table.with(st, [](double*& buf) {
+    if (!buf && hipMalloc((void**)&buf, sizeof(double) * DT_SCRATCH_TILES * DT_B * DT_B) != hipSuccess) buf = nullptr;
+    return buf;
+  });
 }
 
 // ---- Out[i] = zscale * Z[i] + sum_j Cm[i][j] Y[j]: r combinations of the s rows of Y (s, N), streamed once per tile of
@@ -795,8 +786,7 @@ int lip_dot_nt_f64(const float* A, int64_t lda, int32_t m, const float* B, int64
   // tiles than it holds or no buffer is to be had
   double* part = (ks > 1 && tiles * ks <= DT_SCRATCH_TILES) ? dot_nt_scratch(st) : nullptr;
   if (!part) LIP_CHECK_HIP(hipMemsetAsync(C, 0, sizeof(double) * (size_t)m * n, st));
-  static const bool valu = getenv("LIP_DOT_NT_VALU") != nullptr;          // A/B switch: the VALU / LDS kernel
-  static const bool noquad = getenv("LIP_DOT_NT_NOQUAD") != nullptr;      // A/B switch: one tile per block, waves split K
+  const bool valu = switches().dot_nt_valu, noquad = switches().dot_nt_noquad;      // A/B switches
   const int tm32 = (m + DT_B - 1) / DT_B, tn32 = (n + DT_B - 1) / DT_B;
   if (valu) {
     if (part) LIP_ROUTE("dot_nt/valu/part"); else LIP_ROUTE("dot_nt/valu/atomic");
@@ -812,12 +802,7 @@ int lip_dot_nt_f64(const float* A, int64_t lda, int32_t m, const float* B, int64
     if (part) LIP_ROUTE("dot_nt/quad/part"); else LIP_ROUTE("dot_nt/quad/atomic");
     hipLaunchKernelGGL((dot_nt_f64_mfma_kernel<true>), dim3(blocks, (unsigned)ks4), dim3(256), 0, st, A, (long long)lda, m, B,
                        (long long)ldb, n, (long long)K, kper4, C, part);
-    LIP_CHECK_HIP(hipGetLastError());
-    if (part) {
-      hipLaunchKernelGGL(dot_nt_reduce_kernel, dim3((unsigned)(tiles * 16)), dim3(1024), 0, st, part, (int)tiles, (int)ks4, m, n, C);
-      LIP_CHECK_HIP(hipGetLastError());
-    }
-    return LIP_OK;
+    ks = ks4;                                          // (the partial tiles the reduction below adds)
   } else {
     if (part) LIP_ROUTE("dot_nt/tile/part"); else LIP_ROUTE("dot_nt/tile/atomic");
     hipLaunchKernelGGL((dot_nt_f64_mfma_kernel<false>), dim3((unsigned)tiles, (unsigned)ks), dim3(256), 0, st, A, (long long)lda, m, B,

@@ -1526,14 +1526,37 @@ __global__ __launch_bounds__(256) void igemm_first_kernel(const IgemmP prm, int 
 }
 
 // ------------------------------------------------------------------------------------------
-// process-wide state of the launchers: device zero page, CU count, scratch planes, tile override and the precision /
-// split-K / Winograd modes
+// process-wide state of the launchers: environment switches, device zero page, CU count, per-stream scratch and the
+// precision / split-K / Winograd modes
 // ------------------------------------------------------------------------------------------
+// The one place the environment is read (see Switches in lip_internal.h).
+const Switches& switches() {
+  static const Switches sw = [] {
+    auto set = [](const char* e) { return e != nullptr; };
+    auto first = [](const char* e, const char* letters) { return e && e[0] && strchr(letters, e[0]); };
+    auto num = [](const char* e, int dflt) { return e ? atoi(e) : dflt; };
+    Switches s;
+    s.precision_x3 = first(getenv("LIP_PRECISION"), "b1"); s.noksplit = set(getenv("LIP_NOKSPLIT"));
+    s.nowino = set(getenv("LIP_NOWINO")); s.wino_f = first(getenv("LIP_WINO"), "f");
+    s.generic = set(getenv("LIP_GENERIC")); s.nofirst = set(getenv("LIP_NOFIRST")); s.noskinny = set(getenv("LIP_NOSKINNY"));
+    s.nopb = set(getenv("LIP_NOPB")); s.nopb96 = set(getenv("LIP_NOPB96")); s.wgrad3 = set(getenv("LIP_WGRAD3"));
+    s.nopar = set(getenv("LIP_NOPAR")); s.nobv4 = set(getenv("LIP_NOBV4")); s.noadirect = set(getenv("LIP_NOADIRECT"));
+    s.wino_novepi = set(getenv("LIP_WINO_NOVEPI")); s.nosmallp = set(getenv("LIP_NOSMALLP"));
+    s.smallp_factor = num(getenv("LIP_SMALLP_FACTOR"), 2);       // 1..4 measured: +-3 %
+    s.wgw_minblocks = num(getenv("LIP_WGW_MINBLOCKS"), 2); s.tile = num(getenv("LIP_TILE"), -1);
+    s.dbg = set(getenv("LIP_DBG")); s.dot_nt_valu = set(getenv("LIP_DOT_NT_VALU")); s.dot_nt_noquad = set(getenv("LIP_DOT_NT_NOQUAD"));
+    return s;
+  }();
+  return sw;
+}
+
 // 256 bytes of device zeros (per device): the source of masked gather rows in the fast kernels.
 static const float* zero_page() {
   static float* pages[64] = {nullptr};
+  static std::mutex mu;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
   if (!pages[dev]) {
     float* ptr = nullptr;
     if (hipMalloc((void**)&ptr, 256) != hipSuccess) return nullptr;
@@ -1541,12 +1564,6 @@ static const float* zero_page() {
     pages[dev] = ptr;
   }
   return pages[dev];
-}
-
-static int tile_override() {
-  static int v = -2;
-  if (v == -2) { const char* e = getenv("LIP_TILE"); v = e ? atoi(e) : -1; }
-  return v;
 }
 
 static int cu_count() {
@@ -1560,68 +1577,48 @@ static int cu_count() {
   return n;
 }
 
-// Scratch planes of the split-K launches, one buffer per (device, stream) — kernels of one stream are ordered, so the
-// shares of launch i are consumed by its finishing pass before launch i+1 overwrites them; a second stream or device
-// gets its own buffer.  Grown on demand (after draining that stream), kept for the life of the process.  Returns null
-// when the table of 16 entries is full or the allocation fails (the caller then launches unsplit).
-static float* ksplit_scratch(size_t floats, hipStream_t st) {
-  struct Entry { int dev; hipStream_t st; float* buf; size_t cap; };
-  static Entry table[16];
-  static int used = 0;
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  Entry* e = nullptr;
-  for (int i = 0; i < used; ++i)
-    if (table[i].dev == dev && table[i].st == st) { e = &table[i]; break; }
-  if (!e) {
-    if (used == 16) return nullptr;
-    e = &table[used++];
-    e->dev = dev; e->st = st; e->buf = nullptr; e->cap = 0;
-  }
-  if (e->cap < floats) {
-    if (e->buf) { (void)hipStreamSynchronize(st); (void)hipFree(e->buf); e->buf = nullptr; e->cap = 0; }
-    if (hipMalloc((void**)&e->buf, floats * sizeof(float)) != hipSuccess) return nullptr;
-    e->cap = floats;
-  }
-  return e->buf;
+// Float scratch of one (device, stream), grown on demand (after draining that stream) and kept for the life of the
+// process.  It has three users, and a launch sequence uses it for ONE of them: the split-K planes of run_igemm (read by
+// igemm_finish_kernel), the transformed weights of run_igemm_wino (read by igemm_wino_kernel) and the transformed
+// activations of run_wgrad_wino (read by wgrad_wino_kernel).  Each writes the buffer and reads it back with kernels of
+// the same stream before it returns, and kernels of one stream are ordered, so the next user, whichever it is, cannot
+// overwrite data still in use; a second stream or device gets its own buffer.  Returns null when 16 other (device,
+// stream) pairs hold the records or the allocation fails: split-K then launches unsplit, Winograd falls to the direct kernels.
+static float* stream_scratch(size_t floats, hipStream_t st) {
+  struct Rec { float* buf; size_t cap; };
+  static PerStream<Rec> table;
+  return table.with(st, [&](Rec& r) -> float* {
+    if (r.cap < floats) {
+      if (r.buf) { (void)hipStreamSynchronize(st); (void)hipFree(r.buf); r.buf = nullptr; r.cap = 0; }
+      if (hipMalloc((void**)&r.buf, floats * sizeof(float)) != hipSuccess) return nullptr;
+      r.cap = floats;
+    }
+    return r.buf;
+  });
 }
 
-// 0: exact f32 MFMA (default); 1: split-precision bf16x3 operands (lip_set_precision / LIP_PRECISION=bf16x3)
+// The three modes with setters: -1 until the first setter call, and the environment's default (Switches) holds until then.
+// precision 0: exact f32 MFMA (default); 1: split-precision bf16x3 operands (lip_set_precision / LIP_PRECISION=bf16x3)
 static int g_precision = -1;
-int precision_mode() {
-  if (g_precision < 0) {
-    const char* e = getenv("LIP_PRECISION");
-    g_precision = (e && (e[0] == 'b' || e[0] == '1')) ? 1 : 0;
-  }
-  return g_precision;
-}
+int precision_mode() { return g_precision < 0 ? (switches().precision_x3 ? 1 : 0) : g_precision; }
 void set_precision_mode(int m) { g_precision = m ? 1 : 0; }
 
-// split-K of under-filled implicit GEMMs: -1 = not set (environment LIP_NOKSPLIT decides), 0 = off, 1 = on
+// split-K of under-filled implicit GEMMs: 0 = off, 1 = on (default; LIP_NOKSPLIT: off)
 static int g_split_k = -1;
 void set_split_k_mode(int on) { g_split_k = on ? 1 : 0; }
-static bool split_k_enabled() {
-  if (g_split_k < 0) g_split_k = getenv("LIP_NOKSPLIT") ? 0 : 1;
-  return g_split_k == 1;
-}
+static bool split_k_enabled() { return g_split_k < 0 ? !switches().noksplit : g_split_k == 1; }
 
-// Winograd route of the 3x3 / stride-1 layers: -1 = not set (environment: LIP_NOWINO -> off), 0 = off, 1 = on (default:
-// every eligible launch), 2 = on (kept for the tests that force the route; same launches as 1 since the fill rule went)
+// Winograd route of the 3x3 / stride-1 layers: 0 = off (LIP_NOWINO), 1 = on (default: every eligible launch), 2 = on
+// (LIP_WINO=f; kept for the tests that force the route; same launches as 1 since the fill rule went)
 static int g_wino = -1;
 void set_wino_mode(int m) { g_wino = (m < 0 || m > 2) ? 1 : m; }
 int wino_mode() {
-  if (g_wino < 0) {
-    const char* f = getenv("LIP_WINO");
-    g_wino = getenv("LIP_NOWINO") ? 0 : ((f && f[0] == 'f') ? 2 : 1);
-  }
-  return g_wino;
+  const Switches& sw = switches();
+  return g_wino < 0 ? (sw.nowino ? 0 : (sw.wino_f ? 2 : 1)) : g_wino;
 }
 
 static bool igemm_first_ok(const IgemmP& p, int P) {
-  static const bool off = getenv("LIP_NOFIRST") != nullptr || getenv("LIP_GENERIC") != nullptr;        // A/B switch
-  if (off || precision_mode() != 0 || p.nseg != 1 || P < 8) return false;
+  if (switches().nofirst || switches().generic || precision_mode() != 0 || p.nseg != 1 || P < 8) return false;
   const SegP& s = p.seg[0];
   return s.mode == 0 && s.Ktot <= 64 && (s.C & 15) != 0 && p.N == 32 && s.a_ps == 0 && !s.b_trans && !p.res && !p.red0 &&
          !p.red1 && (!p.e1 || p.xhat) && (long long)p.R * 32 < (1ll << 31);
@@ -2190,8 +2187,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 static bool wgrad_skinny_ok(const WgradP& p) {
-  static const bool off = getenv("LIP_NOSKINNY") != nullptr || getenv("LIP_GENERIC") != nullptr;       // A/B switch
-  return !off && precision_mode() == 0 && p.seg_rows == 0 && p.ksplit <= 1 && p.R <= 64 && p.OHW == 1 && p.pad_h == 0 &&
+  return !switches().noskinny && !switches().generic && precision_mode() == 0 && p.seg_rows == 0 && p.ksplit <= 1 && p.R <= 64 && p.OHW == 1 && p.pad_h == 0 &&
          p.pad_w == 0 && p.KH == p.IH && p.KW == p.IW && (long long)p.R * p.M < (1ll << 31) && p.M >= 32 && p.N <= (1 << 20);
 }
 
@@ -2298,8 +2294,7 @@ __global__ __launch_bounds__(256) void wgrad_first_kernel(const WgradP prm, int 
 }
 
 static bool wgrad_first_ok(const WgradP& p, int P) {
-  static const bool off = getenv("LIP_NOFIRST") != nullptr || getenv("LIP_GENERIC") != nullptr;        // A/B switch
-  return !off && precision_mode() == 0 && p.seg_rows == 0 && p.ksplit <= 0 && p.M <= 32 && p.N <= 32 && (p.C & 3) != 0 &&
+  return !switches().nofirst && !switches().generic && precision_mode() == 0 && p.seg_rows == 0 && p.ksplit <= 0 && p.M <= 32 && p.N <= 32 && (p.C & 3) != 0 &&
          p.R >= 2048 && P >= 8 && (long long)p.R * p.N < (1ll << 31);
 }
 
@@ -2501,12 +2496,10 @@ static bool wgrad_wino_ok(const WgradP& p, int P) {
   const int OH = p.OHW / p.OW;
   if (OH != p.IH || p.OW != p.IW || (OH & 1) || (p.OW & 1) != 0) return false;
   if ((long long)p.R * p.N * 4 >= (1ll << 31)) return false;
-  {   // ONE (probe, c tile, n tile) block (a single product on the 32-channel stage): its 12 800 tiles would be split 64 ways
-    // and added with 64-fold contended float atomics — the direct kernel's own row split is faster there (47 vs 31 us;
-    // single product 1.82 -> 1.77 ms).  Two blocks already favour this kernel (2.17 vs 2.60 ms for two products).
-    static const int minb = getenv("LIP_WGW_MINBLOCKS") ? atoi(getenv("LIP_WGW_MINBLOCKS")) : 2;     // A/B switch
-    if ((long long)(p.C / 32) * (p.N / 32) * P < minb) return false;
-  }
+  // ONE (probe, c tile, n tile) block (a single product on the 32-channel stage): its 12 800 tiles would be split 64 ways
+  // and added with 64-fold contended float atomics — the direct kernel's own row split is faster there (47 vs 31 us;
+  // single product 1.82 -> 1.77 ms).  Two blocks already favour this kernel (2.17 vs 2.60 ms for two products).
+  if ((long long)(p.C / 32) * (p.N / 32) * P < switches().wgw_minblocks) return false;
   const long long T = p.R / 4;
   if (16ll * (T + 16ll * 64) * p.C * 4 >= (1ll << 31)) return false;
   return true;
@@ -2524,7 +2517,7 @@ static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st) {
   q.dTPI = FastDiv((unsigned)q.tpi); q.dTW = FastDiv((unsigned)TW);
   q.H = OH; q.W = p.OW; q.C = p.C; q.N = p.N;
   const size_t vfloats = (size_t)16 * q.TQ * p.C * 4;
-  float* vt = ksplit_scratch(vfloats, st);
+  float* vt = stream_scratch(vfloats, st);
   if (!vt) return hipErrorOutOfMemory;
   q.vt = vt; q.vt_bytes = (unsigned)(vfloats * 4);
   q.g = p.g; q.g_ps = p.g_ps; q.g_bytes = (unsigned)((long long)p.R * p.N * 4);
@@ -2541,8 +2534,9 @@ static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st) {
     attr_set = true;
   }
   const dim3 grid((unsigned)((p.C / 32) * (p.N / 32) * S), (unsigned)P);
-  if ((TW & 3) == 0) { LIP_ROUTE("wgrad_wino/rowq"); hipLaunchKernelGGL(wgrad_wino_kernel<true>, grid, dim3(256), shmem, st, q); }
-  else { LIP_ROUTE("wgrad_wino"); hipLaunchKernelGGL(wgrad_wino_kernel<false>, grid, dim3(256), shmem, st, q); }
+  with_flag((TW & 3) == 0, [&](auto rowq) {
+    LIP_ROUTE("wgrad_wino%s", rowq ? "/rowq" : ""); hipLaunchKernelGGL(wgrad_wino_kernel<rowq>, grid, dim3(256), shmem, st, q);
+  });
   return hipGetLastError();
 }
 
@@ -2917,117 +2911,117 @@ static bool igemm_fast_ok(const IgemmP& p) {
   return true;
 }
 
+// LIP_DBG: igemm_fast_kernel stamps its start, the end of its K loop and its end into IgemmP::dbg (3 words per block);
+// the launcher drains the stream and reports the means on stderr, 60 times per tile shape at the most.
+struct IgemmDbg { unsigned long long* buf = nullptr; int reports = 0; };
+constexpr size_t kDbgBytes = 3 * 8192 * sizeof(unsigned long long);
+
+static unsigned long long* igemm_dbg_begin(IgemmDbg& d, hipStream_t st) {
+  if (!d.buf && hipMalloc((void**)&d.buf, kDbgBytes) != hipSuccess) return nullptr;
+  (void)hipMemsetAsync(d.buf, 0, kDbgBytes, st);
+  return d.buf;
+}
+
+static void igemm_dbg_report(IgemmDbg& d, int WM, int WN, int TM, int TN, long long blocks, const IgemmP& p, hipStream_t st) {
+  if (d.reports >= 60) return;
+  ++d.reports;
+  (void)hipStreamSynchronize(st);
+  static unsigned long long host[kDbgBytes / sizeof(unsigned long long)];
+  (void)hipMemcpy(host, d.buf, kDbgBytes, hipMemcpyDeviceToHost);
+  double loop = 0, epi = 0; long long cnt = 0;
+  for (long long b = 0; b < (blocks < 8192 ? blocks : 8192); ++b) {
+    if (!host[3 * b + 2]) continue;
+    loop += (double)(host[3 * b + 1] - host[3 * b]); epi += (double)(host[3 * b + 2] - host[3 * b + 1]);
+    ++cnt;
+  }
+  if (cnt) fprintf(stderr, "[lip dbg] igemm<%d,%d,%d,%d> split=%d blocks=%lld (of %lld) nseg=%d N=%d: K-loop %.0f cycles, epilogue+drain %.0f cycles per block\n",
+                   WM, WN, TM, TN, precision_mode(), cnt, blocks, p.nseg, p.N, loop / cnt, epi / cnt);
+}
+
 template <int WM, int WN, int TM, int TN>
 static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
   using T = Tile<WM, WN, TM, TN>;
+  const Switches& sw = switches();
   const long long tiles = (long long)((p.R + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN);
   dim3 grid((unsigned)tiles, (unsigned)P, 1);
-  static const bool force_generic = getenv("LIP_GENERIC") != nullptr;     // A/B switch
-  if (!force_generic && igemm_fast_ok(p)) {
-    IgemmP q = p;
-    q.zeros = zero_page();
-    if (!q.zeros) return hipErrorOutOfMemory;
-    static const bool dbg = getenv("LIP_DBG") != nullptr;       // diagnostic stamps (never in a timed run)
-    static unsigned long long* dbgbuf = nullptr;
-    q.dbg = nullptr;
-
-    if (dbg) {
-      if (!dbgbuf && hipMalloc((void**)&dbgbuf, 3 * 8192 * sizeof(unsigned long long)) != hipSuccess) return hipErrorOutOfMemory;
-      (void)hipMemsetAsync(dbgbuf, 0, 3 * 8192 * sizeof(unsigned long long), st);
-      q.dbg = dbgbuf;
-    }
-    // stride-2 data gradient on an even grid: parity-class row order, unreachable taps skipped (A/B: LIP_NOPAR)
-    static const bool nopar = getenv("LIP_NOPAR") != nullptr;
-    const int OH = p.OHW / p.OW;
-    bool par = !nopar && (OH % 2 == 0) && (p.OW % 2 == 0), any_s2 = false;
-    for (int s = 0; s < p.nseg; ++s) {
-      par = par && p.seg[s].mode == 1 && (p.seg[s].stride == 1 || p.seg[s].stride == 2);
-      any_s2 = any_s2 || (p.seg[s].mode == 1 && p.seg[s].stride == 2);
-    }
-    par = par && any_s2;
-    // B as dwordx4 when N % 4 == 0, on the tiles of 64+ columns (A/B switch LIP_NOBV4; measured per op at P = 256:
-    // N = 128 forward 117.5 -> 128.1 TF, N = 64 forward 111.5 -> 119, backward +2..7 %; the 32-column tile, where only
-    // half the threads would carry a B load, lost 5 % and keeps dword loads)
-    static const bool nobv4 = getenv("LIP_NOBV4") != nullptr;
-    const bool split = precision_mode() == 1;      // (split mode: 2081 -> 1820 GGN-vp/s with dwordx4 B loads — off)
-    const bool bv4 = !nobv4 && !split && (p.N & 3) == 0;
-    if (par) {
-      q.OW2 = p.OW / 2; q.OHW2 = (OH / 2) * q.OW2; q.Rc = (p.R / p.OHW) * q.OHW2;
-      q.dOHW2 = FastDiv((unsigned)q.OHW2); q.dOW2 = FastDiv((unsigned)q.OW2);
-      grid.x = (unsigned)(4ll * ((q.Rc + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN));
-    }
-    // few probes: fewer blocks than the chip holds and a long K loop — split the K-tiles over gridDim.z (each share
-    // >= 12 K-tiles, <= 4 shares; only where the chip is at most half full: at 200 blocks — the 64-column stage at one probe —
-    // the second pass costs more than the shorter K loop saves, 37 -> 40 us per launch), raw sums to a scratch plane per share, igemm_finish_kernel adds them
-    // and runs the fused epilogue (a fix-up inside the kernel by the share that arrives last at a tile counter needs
-    // agent-scope fences: 38 -> 80 us per launch, measured).  A/B switch LIP_NOKSPLIT.
-    if constexpr (WM == 2 && TM == 1 && TN == 1) {
-      const bool noks = !split_k_enabled();
-      int kt = 0;
-      for (int s = 0; s < p.nseg; ++s) kt += p.seg[s].Ktot / BK;
-      const long long blocks = tiles * P;
-      long long ks = (4ll * cu_count()) / (blocks > 0 ? blocks : 1);
-      if (ks > kt / 12) ks = kt / 12;
-      if (ks > 4) ks = 4;
-      const size_t plane = (size_t)P * p.R * p.N;
-      if (!noks && !p.no_ksplit && !split && !par && !dbg && ks >= 2 && 2 * blocks <= cu_count() && plane * ks * sizeof(float) <= ((size_t)256 << 20)) {
-        // per (device, stream): launches of one stream are ordered.  Split-K is only an optimisation: when the scratch
-        // table is full (a process rotating through many streams) or the allocation fails, the launch below runs unsplit
-        float* scratch = ksplit_scratch(plane * ks, st);
-        if (scratch) {
-          q.partial = scratch; q.partial_zs = (long long)plane;
-          dim3 g3((unsigned)tiles, (unsigned)P, (unsigned)ks);
-          if (bv4) { LIP_ROUTE("igemm_fast<%d,%d,%d,%d>/ks/bv4", WM, WN, TM, TN); hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, false, false, true, true>), g3, dim3(T::NT), 0, st, q); }
-          else { LIP_ROUTE("igemm_fast<%d,%d,%d,%d>/ks", WM, WN, TM, TN); hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, false, false, false, true>), g3, dim3(T::NT), 0, st, q); }
-          hipLaunchKernelGGL((igemm_finish_kernel<WM, WN, TM, TN>), grid, dim3(T::NT), 0, st, q, (int)ks);
-          return hipGetLastError();
-        }
-      }
-    }
-    if constexpr (WM == 4 && WN == 1) {
-      // A operand straight into the MFMA registers (A/B switch LIP_NOADIRECT)
-      static const bool noad = getenv("LIP_NOADIRECT") != nullptr;
-      if (!noad && !split && !par && !dbg) {
-        if (bv4) { LIP_ROUTE("igemm_adirect<%d,%d,%d,%d>/bv4", WM, WN, TM, TN); hipLaunchKernelGGL((igemm_adirect_kernel<TM, TN, true>), grid, dim3(256), 0, st, q); }
-        else { LIP_ROUTE("igemm_adirect<%d,%d,%d,%d>", WM, WN, TM, TN); hipLaunchKernelGGL((igemm_adirect_kernel<TM, TN, false>), grid, dim3(256), 0, st, q); }
-        return hipGetLastError();
-      }
-    }
-#define LIP_LAUNCH_IGEMM(S_, P_, V_)                                                                                   \
-  do {                                                                                                                 \
-    LIP_ROUTE("igemm_fast<%d,%d,%d,%d>%s%s%s", WM, WN, TM, TN, S_ ? "/x3" : "", P_ ? "/par" : "", V_ ? "/bv4" : "");  \
-    hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, S_, P_, V_>), grid, dim3(T::NT), 0, st, q);                  \
-  } while (0)
-    if (split) {
-      if (par) LIP_LAUNCH_IGEMM(true, true, false); else LIP_LAUNCH_IGEMM(true, false, false);
-    } else {
-      if (par) { if (bv4) LIP_LAUNCH_IGEMM(false, true, true); else LIP_LAUNCH_IGEMM(false, true, false); }
-      else { if (bv4) LIP_LAUNCH_IGEMM(false, false, true); else LIP_LAUNCH_IGEMM(false, false, false); }
-    }
-#undef LIP_LAUNCH_IGEMM
-    if (dbg) {
-      static int reports = 0;
-      if (reports < 60) {
-        (void)hipStreamSynchronize(st);
-        static unsigned long long host[3 * 8192];
-        (void)hipMemcpy(host, dbgbuf, sizeof(host), hipMemcpyDeviceToHost);
-        const long long nb = (long long)tiles * P < 8192 ? (long long)tiles * P : 8192;
-        double loop = 0, epi = 0; long long cnt = 0;
-        for (long long b = 0; b < nb; ++b) {
-          if (!host[3 * b + 2]) continue;
-          loop += (double)(host[3 * b + 1] - host[3 * b]); epi += (double)(host[3 * b + 2] - host[3 * b + 1]);
-          ++cnt;
-        }
-        if (cnt) fprintf(stderr, "[lip dbg] igemm<%d,%d,%d,%d> split=%d blocks=%lld (of %lld) nseg=%d N=%d: K-loop %.0f cycles, epilogue+drain %.0f cycles per block\n",
-                         WM, WN, TM, TN, precision_mode(), cnt, (long long)tiles * P, p.nseg, p.N, loop / cnt, epi / cnt);
-        ++reports;
-      }
-    }
-  }
-  else {
+  if (sw.generic || !igemm_fast_ok(p)) {
     LIP_ROUTE("igemm<%d,%d,%d,%d>", WM, WN, TM, TN);
     hipLaunchKernelGGL((igemm_kernel<WM, WN, TM, TN>), grid, dim3(T::NT), 0, st, p);
+    return hipGetLastError();
   }
+  // ---- the decision: which of the fast kernels, with which flags ----
+  const bool split = precision_mode() == 1;      // bf16x3 operands
+  // stride-2 data gradient on an even grid: parity-class row order, unreachable taps skipped (A/B: LIP_NOPAR)
+  const int OH = p.OHW / p.OW;
+  bool par = !sw.nopar && (OH % 2 == 0) && (p.OW % 2 == 0), any_s2 = false;
+  for (int s = 0; s < p.nseg; ++s) {
+    par = par && p.seg[s].mode == 1 && (p.seg[s].stride == 1 || p.seg[s].stride == 2);
+    any_s2 = any_s2 || (p.seg[s].mode == 1 && p.seg[s].stride == 2);
+  }
+  par = par && any_s2;
+  // B as dwordx4 when N % 4 == 0, on the tiles of 64+ columns (A/B switch LIP_NOBV4; measured per op at P = 256:
+  // N = 128 forward 117.5 -> 128.1 TF, N = 64 forward 111.5 -> 119, backward +2..7 %; the 32-column tile, where only
+  // half the threads would carry a B load, lost 5 % and keeps dword loads; split mode: 2081 -> 1820 GGN-vp/s — off)
+  const bool bv4 = !sw.nobv4 && !split && (p.N & 3) == 0;
+  const bool plain = !split && !par && !sw.dbg;    // what the split-K and the A-direct kernels serve
+  // few probes: fewer blocks than the chip holds and a long K loop — split the K-tiles over gridDim.z (each share
+  // >= 12 K-tiles, <= 4 shares; only where the chip is at most half full: at 200 blocks — the 64-column stage at one probe —
+  // the second pass costs more than the shorter K loop saves, 37 -> 40 us per launch), raw sums to a scratch plane per share, igemm_finish_kernel adds them
+  // and runs the fused epilogue (a fix-up inside the kernel by the share that arrives last at a tile counter needs
+  // agent-scope fences: 38 -> 80 us per launch, measured).  A/B switch LIP_NOKSPLIT.
+  constexpr bool KS_TILE = WM == 2 && TM == 1 && TN == 1;
+  const size_t plane = (size_t)P * p.R * p.N;
+  long long ks = 1;                                // split-K shares
+  if (KS_TILE && plain && split_k_enabled() && !p.no_ksplit && 2 * tiles * P <= cu_count()) {
+    int kt = 0;
+    for (int s = 0; s < p.nseg; ++s) kt += p.seg[s].Ktot / BK;
+    ks = (4ll * cu_count()) / (tiles * P > 0 ? tiles * P : 1);
+    if (ks > kt / 12) ks = kt / 12;
+    if (ks > 4) ks = 4;
+    if (ks < 2 || plane * ks * sizeof(float) > ((size_t)256 << 20)) ks = 1;
+  }
+  // A operand straight into the MFMA registers (A/B switch LIP_NOADIRECT)
+  constexpr bool AD_TILE = WM == 4 && WN == 1;
+  const bool adirect = AD_TILE && plain && !sw.noadirect;
+  // ---- the launch ----
+  IgemmP q = p;
+  q.zeros = zero_page();
+  if (!q.zeros) return hipErrorOutOfMemory;
+  static IgemmDbg dbg;                             // (per tile shape)
+  q.dbg = sw.dbg ? igemm_dbg_begin(dbg, st) : nullptr;
+  if (sw.dbg && !q.dbg) return hipErrorOutOfMemory;
+  if (par) {
+    q.OW2 = p.OW / 2; q.OHW2 = (OH / 2) * q.OW2; q.Rc = (p.R / p.OHW) * q.OHW2;
+    q.dOHW2 = FastDiv((unsigned)q.OHW2); q.dOW2 = FastDiv((unsigned)q.OW2);
+    grid.x = (unsigned)(4ll * ((q.Rc + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN));
+  }
+  if constexpr (KS_TILE) {
+    // (split-K is only an optimisation: without scratch — a 17th stream, a failed allocation — the launch below runs unsplit)
+    float* scratch = ks >= 2 ? stream_scratch(plane * ks, st) : nullptr;
+    if (scratch) {
+      q.partial = scratch; q.partial_zs = (long long)plane;
+      const dim3 g3((unsigned)tiles, (unsigned)P, (unsigned)ks);
+      with_flag(bv4, [&](auto v) {
+        LIP_ROUTE("igemm_fast<%d,%d,%d,%d>/ks%s", WM, WN, TM, TN, v ? "/bv4" : ""); hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, false, false, v, true>), g3, dim3(T::NT), 0, st, q);
+      });
+      hipLaunchKernelGGL((igemm_finish_kernel<WM, WN, TM, TN>), grid, dim3(T::NT), 0, st, q, (int)ks);
+      return hipGetLastError();
+    }
+  }
+  if constexpr (AD_TILE) {
+    if (adirect) return with_flag(bv4, [&](auto v) {
+      LIP_ROUTE("igemm_adirect<%d,%d,%d,%d>%s", WM, WN, TM, TN, v ? "/bv4" : ""); hipLaunchKernelGGL((igemm_adirect_kernel<TM, TN, v>), grid, dim3(256), 0, st, q);
+      return hipGetLastError();
+    });
+  }
+  with_flag(split, [&](auto s) { with_flag(par, [&](auto pr) { with_flag(bv4, [&](auto v) {
+    constexpr bool S = decltype(s)::value, PR = decltype(pr)::value;
+    if constexpr (!(S && v)) {                     // (the split-precision loader has no dwordx4 form)
+      LIP_ROUTE("igemm_fast<%d,%d,%d,%d>%s%s%s", WM, WN, TM, TN, S ? "/x3" : "", PR ? "/par" : "", v ? "/bv4" : "");
+      hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, S, PR, v>), grid, dim3(T::NT), 0, st, q);
+    }
+  }); }); });
+  if (sw.dbg) igemm_dbg_report(dbg, WM, WN, TM, TN, tiles * P, p, st);
   return hipGetLastError();
 }
 
@@ -3048,22 +3042,21 @@ static WinoGeom wino_geom(int OH, int OW, long long n_img) {
 // that first launches the geometry — the kernels of a stream are ordered, so the fill precedes every reader, with no
 // event, no host synchronisation and nothing shared between two streams that meet a geometry at the same time.  A
 // binding's geometries never change, so the steady state is a look-up.  Kept for the life of the process.  Returns null
-// when the allocation or the fill fails (the caller then leaves the Winograd route).
+// when the allocation or the fill fails, or 16 other (device, stream) pairs hold the records — which cannot happen after
+// run_igemm_wino got that stream's scratch from a table of the same size (the caller then leaves the Winograd route).
 static const i32x4v* wino_table(const WinoGeom& g, int H, int W, hipStream_t st) {
-  struct Entry { int dev; hipStream_t st; int BWs, BHs, H, W; int* tab; };
-  static std::vector<Entry> table;
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  for (const Entry& e : table)      // (NI, FR, FC and NS follow from BWs and BHs)
-    if (e.dev == dev && e.st == st && e.BWs == g.BWs && e.BHs == g.BHs && e.H == H && e.W == W) return reinterpret_cast<const i32x4v*>(e.tab);
-  int* tab = nullptr;
-  if (hipMalloc((void**)&tab, WINO_TAB_INTS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  hipLaunchKernelGGL(wino_table_kernel, dim3(1), dim3(256), 0, st, tab, g.BWs, g.BHs, g.FR, g.FC, g.NS, H, W);
-  if (hipGetLastError() != hipSuccess) { (void)hipFree(tab); return nullptr; }
-  table.push_back(Entry{dev, st, g.BWs, g.BHs, H, W, tab});
-  return reinterpret_cast<const i32x4v*>(tab);
+  struct Geom { int BWs, BHs, H, W; int* tab; };      // (NI, FR, FC and NS follow from BWs and BHs)
+  static PerStream<std::vector<Geom>> table;
+  return table.with(st, [&](std::vector<Geom>& geoms) -> const i32x4v* {
+    for (const Geom& e : geoms)
+      if (e.BWs == g.BWs && e.BHs == g.BHs && e.H == H && e.W == W) return reinterpret_cast<const i32x4v*>(e.tab);
+    int* tab = nullptr;
+    if (hipMalloc((void**)&tab, WINO_TAB_INTS * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    hipLaunchKernelGGL(wino_table_kernel, dim3(1), dim3(256), 0, st, tab, g.BWs, g.BHs, g.FR, g.FC, g.NS, H, W);
+    if (hipGetLastError() != hipSuccess) { (void)hipFree(tab); return nullptr; }
+    geoms.push_back(Geom{g.BWs, g.BHs, H, W, tab});
+    return reinterpret_cast<const i32x4v*>(tab);
+  });
 }
 
 static bool igemm_wino_ok(const IgemmP& p, int P) {
@@ -3096,7 +3089,7 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st) {
   const long long n_img = p.R / p.OHW;
   size_t need = 0;
   for (int s = 0; s < p.nseg; ++s) need += (size_t)(p.seg[s].b_ps ? P : 1) * 16 * p.seg[s].C * p.N;
-  float* scratch = ksplit_scratch(need, st);
+  float* scratch = stream_scratch(need, st);
   if (!scratch) return hipErrorOutOfMemory;
   size_t off = 0;
   for (int s = 0; s < p.nseg; ++s) {
@@ -3131,11 +3124,11 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st) {
   }
   // 16-byte epilogue accesses when every operand tensor allows them (A/B switch LIP_WINO_NOVEPI)
   auto al16 = [](const void* ptr, long long ps) { return ptr == nullptr || ((((uintptr_t)ptr) & 15) == 0 && (ps & 3) == 0); };
-  static const bool novepi = getenv("LIP_WINO_NOVEPI") != nullptr;
-  const bool vepi = !novepi && al16(p.out, p.out_ps) && al16(p.res, p.res_ps) && al16(p.xhat, 0) && al16(p.dphi, 0) && al16(p.xhat2, 0);
+  const bool vepi = !switches().wino_novepi && al16(p.out, p.out_ps) && al16(p.res, p.res_ps) && al16(p.xhat, 0) && al16(p.dphi, 0) && al16(p.xhat2, 0);
   dim3 grid((unsigned)gx, (unsigned)P, 1);
-  if (vepi) { LIP_ROUTE("igemm_wino/vepi"); hipLaunchKernelGGL(igemm_wino_kernel<true>, grid, dim3(256), shmem, st, q, wx); }
-  else { LIP_ROUTE("igemm_wino"); hipLaunchKernelGGL(igemm_wino_kernel<false>, grid, dim3(256), shmem, st, q, wx); }
+  with_flag(vepi, [&](auto v) {
+    LIP_ROUTE("igemm_wino%s", v ? "/vepi" : ""); hipLaunchKernelGGL(igemm_wino_kernel<v>, grid, dim3(256), shmem, st, q, wx);
+  });
   return hipGetLastError();
 }
 
@@ -3150,20 +3143,19 @@ hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st) {
   // Few probes (single-vector Krylov loops): with fewer 128-row blocks than CUs the launch time is ONE block's K loop,
   // so take the tiles with the least work per wave (32x32 per wave, 64-row blocks) — at P = 1 the 128-channel layers
   // of the CIFAR net run 25 blocks of 144 K-tiles otherwise (measured 177 us per launch).  A/B switch LIP_NOSMALLP.
-  static const bool nosmallp = getenv("LIP_NOSMALLP") != nullptr;
   const long long blocks128 = (long long)((p.R + 127) / 128) * ((p.N + (p.N > 64 ? 127 : (p.N > 32 ? 63 : 31))) / (p.N > 64 ? 128 : (p.N > 32 ? 64 : 32))) * P;
-  static const int smallp_factor = getenv("LIP_SMALLP_FACTOR") ? atoi(getenv("LIP_SMALLP_FACTOR")) : 2;   // 1..4 measured: +-3 %
-  if (!nosmallp && p.R > 64 && blocks128 < (long long)smallp_factor * cu_count()) {
+  if (!switches().nosmallp && p.R > 64 && blocks128 < (long long)switches().smallp_factor * cu_count()) {
     if (p.N > 32) return run_igemm<2, 2, 1, 1>(p, P, st);
     return run_igemm<2, 1, 1, 1>(p, P, st);
   }
   // experiment switches (A/B only): LIP_TILE=2 one-wave blocks (32 x 32 / 32 x 64 per block, no cross-wave barrier),
   // LIP_TILE=3 one wave with two row tiles (64 x 32), LIP_TILE=4 two-wave 64-row blocks
-  if (tile_override() == 2 && p.N <= 64) return p.N > 32 ? run_igemm<1, 1, 1, 2>(p, P, st) : run_igemm<1, 1, 1, 1>(p, P, st);
-  if (tile_override() == 3 && p.N <= 32) return run_igemm<1, 1, 2, 1>(p, P, st);
-  if (tile_override() == 4 && p.N <= 32) return run_igemm<2, 1, 1, 1>(p, P, st);
+  const int tile = switches().tile;
+  if (tile == 2 && p.N <= 64) return p.N > 32 ? run_igemm<1, 1, 1, 2>(p, P, st) : run_igemm<1, 1, 1, 1>(p, P, st);
+  if (tile == 3 && p.N <= 32) return run_igemm<1, 1, 2, 1>(p, P, st);
+  if (tile == 4 && p.N <= 32) return run_igemm<2, 1, 1, 1>(p, P, st);
   const bool small_m = p.R <= 64;
-  const bool big_m = p.R >= 4096 && tile_override() == 1;    // LIP_TILE=1: 256-row tiles (A/B: slower on every shape, r1 and r2)
+  const bool big_m = p.R >= 4096 && tile == 1;    // LIP_TILE=1: 256-row tiles (A/B: slower on every shape, r1 and r2)
   if (p.N > 64) return small_m ? run_igemm<2, 2, 1, 2>(p, P, st) : run_igemm<2, 2, 2, 2>(p, P, st);
   if (p.N > 32) return small_m ? run_igemm<2, 2, 1, 1>(p, P, st) : (big_m ? run_igemm<4, 1, 2, 2>(p, P, st) : run_igemm<4, 1, 1, 2>(p, P, st));
   return small_m ? run_igemm<2, 1, 1, 1>(p, P, st) : (big_m ? run_igemm<4, 1, 2, 1>(p, P, st) : run_igemm<4, 1, 1, 1>(p, P, st));
@@ -3229,28 +3221,21 @@ static hipError_t run_wgrad(Tile<WM, WN, TM, TN>, const WgradP& p0, int P, hipSt
   WgradP p = p0;
   if (p.ksplit <= 0) p.ksplit = auto_ksplit(tiles * P, TM * TN >= 4 ? 2 : (TM * TN == 2 ? 3 : 4), p.R, T::BM * T::BN, 8 * TM * TN);
   dim3 grid((unsigned)tiles, (unsigned)P, (unsigned)p.ksplit);
-  static const bool force_generic = getenv("LIP_GENERIC") != nullptr;     // A/B switch
-  if (!force_generic && (p.C & 3) == 0 && (((uintptr_t)p.a) & 15) == 0) {
+  if (!switches().generic && (p.C & 3) == 0 && (((uintptr_t)p.a) & 15) == 0) {
     WgradP q = p;
     q.zeros = zero_page();
     if (!q.zeros) return hipErrorOutOfMemory;
-    // cotangent rows as float4 on the 64+ column tiles (N % 4 == 0, 16-byte aligned slot; A/B switch LIP_NOBV4)
-    static const bool nobv4 = getenv("LIP_NOBV4") != nullptr;
+    // cotangent rows as float4 (N % 4 == 0, 16-byte aligned slot): in split precision (bf16x3 operands) on every tile
+    // width whose loader has the form, else on the 64+ column tiles (A/B switch LIP_NOBV4)
     const bool v4 = (p.N & 3) == 0 && (p.g_ps & 3) == 0 && (((uintptr_t)p.g) & 15) == 0;
-    if constexpr (T::AQ == 2) {
-      if (precision_mode() == 1 && v4) {              // split precision (bf16x3 operands), every tile width
-        LIP_ROUTE("wgrad_fast<%d,%d,%d,%d>/x3", WM, WN, TM, TN);
-        hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, false, true, true>), grid, dim3(T::NT), 0, st, q);
-        return hipGetLastError();
+    const bool x3 = T::AQ == 2 && precision_mode() == 1 && v4;
+    with_flag(x3, [&](auto s) { with_flag(x3 || (!switches().nobv4 && T::BN >= 64 && v4), [&](auto b) {
+      constexpr bool S = decltype(s)::value;
+      if constexpr (!S || (b && T::AQ == 2)) {
+        LIP_ROUTE("wgrad_fast<%d,%d,%d,%d>%s", WM, WN, TM, TN, S ? "/x3" : (b ? "/v4" : ""));
+        hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, false, b, S>), grid, dim3(T::NT), 0, st, q);
       }
-    }
-    if (!nobv4 && T::BN >= 64 && v4) {
-      LIP_ROUTE("wgrad_fast<%d,%d,%d,%d>/v4", WM, WN, TM, TN);
-      hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, false, true>), grid, dim3(T::NT), 0, st, q);
-    } else {
-      LIP_ROUTE("wgrad_fast<%d,%d,%d,%d>", WM, WN, TM, TN);
-      hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, false, false>), grid, dim3(T::NT), 0, st, q);
-    }
+    }); });
   }
   else {
     LIP_ROUTE("wgrad<%d,%d,%d,%d>", WM, WN, TM, TN);
@@ -3279,15 +3264,13 @@ static hipError_t run_wgrad_pb(const WgradP& p, int P, hipStream_t st) {
     q.ksplit = ks < 1 ? 1 : (int)ks;
   }
   dim3 grid((unsigned)tiles, 1, (unsigned)q.ksplit);
-  if constexpr (T::NT % (T::BM / 4) == 0) {        // (the split-precision loader needs one m-quad per thread)
-    if (precision_mode() == 1) {
-      LIP_ROUTE("wgrad_pb<%d,%d,%d,%d>/x3", WM, WN, TM, TN);
-      hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, true, true, true>), grid, dim3(T::NT), 0, st, q);
-      return hipGetLastError();
+  constexpr bool X3_TILE = T::NT % (T::BM / 4) == 0;        // (the split-precision loader needs one m-quad per thread)
+  with_flag(X3_TILE && precision_mode() == 1, [&](auto s) {
+    if constexpr (!s || X3_TILE) {
+      LIP_ROUTE("wgrad_pb<%d,%d,%d,%d>%s", WM, WN, TM, TN, s ? "/x3" : "");
+      hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, true, true, s>), grid, dim3(T::NT), 0, st, q);
     }
-  }
-  LIP_ROUTE("wgrad_pb<%d,%d,%d,%d>", WM, WN, TM, TN);
-  hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, true>), grid, dim3(T::NT), 0, st, q);
+  });
   return hipGetLastError();
 }
 
@@ -3304,20 +3287,18 @@ hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st) {
     (void)hipGetLastError();
   }
   if (p.overwrite) return hipErrorInvalidValue;       // the engine asks for it only where wgrad_will_overwrite() holds
-  static const bool nopb = getenv("LIP_NOPB") != nullptr || getenv("LIP_GENERIC") != nullptr;   // A/B switch
-  const bool pb_ok = !nopb && P > 1 && p.N <= 64 && (p.N & 3) == 0 && p.M >= 96 && (p.g_ps & 3) == 0 && (((uintptr_t)p.g) & 15) == 0 && (p.C & 3) == 0 && (((uintptr_t)p.a) & 15) == 0 &&
+  const Switches& sw = switches();
+  const bool pb_ok = !sw.nopb && !sw.generic && P > 1 && p.N <= 64 && (p.N & 3) == 0 && p.M >= 96 && (p.g_ps & 3) == 0 && (((uintptr_t)p.g) & 15) == 0 && (p.C & 3) == 0 && (((uintptr_t)p.a) & 15) == 0 &&
                      (long long)(P - 1) * p.g_ps + (long long)p.R * p.N < (1ll << 32);
   // measured on MI355X (CIFAR ResNet1M, P = 256): N = 32, M = 288: 3.72 -> 2.67 ms; N = 64, M = 288: 1.58 -> 1.36 ms;
   // N = 64, M = 576 with 128-row tiles (11 % padded rows): 2.61 -> 2.68 ms — that case takes the 96-row tile below
   const int waste128 = (p.M + 127) / 128 * 128 - p.M;
-  static const bool pb96 = getenv("LIP_NOPB96") == nullptr;     // A/B: 96-row probe-batched tile also for N = 64, M = 576
-  if (pb_ok && (p.N <= 32 || 5 * waste128 >= p.M || (pb96 && p.M % 96 == 0 && p.M % 128 != 0))) {
+  if (pb_ok && (p.N <= 32 || 5 * waste128 >= p.M || (!sw.nopb96 && p.M % 96 == 0 && p.M % 128 != 0))) {
     // 96-row tiles for M = 288 / 576: four waves side by side along the probes' columns (each wave 96 x 32 = one
     // probe's channels) — the three-wave form <3,1,1,4> (208 registers: two blocks of three waves per CU) put 2-2-1-1
     // waves on the four SIMDs; it stays for the split-precision mode, whose row-pair loader needs one m-quad per thread
-    static const bool w3 = getenv("LIP_WGRAD3") != nullptr;          // A/B switch
     if (p.M % 96 == 0 && p.M % 128 != 0)
-      return (precision_mode() == 1 || w3) ? run_wgrad_pb<3, 1, 1, 4>(p, P, st) : run_wgrad_pb<1, 4, 3, 1>(p, P, st);
+      return (precision_mode() == 1 || sw.wgrad3) ? run_wgrad_pb<3, 1, 1, 4>(p, P, st) : run_wgrad_pb<1, 4, 3, 1>(p, P, st);
     return run_wgrad_pb<2, 2, 2, 2>(p, P, st);
   }
   // (64-row per-probe tiles for M = 288 were measured slower than 128-row ones: 54.6 vs 52.4 ms per step — removed;

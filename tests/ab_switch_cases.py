@@ -1,7 +1,7 @@
 """The kernels behind the A/B environment switches — TEST INFRASTRUCTURE (a plain helper module).
 
-The library reads each ``LIP_...`` switch once per process (function-local statics in csrc/lip_mfma.hip and
-csrc/lip_krylov.hip), so a switch can only be tested in a fresh process: tests/test_ab_switches.py starts
+The library reads each ``LIP_...`` switch once per process (``struct Switches`` of csrc/lip_internal.h, filled on the
+first call of ``switches()`` in csrc/lip_mfma.hip), so a switch can only be tested in a fresh process: tests/test_ab_switches.py starts
 tests/ab_child.py once per entry below, with the entry's environment, and asserts for every row that the census is
 exactly the expected route and that the op passes the same float64 check as in tests/test_kernel_routes.py /
 tests/test_krylov_ops.py.  tests/test_ab_switches_cpu.py checks the table itself.

@@ -99,10 +99,15 @@ def restore_modes(lib, prev):
     lib.lip_set_split_k(1)
 
 
-def run_case(case, seed=0):
-    """run one case; returns (census of the first run, stats {output: (max err, rms / sqrt(K))})."""
+def run_case(case, seed=0, shared=None):
+    """run one case; returns (census of the first run, stats {output: (max err, rms / sqrt(K))}).  shared: a dict that
+    keeps the laid-out op, its host buffers and the two float64 emulations for the next run of the same case."""
     h = harness()
-    op, L, host, outs = h.build(case.spec, seed)
+    shared = {} if shared is None else shared
+    if not shared:
+        op, L, host, outs = h.build(case.spec, seed)
+        shared.update(op=op, host=host, outs=outs)
+    op, host, outs = shared["op"], shared["host"], shared["outs"]
     P = case.spec.P
     prev = set_modes(h.lib, case)
     try:
@@ -117,10 +122,11 @@ def run_case(case, seed=0):
             again = h.download(dev)
     finally:
         restore_modes(h.lib, prev)
-    ref = emulate(h.eng.cn, h.chunk, op, host, P)
-    mag = emulate(h.eng.cn, h.chunk, op, host, P, absolute=True)
+    if "ref" not in shared:
+        shared["ref"] = emulate(h.eng.cn, h.chunk, op, host, P)
+        shared["mag"] = emulate(h.eng.cn, h.chunk, op, host, P, absolute=True)
     k_of, rms_c = tolerances(case)
-    stats = check(got, ref, mag, host, outs, k_of, rms_c, what=case.name)
+    stats = check(got, shared["ref"], shared["mag"], host, outs, k_of, rms_c, what=case.name)
     if case.det:
         for k in got:
             assert torch.equal(got[k].view(torch.int32), again[k].view(torch.int32)), \
@@ -135,6 +141,29 @@ def test_route(case):
     if case.cu and cus != MI355X_CUS:
         pytest.skip(f"route of {case.name} assumes {MI355X_CUS} CUs, this device has {cus} (numbers checked)")
     assert census == {case.route: 1}, f"{case.name}: expected the route {case.route}, the census shows {census}"
+
+
+# One stream's float scratch serves the split-K planes, the transformed Winograd weights and the transformed Winograd
+# activations in turn (stream_scratch of lip_mfma.hip).  The harness launches on torch's current stream, so the sequence
+# runs on the default stream and then on a second one, which gets a scratch record and geometry tables of its own.
+# Floats needed: 18 816 (3 planes), 16 384, 32 768 (grows), 40 960 (grows), then two smaller needs of the grown buffer.
+SCRATCH_SEQUENCE = ["ks_2211_bv4", "wino_8x8", "wino_12x12", "wg_wino_12", "ks_2211_bv4", "wino_8x8"]
+
+
+def test_users_of_one_streams_scratch_back_to_back():
+    by_name = {c.name: c for c in CASES}
+    shared = {name: {} for name in SCRATCH_SEQUENCE}
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    harness()
+    for stream in (torch.cuda.current_stream(), torch.cuda.Stream()):
+        torch.cuda.synchronize()
+        with torch.cuda.stream(stream):
+            for step, name in enumerate(SCRATCH_SEQUENCE):
+                case = by_name[name]
+                census, _ = run_case(case, shared=shared[name])          # (its own row's bounds, determinism included)
+                if not case.cu or cus == MI355X_CUS:
+                    assert census == {case.route: 1}, f"step {step} ({name}): expected {case.route}, the census shows {census}"
+        torch.cuda.synchronize()
 
 
 def test_table_reaches_every_route():
