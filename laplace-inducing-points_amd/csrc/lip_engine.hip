@@ -38,14 +38,23 @@ struct lip_engine {
   int64_t work_pp = 0;      // workspace floats per probe
   int32_t max_chunk = 0;    // probes per chunk
   bool primal_done = false;
-  // optional per-op timing (HIP events recorded on the launch stream)
+  // optional per-op timing (HIP events recorded on the launch stream); a run records into it through its const engine
   bool prof = false;
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
-  std::vector<int> ev_kind;   // kind of the op bracketed by events (2i, 2i+1)
+  mutable std::vector<hipEvent_t> ev_pool;
+  mutable size_t ev_used = 0;
+  mutable std::vector<int> ev_kind;   // kind of the op bracketed by events (2i, 2i+1)
 };
 
 namespace {
+
+// What a backward sweep does with the parameter cotangents (weight gradients, bias / BN reductions) it forms
+enum class Sweep {
+  SUMMED,   // lip_ggn_vp / lip_vjp: summed over the examples into the (P, D) block Y
+  ROWS,     // lip_vjp_rows: Y holds one row per (probe, example); no reduction crosses examples
+  SQSUM,    // lip_vjp_sqsum: formed per (probe, example) as in ROWS, squared and summed into ONE (D,) vector Y
+  WNORM,    // lip_vjp_wnorm: formed per (probe, example); Y is the (D,) WEIGHT vector, read only, and the weighted square
+            // norm of every cotangent is added to wout[p * n + i]
+};
 
 struct RunCtx {
   const lip_engine* e;
@@ -56,22 +65,31 @@ struct RunCtx {
   int head_mode;
   float head_c;
   hipStream_t st;
-  bool rows = false;   // lip_vjp_rows: Y holds one row per (probe, example); no reduction crosses examples
-  // lip_vjp_sqsum: Y is ONE (D,) vector; every parameter cotangent is formed per (probe, example) as in `rows`, squared
-  // and summed into Y by the square-accumulating kernels (weight gradients, bias / BN reductions); `scratch` is theirs
-  bool sqsum = false;
-  float* scratch = nullptr;
+  Sweep mode = Sweep::SUMMED;
+  float* scratch = nullptr;       // SQSUM / WNORM: the square-accumulating kernels' scratch
   long long scratch_floats = 0;
-  // lip_vjp_wnorm (set together with sqsum: the same ops leave the summed path): Y is the (D,) WEIGHT vector, read only
-  // (wones: every weight is 1 and Y is a placeholder of the right extent that is never read); the weighted square norm of
-  // every per-(probe, example) parameter cotangent is added to wout[p * n + i]
-  bool wnorm = false, wones = false;
+  bool wones = false;             // WNORM: every weight is 1 and Y is a placeholder of the right extent that is never read
   float* wout = nullptr;
   // summed products (lip_ggn_vp / lip_vjp): a weight gradient that reduces all rows in one block may WRITE
   // y = s acc + alpha v instead of adding to an initialised block (the initialisation then skips its parameters)
   bool fuse = false;
   float alpha = 0.f;
+
+  bool per_example() const { return mode != Sweep::SUMMED; }      // cotangents are taken per example
+  bool may_overwrite(const lip_ref_t& out) const { return fuse && mode == Sweep::SUMMED && out.space == LIP_SP_YOUT; }
 };
+
+// The kinds of sweep, from the operands of one pass (a plain RunCtx{..., st} is summed and not fused)
+inline RunCtx fused_sum(RunCtx c, float alpha) { c.fuse = true; c.alpha = alpha; return c; }
+inline RunCtx example_rows(RunCtx c) { c.mode = Sweep::ROWS; return c; }
+inline RunCtx square_sum(RunCtx c, float* scratch, long long floats) {
+  c.mode = Sweep::SQSUM; c.scratch = scratch; c.scratch_floats = floats;
+  return c;
+}
+inline RunCtx weighted_norm(RunCtx c, float* scratch, long long floats, bool wones, float* wout) {
+  c.mode = Sweep::WNORM; c.scratch = scratch; c.scratch_floats = floats; c.wones = wones; c.wout = wout;
+  return c;
+}
 
 inline float* resolve(const RunCtx& c, const lip_ref_t& r) {
   switch (r.space) {
@@ -86,40 +104,61 @@ inline float* resolve(const RunCtx& c, const lip_ref_t& r) {
   }
 }
 
-// lip_vjp_rows: the parameter reductions an op would fuse (bias / BN cotangents: column sums over ALL rows of a
-// probe) are taken per example instead, by a segmented reduce over the op's freshly written output.
-struct RowReds { float* red0; float* red1; const float* xhat; };
-
 #define RUN_CHECK(expr, what)                                                                  \
   do {                                                                                         \
     hipError_t _e = (expr);                                                                    \
     if (_e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(_e)); return LIP_ERR_HIP; } \
   } while (0)
 
-// Segmented (per-example) parameter reductions of lip_vjp_rows, taken over an op's output tensor [P][n][rows][N].
-// lip_vjp_sqsum (c.sqsum): the same per-example sums, squared and summed over examples and probes into the (D,) output.
-int rows_reduce(const RunCtx& c, const float* out, long long out_ps, int n_img, int rows, int N, const float* xhat,
-                float* red0, long long red0_ps, float* red1, long long red1_ps) {
-  if (!red0 && !red1) return LIP_OK;
+constexpr int MAX_REDUCED_WIDTH = 8192;   // columns of a parameter reduction (bias / BN cotangents) the kernels take
+
+// Scratch floats ONE backward op needs in a sweep over `pairs` (probe, example) pairs: lip_vjp_sqsum's are bounded by the
+// target grid, lip_vjp_wnorm's are pairs x output tiles
+long long wgrad_scratch(Sweep mode, int M, int N, int OHW, long long pairs) {
+  return mode == Sweep::WNORM ? wgrad_wnorm_tiles(M, N, OHW) * pairs : mode == Sweep::SQSUM ? wgrad_sqsum_scratch(M, N, OHW, pairs) : 0;
+}
+long long reduce_scratch(Sweep mode, int N, long long pairs) {
+  return mode == Sweep::WNORM ? reduce_wnorm_tiles(N) * pairs : mode == Sweep::SQSUM ? reduce_sqsum_scratch(N, pairs) : 0;
+}
+
+template <class Prm>
+void resolve_reductions(const RunCtx& c, const lip_op_t& op, Prm& p) {
+  p.red0 = resolve(c, op.red0); p.red0_ps = op.red0.pstride;
+  p.red1 = resolve(c, op.red1); p.red1_ps = op.red1.pstride;
+}
+
+// per-example form of a reduction over [P][n][rows][N]: one output row per (probe, example) instead of one per probe
+void per_example(ReduceP& r, int n_img, int rows) {
+  r.R = rows; r.nseg = n_img; r.red_seg = r.red0 ? r.red0_ps : r.red1_ps;
+  r.red0_ps *= n_img; r.red1_ps *= n_img;
+}
+
+// The parameter reductions of a filled ReduceP, as the sweep takes them: summed or per example (ROWS), squared into the
+// (D,) output (SQSUM), or weighted into wout (WNORM)
+int reduce_params(const RunCtx& c, const ReduceP& r, int n_img, const char* who) {
+  if (!r.g || r.N <= 0 || r.N > MAX_REDUCED_WIDTH || (r.red1 && !r.xhat)) { set_error("%s: bad reduction operands", who); return LIP_ERR_ARG; }
+  if (reduce_scratch(c.mode, r.N, (long long)c.P * n_img) > c.scratch_floats) { set_error("%s: reduction scratch too small", who); return LIP_ERR_ARG; }
+  switch (c.mode) {
+    case Sweep::WNORM: RUN_CHECK(launch_reduce_wnorm(r, c.P, c.wones, c.wout, c.scratch, c.scratch_floats, c.st), who); break;
+    case Sweep::SQSUM: RUN_CHECK(launch_reduce_sqsum(r, c.P, c.scratch, c.scratch_floats, c.st), who); break;
+    default: RUN_CHECK(launch_reduce(r, c.P, c.st), who);
+  }
+  return LIP_OK;
+}
+
+// Launch an op that fuses parameter reductions (column sums over ALL rows of a probe).  A per-example sweep launches it
+// without them and takes them by a segmented reduce over the op's freshly written output [P][n][rows][N] instead.
+template <class Prm, class Launch>
+int launch_with_reductions(const RunCtx& c, Prm& p, Launch launch, const char* who, int n_img, int rows, int N, const float* xhat) {
+  if (!c.per_example() || (!p.red0 && !p.red1)) { RUN_CHECK(launch(p), who); return LIP_OK; }
   ReduceP r;
   memset(&r, 0, sizeof(r));
-  r.g = out; r.g_ps = out_ps; r.R = rows; r.N = N; r.xhat = xhat;
-  r.red0 = red0; r.red1 = red1;
-  r.nseg = n_img; r.red_seg = red0 ? red0_ps : red1_ps;
-  r.red0_ps = red0_ps * n_img; r.red1_ps = red1_ps * n_img;
-  if (N <= 0 || N > 8192 || (red1 && !xhat)) { set_error("per-example reduce: bad operands"); return LIP_ERR_ARG; }
-  if (c.wnorm) {
-    if (reduce_wnorm_tiles(N) * c.P * n_img > c.scratch_floats) { set_error("weighted-norm reduce: scratch too small"); return LIP_ERR_ARG; }
-    RUN_CHECK(launch_reduce_wnorm(r, c.P, c.wones, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm reduce launch");
-    return LIP_OK;
-  }
-  if (c.sqsum) {
-    if (reduce_sqsum_scratch(N, (long long)c.P * n_img) > c.scratch_floats) { set_error("square-sum reduce: scratch too small"); return LIP_ERR_ARG; }
-    RUN_CHECK(launch_reduce_sqsum(r, c.P, c.scratch, c.scratch_floats, c.st), "square-sum reduce launch");
-    return LIP_OK;
-  }
-  RUN_CHECK(launch_reduce(r, c.P, c.st), "per-example reduce launch");
-  return LIP_OK;
+  r.g = p.out; r.g_ps = p.out_ps; r.N = N; r.xhat = xhat;
+  r.red0 = p.red0; r.red0_ps = p.red0_ps; r.red1 = p.red1; r.red1_ps = p.red1_ps;
+  per_example(r, n_img, rows);
+  p.red0 = nullptr; p.red1 = nullptr;
+  RUN_CHECK(launch(p), who);
+  return reduce_params(c, r, n_img, who);
 }
 
 int check_space(const RunCtx& c, const lip_ref_t& r, const char* what) {
@@ -143,10 +182,10 @@ int make_wgrad(const RunCtx& c, const lip_op_t& op, WgradP& p) {
   p.y = resolve(c, op.out); p.y_ps = op.out.pstride;
   p.scale = resolve(c, op.scale);
   p.ksplit = op.ksplit > 0 ? op.ksplit : 0;           // 0: the launcher picks the row split for the probe count
-  if (c.rows) {
+  if (c.mode == Sweep::ROWS) {
     p.ksplit = op.n_img; p.seg_rows = p.OHW; p.seg_ys = p.y_ps; p.y_ps *= op.n_img;
-  } else if (c.sqsum) {
-    p.ksplit = 1; p.seg_rows = p.OHW; p.seg_ys = 0;     // per-example row geometry; launch_wgrad_sqsum walks the examples
+  } else if (c.per_example()) {
+    p.ksplit = 1; p.seg_rows = p.OHW; p.seg_ys = 0;     // per-example row geometry; the square-accumulating launchers walk the examples
   }
   if (!p.a || !p.g || !p.y || p.R <= 0 || p.N <= 0 || p.M <= 0) { set_error("WGRAD: bad operands"); return LIP_ERR_ARG; }
   if ((long long)p.R * p.N >= (1ll << 31) || (long long)op.n_img * p.IH * p.IW * p.C >= (1ll << 31) || (long long)p.M * p.N >= (1ll << 31)) {
@@ -154,7 +193,7 @@ int make_wgrad(const RunCtx& c, const lip_op_t& op, WgradP& p) {
     return LIP_ERR_ARG;
   }
   if ((p.C & 3) == 0 && (((uintptr_t)p.a) & 15)) { set_error("WGRAD: activations not 16-byte aligned"); return LIP_ERR_ARG; }
-  if (c.fuse && !c.rows && !c.sqsum && op.out.space == LIP_SP_YOUT && wgrad_will_overwrite(p, c.P)) {
+  if (c.may_overwrite(op.out) && wgrad_will_overwrite(p, c.P)) {
     p.overwrite = 1;
     p.v = c.V ? c.V + op.out.off : nullptr; p.v_ps = op.out.pstride; p.alpha = c.alpha;
   }
@@ -195,8 +234,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       p.xhat = resolve(c, op.xhat);
       p.res = resolve(c, op.res); p.res_ps = op.res.pstride;
       p.dphi = resolve(c, op.dphi);
-      p.red0 = resolve(c, op.red0); p.red0_ps = op.red0.pstride;
-      p.red1 = resolve(c, op.red1); p.red1_ps = op.red1.pstride;
+      resolve_reductions(c, op, p);
       p.xhat2 = resolve(c, op.xhat2);
       if (!p.out || p.R <= 0 || p.N <= 0) { set_error("IGEMM: bad output"); return LIP_ERR_ARG; }
       {   // the kernels index tensors with 32-bit arithmetic: refuse bindings that do not fit instead of wrapping
@@ -208,30 +246,21 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       }
       if (p.e1 && !p.xhat) { set_error("IGEMM: e1 without xhat"); return LIP_ERR_ARG; }
       if (p.red1 && !p.xhat2) { set_error("IGEMM: red1 without xhat2"); return LIP_ERR_ARG; }
-      if ((c.rows || c.sqsum) && (p.red0 || p.red1)) {
-        float* r0 = p.red0; float* r1 = p.red1;
-        p.red0 = nullptr; p.red1 = nullptr;
-        RUN_CHECK(launch_igemm(p, c.P, c.st), "igemm launch");
-        return rows_reduce(c, p.out, p.out_ps, op.n_img, p.OHW, p.N, p.xhat2, r0, p.red0_ps, r1, p.red1_ps);
-      }
-      RUN_CHECK(launch_igemm(p, c.P, c.st), "igemm launch");
-      return LIP_OK;
+      return launch_with_reductions(c, p, [&](const IgemmP& q) { return launch_igemm(q, c.P, c.st); }, "IGEMM launch",
+                                    op.n_img, p.OHW, p.N, p.xhat2);
     }
     case LIP_OP_WGRAD: {
       WgradP p;
       const int rc = make_wgrad(c, op, p);
       if (rc) return rc;
-      if (c.wnorm) {
-        if (wgrad_wnorm_tiles(p.M, p.N, p.OHW) * c.P * op.n_img > c.scratch_floats) { set_error("weighted-norm WGRAD: scratch too small"); return LIP_ERR_ARG; }
-        RUN_CHECK(launch_wgrad_wnorm(p, c.P, op.n_img, c.wones ? nullptr : p.y, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm wgrad launch");
-        return LIP_OK;
+      if (wgrad_scratch(c.mode, p.M, p.N, p.OHW, (long long)c.P * op.n_img) > c.scratch_floats) { set_error("WGRAD: scratch too small"); return LIP_ERR_ARG; }
+      switch (c.mode) {
+        case Sweep::WNORM:
+          RUN_CHECK(launch_wgrad_wnorm(p, c.P, op.n_img, c.wones ? nullptr : p.y, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm wgrad launch");
+          break;
+        case Sweep::SQSUM: RUN_CHECK(launch_wgrad_sqsum(p, c.P, op.n_img, c.scratch, c.scratch_floats, c.st), "square-sum wgrad launch"); break;
+        default: RUN_CHECK(launch_wgrad(p, c.P, c.st), "wgrad launch");
       }
-      if (c.sqsum) {
-        if (wgrad_sqsum_scratch(p.M, p.N, p.OHW, (long long)c.P * op.n_img) > c.scratch_floats) { set_error("square-sum WGRAD: scratch too small"); return LIP_ERR_ARG; }
-        RUN_CHECK(launch_wgrad_sqsum(p, c.P, op.n_img, c.scratch, c.scratch_floats, c.st), "square-sum wgrad launch");
-        return LIP_OK;
-      }
-      RUN_CHECK(launch_wgrad(p, c.P, c.st), "wgrad launch");
       return LIP_OK;
     }
     case LIP_OP_REDUCE: {
@@ -240,25 +269,9 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       p.g = resolve(c, op.seg[0].a); p.g_ps = op.seg[0].a.pstride;
       p.R = op.n_img * op.OH * op.OW; p.N = op.N;
       p.xhat = resolve(c, op.xhat2);
-      p.red0 = resolve(c, op.red0); p.red0_ps = op.red0.pstride;
-      p.red1 = resolve(c, op.red1); p.red1_ps = op.red1.pstride;
-      if (!p.g || p.N <= 0 || p.N > 8192 || (p.red1 && !p.xhat)) { set_error("REDUCE: bad operands"); return LIP_ERR_ARG; }
-      if (c.rows || c.sqsum) {
-        p.R = op.OH * op.OW; p.nseg = op.n_img; p.red_seg = p.red0 ? p.red0_ps : p.red1_ps;
-        p.red0_ps *= op.n_img; p.red1_ps *= op.n_img;
-      }
-      if (c.wnorm) {
-        if (reduce_wnorm_tiles(p.N) * c.P * op.n_img > c.scratch_floats) { set_error("weighted-norm REDUCE: scratch too small"); return LIP_ERR_ARG; }
-        RUN_CHECK(launch_reduce_wnorm(p, c.P, c.wones, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm reduce launch");
-        return LIP_OK;
-      }
-      if (c.sqsum) {
-        if (reduce_sqsum_scratch(p.N, (long long)c.P * op.n_img) > c.scratch_floats) { set_error("square-sum REDUCE: scratch too small"); return LIP_ERR_ARG; }
-        RUN_CHECK(launch_reduce_sqsum(p, c.P, c.scratch, c.scratch_floats, c.st), "square-sum reduce launch");
-        return LIP_OK;
-      }
-      RUN_CHECK(launch_reduce(p, c.P, c.st), "reduce launch");
-      return LIP_OK;
+      resolve_reductions(c, op, p);
+      if (c.per_example()) per_example(p, op.n_img, op.OH * op.OW);
+      return reduce_params(c, p, op.n_img, "REDUCE");
     }
     case LIP_OP_POOL_FWD:
     case LIP_OP_POOL_BWD: {
@@ -269,17 +282,11 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       p.n = op.n_img; p.HW = op.OH * op.OW; p.C = op.N; p.inv = op.fscale;
       p.dphi = resolve(c, op.dphi);
       p.xhat = resolve(c, op.xhat2);
-      p.red0 = resolve(c, op.red0); p.red0_ps = op.red0.pstride;
-      p.red1 = resolve(c, op.red1); p.red1_ps = op.red1.pstride;
-      if (!p.in || !p.out || p.C <= 0 || p.C > 8192 || (p.red1 && !p.xhat)) { set_error("POOL: bad operands"); return LIP_ERR_ARG; }
-      if (op.kind == LIP_OP_POOL_FWD) RUN_CHECK(launch_pool_fwd(p, c.P, c.st), "pool_fwd launch");
-      else if ((c.rows || c.sqsum) && (p.red0 || p.red1)) {
-        float* r0 = p.red0; float* r1 = p.red1;
-        p.red0 = nullptr; p.red1 = nullptr;
-        RUN_CHECK(launch_pool_bwd(p, c.P, c.st), "pool_bwd launch");
-        return rows_reduce(c, p.out, p.out_ps, p.n, p.HW, p.C, p.xhat, r0, p.red0_ps, r1, p.red1_ps);
-      }
-      else RUN_CHECK(launch_pool_bwd(p, c.P, c.st), "pool_bwd launch");
+      resolve_reductions(c, op, p);
+      if (!p.in || !p.out || p.C <= 0 || p.C > MAX_REDUCED_WIDTH || (p.red1 && !p.xhat)) { set_error("POOL: bad operands"); return LIP_ERR_ARG; }
+      if (op.kind == LIP_OP_POOL_BWD)
+        return launch_with_reductions(c, p, [&](const PoolP& q) { return launch_pool_bwd(q, c.P, c.st); }, "POOL_BWD launch", p.n, p.HW, p.C, p.xhat);
+      RUN_CHECK(launch_pool_fwd(p, c.P, c.st), "pool_fwd launch");
       return LIP_OK;
     }
     case LIP_OP_MAXPOOL_PRIMAL:
@@ -295,18 +302,12 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       p.KH = g.KH; p.KW = g.KW; p.stride = g.stride; p.pad_h = g.pad_h; p.pad_w = g.pad_w;
       p.dphi = resolve(c, op.dphi);
       p.xhat = resolve(c, op.xhat2);
-      p.red0 = resolve(c, op.red0); p.red0_ps = op.red0.pstride;
-      p.red1 = resolve(c, op.red1); p.red1_ps = op.red1.pstride;
-      if (!p.in || !p.out || p.C <= 0 || p.C > 8192 || p.stride <= 0 || (p.red1 && !p.xhat)) { set_error("MAXPOOL: bad operands"); return LIP_ERR_ARG; }
+      resolve_reductions(c, op, p);
+      if (!p.in || !p.out || p.C <= 0 || p.C > MAX_REDUCED_WIDTH || p.stride <= 0 || (p.red1 && !p.xhat)) { set_error("MAXPOOL: bad operands"); return LIP_ERR_ARG; }
       if (op.kind == LIP_OP_MAXPOOL_PRIMAL) RUN_CHECK(launch_maxpool_primal(p, c.st), "maxpool_primal launch");
       else if (op.kind == LIP_OP_MAXPOOL_FWD) RUN_CHECK(launch_maxpool_fwd(p, c.P, c.st), "maxpool_fwd launch");
-      else if ((c.rows || c.sqsum) && (p.red0 || p.red1)) {
-        float* r0 = p.red0; float* r1 = p.red1;
-        p.red0 = nullptr; p.red1 = nullptr;
-        RUN_CHECK(launch_maxpool_bwd(p, c.P, c.st), "maxpool_bwd launch");
-        return rows_reduce(c, p.out, p.out_ps, p.n, p.IH * p.IW, p.C, p.xhat, r0, p.red0_ps, r1, p.red1_ps);
-      }
-      else RUN_CHECK(launch_maxpool_bwd(p, c.P, c.st), "maxpool_bwd launch");
+      else return launch_with_reductions(c, p, [&](const MaxPoolP& q) { return launch_maxpool_bwd(q, c.P, c.st); }, "MAXPOOL_BWD launch",
+                                         p.n, p.IH * p.IW, p.C, p.xhat);
       return LIP_OK;
     }
     case LIP_OP_PRIMAL_POST: {
@@ -354,7 +355,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
   }
 }
 
-hipEvent_t next_event(lip_engine* e) {
+hipEvent_t next_event(const lip_engine* e) {
   if (e->ev_used == e->ev_pool.size()) {
     hipEvent_t ev;
     if (hipEventCreate(&ev) != hipSuccess) return nullptr;
@@ -366,16 +367,15 @@ hipEvent_t next_event(lip_engine* e) {
 int run_tape(const RunCtx& c, int which, bool skip_head) {
   const std::vector<lip_op_t>& t = c.e->tape[which];
   if (t.empty()) { set_error("tape %d is empty", which); return LIP_ERR_STATE; }
-  lip_engine* me = const_cast<lip_engine*>(c.e);
   for (size_t i = 0; i < t.size(); ++i) {
     if (skip_head && t[i].kind == LIP_OP_HEAD) continue;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (me->prof) {
-      e0 = next_event(me); e1 = next_event(me);
-      if (e0 && e1) { me->ev_kind.push_back(t[i].kind); (void)hipEventRecord(e0, c.st); }
+    if (c.e->prof) {
+      e0 = next_event(c.e); e1 = next_event(c.e);
+      if (e0 && e1) { c.e->ev_kind.push_back(t[i].kind); (void)hipEventRecord(e0, c.st); }
     }
     const int rc = run_op(c, t[i]);
-    if (me->prof && e0 && e1) (void)hipEventRecord(e1, c.st);
+    if (c.e->prof && e0 && e1) (void)hipEventRecord(e1, c.st);
     if (rc != LIP_OK) {
       char buf[400];
       snprintf(buf, sizeof(buf), "%s", g_err);
@@ -415,11 +415,18 @@ int init_output(const RunCtx& c, int64_t D) {
   return LIP_OK;
 }
 
-int ready(const lip_engine* e, const char* who) {
+// What every sweep entry point checks first, in this order: the engine, its binding, the primal pass, its own arguments
+int ready(const lip_engine* e, const char* who, bool args_ok) {
   if (!e) { set_error("%s: null engine", who); return LIP_ERR_ARG; }
   if (!e->theta || !e->prim || !e->work || e->max_chunk <= 0) { set_error("%s: engine not bound", who); return LIP_ERR_STATE; }
   if (!e->primal_done) { set_error("%s: primal pass not run", who); return LIP_ERR_STATE; }
+  if (!args_ok) { set_error("%s: bad argument", who); return LIP_ERR_ARG; }
   return LIP_OK;
+}
+
+// ... of a backward sweep from the head cotangents U (lip_vjp and its per-example variants)
+int ready_vjp(const lip_engine* e, const char* who, const float* U, const void* out, int P, int head_mode, bool more_ok = true) {
+  return ready(e, who, U && out && P > 0 && (head_mode == LIP_HEAD_L || head_mode == LIP_HEAD_IN) && more_ok);
 }
 
 // Probes per pass when P exceeds the workspace: equal passes (256 probes on an 85-probe workspace run 4 x 64, not
@@ -429,36 +436,65 @@ inline int balanced_chunk(int P, int max_chunk) {
   return (P + passes - 1) / passes;
 }
 
-// scratch floats of lip_vjp_sqsum on passes of pc probes: the largest need of one backward op (ops run in stream order
-// and reuse it).  Depends on the tape geometry only — bounded by the target grid, not by n or the probe count.
-int64_t sqsum_scratch(const lip_engine* e, int pc) {
+// The probe-chunk loop of every sweep: body(c0, pc) runs the pass over probes [c0, c0 + pc) and returns its status.
+// Probe c0 of a block with `stride` floats per probe starts at block + c0 * stride.
+template <class Body>
+int for_each_pass(const lip_engine* e, int P, Body body) {
+  for (int c0 = 0, step = balanced_chunk(P, e->max_chunk); c0 < P; c0 += step) {
+    const int rc = body(c0, std::min(step, P - c0));
+    if (rc) return rc;
+  }
+  return LIP_OK;
+}
+
+inline float* head_block(const lip_engine* e, const float* U, int c0) { return const_cast<float*>(U) + (int64_t)c0 * e->n_img * e->K; }
+
+// lip_ggn_vp, and lip_ggn_vp_diag (a != null): the same sweep with alpha = 0, its overwrite plan unchanged, then the
+// prior term a (.) V over the pass
+int ggn_sweep(const lip_engine* e, const float* V, float* Y, int P, float scale, float alpha, const float* a, hipStream_t st) {
+  return for_each_pass(e, P, [&](int c0, int pc) {
+    const float* v = V + c0 * e->D;
+    float* y = Y + c0 * e->D;
+    const RunCtx c = fused_sum(RunCtx{e, v, y, nullptr, pc, LIP_HEAD_GGN, scale, st}, alpha);
+    int rc;
+    if ((rc = init_output(c, e->D)) || (rc = run_tape(c, LIP_TAPE_TANGENT, false)) || (rc = run_tape(c, LIP_TAPE_BACKWARD, true))) return rc;
+    if (a) RUN_CHECK(launch_add_diag(y, v, a, pc, (long long)e->D, st), "add_diag");
+    return LIP_OK;
+  });
+}
+
+// Scratch floats of a lip_vjp_sqsum / lip_vjp_wnorm call of P probes: the largest need of one backward op on one pass
+// (ops run in stream order and reuse it).  Depends on the tape geometry and the probes per pass only.
+int64_t sweep_scratch(const lip_engine* e, Sweep mode, int P) {
+  const int pc = e->max_chunk > 0 ? balanced_chunk(P, e->max_chunk) : P;
   int64_t need = 0;
   for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
     const long long pairs = (long long)pc * op.n_img;
     int64_t k = 0;
     if (op.kind == LIP_OP_WGRAD)
-      k = wgrad_sqsum_scratch(op.seg[0].KH * op.seg[0].KW * op.seg[0].C, op.N, op.OH * op.OW, pairs);
+      k = wgrad_scratch(mode, op.seg[0].KH * op.seg[0].KW * op.seg[0].C, op.N, op.OH * op.OW, pairs);
     else if ((op.kind == LIP_OP_IGEMM || op.kind == LIP_OP_REDUCE || op.kind == LIP_OP_POOL_BWD || op.kind == LIP_OP_MAXPOOL_BWD) &&
              (op.red0.space != LIP_SP_NONE || op.red1.space != LIP_SP_NONE))
-      k = reduce_sqsum_scratch(op.N, pairs);
+      k = reduce_scratch(mode, op.N, pairs);
     need = std::max(need, k);
   }
   return need;
 }
 
-// scratch floats of lip_vjp_wnorm on passes of pc probes: (pairs of a pass) x (output tiles of the op with the most)
-int64_t wnorm_scratch(const lip_engine* e, int pc) {
-  int64_t need = 0;
-  for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
-    int64_t tiles = 0;
-    if (op.kind == LIP_OP_WGRAD)
-      tiles = wgrad_wnorm_tiles(op.seg[0].KH * op.seg[0].KW * op.seg[0].C, op.N, op.OH * op.OW);
-    else if ((op.kind == LIP_OP_IGEMM || op.kind == LIP_OP_REDUCE || op.kind == LIP_OP_POOL_BWD || op.kind == LIP_OP_MAXPOOL_BWD) &&
-             (op.red0.space != LIP_SP_NONE || op.red1.space != LIP_SP_NONE))
-      tiles = reduce_wnorm_tiles(op.N);
-    need = std::max(need, tiles * (int64_t)pc * op.n_img);
-  }
-  return need;
+// lip_vjp_sqsum_scratch / lip_vjp_wnorm_scratch
+int scratch_query(const lip_engine* e, const char* who, Sweep mode, int P, int64_t* floats) {
+  if (!e || !floats || P <= 0) { set_error("%s: bad argument", who); return LIP_ERR_ARG; }
+  if (e->tape[LIP_TAPE_BACKWARD].empty()) { set_error("%s: backward tape missing", who); return LIP_ERR_STATE; }
+  *floats = sweep_scratch(e, mode, P);
+  return LIP_OK;
+}
+
+// ... and the refusal of a call whose scratch is smaller than the query says
+int scratch_fits(const lip_engine* e, const char* who, Sweep mode, int P, const float* scratch, int64_t scratch_floats) {
+  const int64_t need = sweep_scratch(e, mode, P);
+  if (scratch_floats >= need && (need == 0 || scratch)) return LIP_OK;
+  set_error("%s: scratch of %lld floats, %lld needed (%s_scratch)", who, (long long)scratch_floats, (long long)need, who);
+  return LIP_ERR_ARG;
 }
 
 }  // namespace
@@ -514,8 +550,7 @@ int lip_engine_bind(lip_engine_t* e, const float* theta, const float* consts, fl
 
 int lip_engine_primal(lip_engine_t* e, void* stream) {
   if (!e || !e->theta || !e->prim) { set_error("lip_engine_primal: engine not bound"); return LIP_ERR_STATE; }
-  RunCtx c{e, nullptr, nullptr, nullptr, 1, 0, 1.f, (hipStream_t)stream};
-  const int rc = run_tape(c, LIP_TAPE_PRIMAL, false);
+  const int rc = run_tape(RunCtx{e, nullptr, nullptr, nullptr, 1, 0, 1.f, (hipStream_t)stream}, LIP_TAPE_PRIMAL, false);
   if (rc == LIP_OK) e->primal_done = true;
   return rc;
 }
@@ -548,8 +583,7 @@ int lip_engine_run_op(lip_engine_t* e, const lip_op_t* op, const float* V, float
                       float head_c, void* stream) {
   if (!e || !op || P <= 0 || P > e->max_chunk) { set_error("lip_engine_run_op: bad argument"); return LIP_ERR_ARG; }
   if (!e->theta || !e->prim) { set_error("lip_engine_run_op: engine not bound"); return LIP_ERR_STATE; }
-  RunCtx c{e, V, Y, H, P, head_mode, head_c, (hipStream_t)stream};
-  return run_op(c, *op);
+  return run_op(RunCtx{e, V, Y, H, P, head_mode, head_c, (hipStream_t)stream}, *op);
 }
 
 int lip_debug_run_ops(lip_engine_t* e, int32_t which, int32_t first, int32_t count, const float* V, float* Y,
@@ -557,7 +591,7 @@ int lip_debug_run_ops(lip_engine_t* e, int32_t which, int32_t first, int32_t cou
   if (!e || which < 0 || which > 2 || P <= 0 || P > e->max_chunk) { set_error("lip_debug_run_ops: bad argument"); return LIP_ERR_ARG; }
   const std::vector<lip_op_t>& t = e->tape[which];
   if (first < 0 || count < 0 || (size_t)(first + count) > t.size()) { set_error("lip_debug_run_ops: bad op range"); return LIP_ERR_ARG; }
-  RunCtx c{e, V, Y, H, P, head_mode, head_c, (hipStream_t)stream};
+  const RunCtx c{e, V, Y, H, P, head_mode, head_c, (hipStream_t)stream};
   for (int i = first; i < first + count; ++i) {
     const int rc = run_op(c, t[i]);
     if (rc) return rc;
@@ -574,153 +608,72 @@ int lip_debug_routes(int64_t* counts, int32_t n, const char** names) {
 }
 
 int lip_ggn_vp(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale, float alpha, void* stream) {
-  int rc = ready(e, "lip_ggn_vp");
-  if (rc) return rc;
-  if (!V || !Y || P <= 0) { set_error("lip_ggn_vp: bad argument"); return LIP_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  for (int c0 = 0, step = balanced_chunk(P, e->max_chunk); c0 < P; c0 += step) {
-    const int pc = (P - c0) < step ? (P - c0) : step;
-    const float* v = V + (int64_t)c0 * e->D;
-    float* y = Y + (int64_t)c0 * e->D;
-    RunCtx c{e, v, y, nullptr, pc, LIP_HEAD_GGN, scale, st};
-    c.fuse = true; c.alpha = alpha;
-    if ((rc = init_output(c, e->D))) return rc;
-    if ((rc = run_tape(c, LIP_TAPE_TANGENT, false))) return rc;
-    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, true))) return rc;
-  }
-  return LIP_OK;
+  const int rc = ready(e, "lip_ggn_vp", V && Y && P > 0);
+  return rc ? rc : ggn_sweep(e, V, Y, P, scale, alpha, nullptr, (hipStream_t)stream);
 }
 
 int lip_ggn_vp_diag(lip_engine_t* e, const float* V, float* Y, int32_t P, float scale, const float* a, void* stream) {
-  int rc = ready(e, "lip_ggn_vp_diag");
-  if (rc) return rc;
-  if (!V || !Y || !a || P <= 0) { set_error("lip_ggn_vp_diag: bad argument"); return LIP_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  for (int c0 = 0, step = balanced_chunk(P, e->max_chunk); c0 < P; c0 += step) {
-    const int pc = (P - c0) < step ? (P - c0) : step;
-    const float* v = V + (int64_t)c0 * e->D;
-    float* y = Y + (int64_t)c0 * e->D;
-    // the sweep of lip_ggn_vp with alpha = 0 (its overwrite plan unchanged), then the prior term over the chunk
-    RunCtx c{e, v, y, nullptr, pc, LIP_HEAD_GGN, scale, st};
-    c.fuse = true; c.alpha = 0.f;
-    if ((rc = init_output(c, e->D))) return rc;
-    if ((rc = run_tape(c, LIP_TAPE_TANGENT, false))) return rc;
-    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, true))) return rc;
-    RUN_CHECK(launch_add_diag(y, v, a, pc, (long long)e->D, st), "add_diag");
-  }
-  return LIP_OK;
+  const int rc = ready(e, "lip_ggn_vp_diag", V && Y && a && P > 0);
+  return rc ? rc : ggn_sweep(e, V, Y, P, scale, 0.f, a, (hipStream_t)stream);
 }
 
 int lip_jvp(lip_engine_t* e, const float* V, float* U, int32_t P, int32_t head_mode, float cc, void* stream) {
-  int rc = ready(e, "lip_jvp");
+  const int rc = ready(e, "lip_jvp", V && U && P > 0 && (head_mode == LIP_HEAD_LT || head_mode == LIP_HEAD_OUT));
   if (rc) return rc;
-  if (!V || !U || P <= 0 || (head_mode != LIP_HEAD_LT && head_mode != LIP_HEAD_OUT)) { set_error("lip_jvp: bad argument"); return LIP_ERR_ARG; }
-  const int64_t hstride = (int64_t)e->n_img * e->K;
-  for (int c0 = 0, step = balanced_chunk(P, e->max_chunk); c0 < P; c0 += step) {
-    const int pc = (P - c0) < step ? (P - c0) : step;
-    RunCtx c{e, V + (int64_t)c0 * e->D, nullptr, U + (int64_t)c0 * hstride, pc, head_mode, cc, (hipStream_t)stream};
-    if ((rc = run_tape(c, LIP_TAPE_TANGENT, false))) return rc;
-  }
-  return LIP_OK;
+  return for_each_pass(e, P, [&](int c0, int pc) {
+    return run_tape(RunCtx{e, V + c0 * e->D, nullptr, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream}, LIP_TAPE_TANGENT, false);
+  });
 }
 
 int lip_vjp(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t head_mode, float cc, void* stream) {
-  int rc = ready(e, "lip_vjp");
+  const int rc = ready_vjp(e, "lip_vjp", U, Y, P, head_mode);
   if (rc) return rc;
-  if (!U || !Y || P <= 0 || (head_mode != LIP_HEAD_L && head_mode != LIP_HEAD_IN)) { set_error("lip_vjp: bad argument"); return LIP_ERR_ARG; }
-  const int64_t hstride = (int64_t)e->n_img * e->K;
-  hipStream_t st = (hipStream_t)stream;
-  for (int c0 = 0, step = balanced_chunk(P, e->max_chunk); c0 < P; c0 += step) {
-    const int pc = (P - c0) < step ? (P - c0) : step;
-    float* y = Y + (int64_t)c0 * e->D;
-    RunCtx c{e, nullptr, y, const_cast<float*>(U) + (int64_t)c0 * hstride, pc, head_mode, cc, st};
-    c.fuse = true; c.alpha = 0.f;
-    if ((rc = init_output(c, e->D))) return rc;
-    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, false))) return rc;
-  }
-  return LIP_OK;
+  return for_each_pass(e, P, [&](int c0, int pc) {
+    const RunCtx c = fused_sum(RunCtx{e, nullptr, Y + c0 * e->D, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream}, 0.f);
+    const int rc = init_output(c, e->D);
+    return rc ? rc : run_tape(c, LIP_TAPE_BACKWARD, false);
+  });
 }
 
 int lip_vjp_rows(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t head_mode, float cc, void* stream) {
-  int rc = ready(e, "lip_vjp_rows");
+  const int rc = ready_vjp(e, "lip_vjp_rows", U, Y, P, head_mode);
   if (rc) return rc;
-  if (!U || !Y || P <= 0 || (head_mode != LIP_HEAD_L && head_mode != LIP_HEAD_IN)) { set_error("lip_vjp_rows: bad argument"); return LIP_ERR_ARG; }
-  const int64_t hstride = (int64_t)e->n_img * e->K, ystride = (int64_t)e->n_img * e->D;
+  const int64_t ystride = (int64_t)e->n_img * e->D;
   hipStream_t st = (hipStream_t)stream;
-  for (int c0 = 0, step = balanced_chunk(P, e->max_chunk); c0 < P; c0 += step) {
-    const int pc = (P - c0) < step ? (P - c0) : step;
-    float* y = Y + (int64_t)c0 * ystride;
+  return for_each_pass(e, P, [&](int c0, int pc) {
+    float* y = Y + c0 * ystride;
     RUN_CHECK(hipMemsetAsync(y, 0, sizeof(float) * (size_t)pc * ystride, st), "memset Y");
-    RunCtx c{e, nullptr, y, const_cast<float*>(U) + (int64_t)c0 * hstride, pc, head_mode, cc, st, true};
-    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, false))) return rc;
-  }
-  return LIP_OK;
+    return run_tape(example_rows(RunCtx{e, nullptr, y, head_block(e, U, c0), pc, head_mode, cc, st}), LIP_TAPE_BACKWARD, false);
+  });
 }
 
 int lip_vjp_sqsum_scratch(lip_engine_t* e, int32_t P, int64_t* floats) {
-  if (!e || !floats || P <= 0) { set_error("lip_vjp_sqsum_scratch: bad argument"); return LIP_ERR_ARG; }
-  if (e->tape[LIP_TAPE_BACKWARD].empty()) { set_error("lip_vjp_sqsum_scratch: backward tape missing"); return LIP_ERR_STATE; }
-  *floats = sqsum_scratch(e, e->max_chunk > 0 ? balanced_chunk(P, e->max_chunk) : P);
-  return LIP_OK;
+  return scratch_query(e, "lip_vjp_sqsum_scratch", Sweep::SQSUM, P, floats);
 }
 
 int lip_vjp_sqsum(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t head_mode, float cc, float* scratch,
                   int64_t scratch_floats, void* stream) {
-  int rc = ready(e, "lip_vjp_sqsum");
-  if (rc) return rc;
-  if (!U || !Y || P <= 0 || (head_mode != LIP_HEAD_L && head_mode != LIP_HEAD_IN) || scratch_floats < 0) {
-    set_error("lip_vjp_sqsum: bad argument");
-    return LIP_ERR_ARG;
-  }
-  const int step = balanced_chunk(P, e->max_chunk);
-  const int64_t need = sqsum_scratch(e, step);
-  if (scratch_floats < need || (need > 0 && !scratch)) {
-    set_error("lip_vjp_sqsum: scratch of %lld floats, %lld needed (lip_vjp_sqsum_scratch)", (long long)scratch_floats, (long long)need);
-    return LIP_ERR_ARG;
-  }
-  const int64_t hstride = (int64_t)e->n_img * e->K;
-  hipStream_t st = (hipStream_t)stream;
-  for (int c0 = 0; c0 < P; c0 += step) {
-    const int pc = (P - c0) < step ? (P - c0) : step;
-    RunCtx c{e, nullptr, Y, const_cast<float*>(U) + (int64_t)c0 * hstride, pc, head_mode, cc, st};
-    c.sqsum = true; c.scratch = scratch; c.scratch_floats = scratch_floats;
-    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, false))) return rc;
-  }
-  return LIP_OK;
+  int rc = ready_vjp(e, "lip_vjp_sqsum", U, Y, P, head_mode, scratch_floats >= 0);
+  if (rc || (rc = scratch_fits(e, "lip_vjp_sqsum", Sweep::SQSUM, P, scratch, scratch_floats))) return rc;
+  return for_each_pass(e, P, [&](int c0, int pc) {
+    const RunCtx c{e, nullptr, Y, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    return run_tape(square_sum(c, scratch, scratch_floats), LIP_TAPE_BACKWARD, false);
+  });
 }
 
 int lip_vjp_wnorm_scratch(lip_engine_t* e, int32_t P, int64_t* floats) {
-  if (!e || !floats || P <= 0) { set_error("lip_vjp_wnorm_scratch: bad argument"); return LIP_ERR_ARG; }
-  if (e->tape[LIP_TAPE_BACKWARD].empty()) { set_error("lip_vjp_wnorm_scratch: backward tape missing"); return LIP_ERR_STATE; }
-  *floats = wnorm_scratch(e, e->max_chunk > 0 ? balanced_chunk(P, e->max_chunk) : P);
-  return LIP_OK;
+  return scratch_query(e, "lip_vjp_wnorm_scratch", Sweep::WNORM, P, floats);
 }
 
 int lip_vjp_wnorm(lip_engine_t* e, const float* U, const float* w, float* out, int32_t P, int32_t head_mode, float cc,
                   float* scratch, int64_t scratch_floats, void* stream) {
-  int rc = ready(e, "lip_vjp_wnorm");
-  if (rc) return rc;
-  if (!U || !out || P <= 0 || (head_mode != LIP_HEAD_L && head_mode != LIP_HEAD_IN) || scratch_floats < 0) {
-    set_error("lip_vjp_wnorm: bad argument");
-    return LIP_ERR_ARG;
-  }
-  const int step = balanced_chunk(P, e->max_chunk);
-  const int64_t need = wnorm_scratch(e, step);
-  if (scratch_floats < need || (need > 0 && !scratch)) {
-    set_error("lip_vjp_wnorm: scratch of %lld floats, %lld needed (lip_vjp_wnorm_scratch)", (long long)scratch_floats, (long long)need);
-    return LIP_ERR_ARG;
-  }
-  const int64_t hstride = (int64_t)e->n_img * e->K;
-  hipStream_t st = (hipStream_t)stream;
-  for (int c0 = 0; c0 < P; c0 += step) {
-    const int pc = (P - c0) < step ? (P - c0) : step;
+  int rc = ready_vjp(e, "lip_vjp_wnorm", U, out, P, head_mode, scratch_floats >= 0);
+  if (rc || (rc = scratch_fits(e, "lip_vjp_wnorm", Sweep::WNORM, P, scratch, scratch_floats))) return rc;
+  return for_each_pass(e, P, [&](int c0, int pc) {
     // (w == NULL: theta stands in for the weight vector — a (D,) device block whose slices are addressed, never read)
-    RunCtx c{e, nullptr, const_cast<float*>(w ? w : e->theta), const_cast<float*>(U) + (int64_t)c0 * hstride, pc, head_mode, cc, st};
-    c.sqsum = true; c.scratch = scratch; c.scratch_floats = scratch_floats;
-    c.wnorm = true; c.wones = w == nullptr; c.wout = out + (int64_t)c0 * e->n_img;
-    if ((rc = run_tape(c, LIP_TAPE_BACKWARD, false))) return rc;
-  }
-  return LIP_OK;
+    const RunCtx c{e, nullptr, const_cast<float*>(w ? w : e->theta), head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    return run_tape(weighted_norm(c, scratch, scratch_floats, w == nullptr, out + (int64_t)c0 * e->n_img), LIP_TAPE_BACKWARD, false);
+  });
 }
 
 int lip_debug_wnorm_route_count(void) { return (int)WN_ROUTES; }

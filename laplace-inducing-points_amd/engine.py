@@ -594,6 +594,7 @@ class LinearizedNet:
         h = C.c_void_p()
         nv.check(self.lib.lip_engine_create(C.byref(h), cn.D, self.n, cn.K), "lip_engine_create")
         self.h = h
+        self._scratches = {}
         self._tapes = []
         for which, tape in enumerate(cn.tapes):
             arr = (nv.Op * len(tape))(*tape)
@@ -619,6 +620,22 @@ class LinearizedNet:
         if V.shape[-1] != width:
             raise ValueError(f"expected trailing dimension {width}, got {tuple(V.shape)}")
         return V.reshape(-1, width).to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _cotangents(self, U: torch.Tensor, mode: str, strict: bool = False):
+        """(P, n K) device block of the head cotangents U, and the head constant of ``mode`` (``strict``: 'l' or 'raw')"""
+        if strict and mode not in ("l", "raw"):
+            raise ValueError("mode must be 'l' or 'raw'")
+        Ub = U.reshape(-1, self.n * self.K).to(device=self.device, dtype=torch.float32).contiguous()
+        return Ub, (nv.HEAD_L if mode == "l" else nv.HEAD_IN)
+
+    def _scratch(self, query: str) -> torch.Tensor:
+        """scratch of a square-accumulating sweep: allocated once, sized for the probe chunk by its ``*_scratch`` query"""
+        scratch = self._scratches.get(query)
+        if scratch is None:
+            floats = C.c_int64(0)
+            nv.check(getattr(self.lib, query)(self.h, int(self.chunk), C.byref(floats)), query)
+            scratch = self._scratches[query] = torch.empty(max(1, floats.value), device=self.device, dtype=torch.float32)
+        return scratch
 
     def outputs(self) -> torch.Tensor:
         """primal network outputs f(z_i; theta) (n, K)"""
@@ -686,18 +703,16 @@ class LinearizedNet:
         return U
 
     def vjp(self, U: torch.Tensor, mode: str = "raw", c: float = 1.0) -> torch.Tensor:
-        Ub = U.reshape(-1, self.n * self.K).to(device=self.device, dtype=torch.float32).contiguous()
+        Ub, m = self._cotangents(U, mode)
         Y = torch.empty(Ub.shape[0], self.D, device=self.device, dtype=torch.float32)
-        m = nv.HEAD_L if mode == "l" else nv.HEAD_IN
         nv.check(self.lib.lip_vjp(self.h, nv.ptr(Ub), nv.ptr(Y), Ub.shape[0], m, float(c), nv.stream_ptr()), "lip_vjp")
         return Y
 
     def vjp_rows(self, U: torch.Tensor, mode: str = "raw", c: float = 1.0) -> torch.Tensor:
         """Per-example rows of :meth:`vjp`: ``out[p, i] = J_i^T (c L_i U[p, i])`` -> (P, n, D).  Nothing is summed
         over examples, so the cost is that of ONE backward sweep per probe for all n rows."""
-        Ub = U.reshape(-1, self.n * self.K).to(device=self.device, dtype=torch.float32).contiguous()
+        Ub, m = self._cotangents(U, mode)
         Y = torch.empty(Ub.shape[0], self.n, self.D, device=self.device, dtype=torch.float32)
-        m = nv.HEAD_L if mode == "l" else nv.HEAD_IN
         nv.check(self.lib.lip_vjp_rows(self.h, nv.ptr(Ub), nv.ptr(Y), Ub.shape[0], m, float(c), nv.stream_ptr()),
                  "lip_vjp_rows")
         return Y
@@ -709,20 +724,12 @@ class LinearizedNet:
         so no (P, n, D) rows exist; the result is bitwise reproducible.  One-hot probes e_k on every example give the
         GGN diagonal (:func:`ggn.compute_ggn_diag`); per-example loss gradients ('raw') the empirical-Fisher diagonal.
         The kernels' scratch is a device buffer allocated once per engine, sized for the engine's probe chunk."""
-        if mode not in ("l", "raw"):
-            raise ValueError("mode must be 'l' or 'raw'")
-        Ub = U.reshape(-1, self.n * self.K).to(device=self.device, dtype=torch.float32).contiguous()
+        Ub, m = self._cotangents(U, mode, strict=True)
         if out is None:
             out = torch.zeros(self.D, device=self.device, dtype=torch.float32)
         elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == self.D):
             raise ValueError(f"out must be a contiguous float32 device vector of {self.D} floats")
-        scratch = getattr(self, "_sq_scratch", None)
-        if scratch is None:
-            floats = C.c_int64(0)
-            nv.check(self.lib.lip_vjp_sqsum_scratch(self.h, int(self.chunk), C.byref(floats)), "lip_vjp_sqsum_scratch")
-            scratch = torch.empty(max(1, floats.value), device=self.device, dtype=torch.float32)
-            self._sq_scratch = scratch
-        m = nv.HEAD_L if mode == "l" else nv.HEAD_IN
+        scratch = self._scratch("lip_vjp_sqsum_scratch")
         nv.check(self.lib.lip_vjp_sqsum(self.h, nv.ptr(Ub), nv.ptr(out), Ub.shape[0], m, float(c), nv.ptr(scratch),
                                         scratch.numel(), nv.stream_ptr()), "lip_vjp_sqsum")
         return out
@@ -736,9 +743,7 @@ class LinearizedNet:
         (P, n, D) rows exist and the result is bitwise reproducible.  One-hot probes e_k with the variances of a diagonal
         posterior give the linearised predictive variances (:func:`lla.predict_lla_diag`).  The kernels' scratch is a
         device buffer allocated once per engine, sized for the engine's probe chunk."""
-        if mode not in ("l", "raw"):
-            raise ValueError("mode must be 'l' or 'raw'")
-        Ub = U.reshape(-1, self.n * self.K).to(device=self.device, dtype=torch.float32).contiguous()
+        Ub, m = self._cotangents(U, mode, strict=True)
         P = Ub.shape[0]
         if w is not None:
             w = w.detach().to(device=self.device, dtype=torch.float32).contiguous()
@@ -748,13 +753,7 @@ class LinearizedNet:
             out = torch.zeros(P, self.n, device=self.device, dtype=torch.float32)
         elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == P * self.n):
             raise ValueError(f"out must be a contiguous float32 device block of {P} x {self.n} floats")
-        scratch = getattr(self, "_wn_scratch", None)
-        if scratch is None:
-            floats = C.c_int64(0)
-            nv.check(self.lib.lip_vjp_wnorm_scratch(self.h, int(self.chunk), C.byref(floats)), "lip_vjp_wnorm_scratch")
-            scratch = torch.empty(max(1, floats.value), device=self.device, dtype=torch.float32)
-            self._wn_scratch = scratch
-        m = nv.HEAD_L if mode == "l" else nv.HEAD_IN
+        scratch = self._scratch("lip_vjp_wnorm_scratch")
         nv.check(self.lib.lip_vjp_wnorm(self.h, nv.ptr(Ub), nv.ptr(w), nv.ptr(out), P, m, float(c), nv.ptr(scratch),
                                         scratch.numel(), nv.stream_ptr()), "lip_vjp_wnorm")
         return out

@@ -144,6 +144,56 @@ def test_probe_chunking_and_single_vector():
     assert torch.allclose(a[2], c[0], rtol=1e-4, atol=1e-5)   # split-K atomics reorder the sum
 
 
+@pytest.fixture(scope="module")
+def ragged_over_three_passes():
+    """mlp_ragged bound with a 3-probe workspace and P = 7 probes (passes of 3, 3 and 1: a full pass, a repeated offset
+    and a short last pass), next to the float64 emulator, which is fed pass by pass since its workspace holds 3 probes."""
+    net, Z, model_type, _ = _cases()["mlp_ragged"]
+    state = create_state(net, 3, dtype=F64, logvar=-0.3)
+    eng = LinearizedNet(state, Z, model_type, max_chunk=3)
+    assert eng.chunk == 3
+    flat, _ = flatten_nn_params(state.params)
+    tm = TapeMachine(eng.cn, flat, build_consts(eng.cn, state.params, state.batch_stats, "cpu", F64), Z, chunk=3)
+    tm.primal()
+    g = torch.Generator().manual_seed(11)
+    V = torch.randn(7, eng.D, dtype=F64, generator=g)
+    U = torch.randn(7, eng.n, eng.K, dtype=F64, generator=g)
+
+    def by_pass(fn, X, mode, c):
+        return torch.cat([fn(X[c0:c0 + 3], mode, c).clone() for c0 in (0, 3, 6)])
+    return eng, tm, V, U, by_pass
+
+
+def test_jvp_over_three_probe_passes(ragged_over_three_passes):
+    eng, tm, V, _, by_pass = ragged_over_three_passes
+    lt, raw = eng.jvp(V, "lt", 1.3), eng.jvp(V, "raw")
+    torch.cuda.synchronize()
+    assert lt.shape == raw.shape == (7, eng.n, eng.K)
+    assert _rel(lt, by_pass(tm.jvp, V, nv.HEAD_LT, 1.3)) <= 2e-4
+    assert _rel(raw, by_pass(tm.jvp, V, nv.HEAD_OUT, 1.0)) <= 2e-4
+
+
+def test_vjp_over_three_probe_passes(ragged_over_three_passes):
+    eng, tm, _, U, by_pass = ragged_over_three_passes
+    l, raw = eng.vjp(U, "l", 0.7), eng.vjp(U, "raw")
+    torch.cuda.synchronize()
+    assert l.shape == raw.shape == (7, eng.D)
+    assert _rel(l, by_pass(tm.vjp, U, nv.HEAD_L, 0.7)) <= 2e-4
+    assert _rel(raw, by_pass(tm.vjp, U, nv.HEAD_IN, 1.0)) <= 2e-4
+
+
+def test_vjp_rows_over_three_probe_passes(ragged_over_three_passes):
+    eng, tm, _, U, by_pass = ragged_over_three_passes
+    rows = eng.vjp_rows(U, "l", 0.7)
+    torch.cuda.synchronize()
+    assert rows.shape == (7, eng.n, eng.D)
+    assert _rel(rows.sum(1), by_pass(tm.vjp, U, nv.HEAD_L, 0.7)) <= 2e-4
+    for i in (0, 4, 8):
+        Um = torch.zeros_like(U)
+        Um[:, i] = U[:, i]
+        assert _rel(rows[:, i], by_pass(tm.vjp, Um, nv.HEAD_L, 0.7)) <= 2e-4, i
+
+
 @pytest.mark.parametrize("name", ["resnet1m", "mlp_ragged"])
 def test_products_do_not_read_stale_workspace(name):
     """The cached bindings share ONE probe workspace (``ggn.shared_workspace``), so whatever another engine left there must

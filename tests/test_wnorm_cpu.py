@@ -9,7 +9,7 @@ import torch
 from lip_amd import _native as nv
 from lip_amd.lla import covariance_from_polarisation, polarisation_probes, probit_predictive
 
-LIP_ERR_ARG = 1          # include/lip.h
+LIP_ERR_ARG, LIP_ERR_STATE = 1, 3         # include/lip.h
 
 
 def test_vjp_wnorm_errors_are_status_codes_not_crashes():
@@ -28,6 +28,35 @@ def test_vjp_wnorm_errors_are_status_codes_not_crashes():
         assert lib.lip_vjp_wnorm_scratch(h, 0, ctypes.byref(n)) == LIP_ERR_ARG                        # no probes
         assert lib.lip_vjp_wnorm_scratch(h, 4, ctypes.byref(n)) != 0                                  # no tape yet
         assert b"tape" in lib.lip_last_error()
+        assert n.value == -1
+    finally:
+        assert lib.lip_engine_destroy(h) == 0
+
+
+def test_every_sweep_entry_point_refuses_a_null_then_an_unbound_engine_by_name():
+    """The seven sweeps and the two scratch queries share their checks: a null engine is LIP_ERR_ARG and an engine that
+    is neither bound nor given a tape is LIP_ERR_STATE, before any other argument is looked at, and the message names
+    the entry point that was called."""
+    lib = nv.load()
+    n = ctypes.c_int64(-1)
+    calls = {
+        "lip_ggn_vp": lambda e: lib.lip_ggn_vp(e, None, None, 1, 1.0, 0.0, None),
+        "lip_ggn_vp_diag": lambda e: lib.lip_ggn_vp_diag(e, None, None, 1, 1.0, None, None),
+        "lip_jvp": lambda e: lib.lip_jvp(e, None, None, 1, nv.HEAD_LT, 1.0, None),
+        "lip_vjp": lambda e: lib.lip_vjp(e, None, None, 1, nv.HEAD_L, 1.0, None),
+        "lip_vjp_rows": lambda e: lib.lip_vjp_rows(e, None, None, 1, nv.HEAD_L, 1.0, None),
+        "lip_vjp_sqsum": lambda e: lib.lip_vjp_sqsum(e, None, None, 1, nv.HEAD_L, 1.0, None, 0, None),
+        "lip_vjp_wnorm": lambda e: lib.lip_vjp_wnorm(e, None, None, None, 1, nv.HEAD_L, 1.0, None, 0, None),
+        "lip_vjp_sqsum_scratch": lambda e: lib.lip_vjp_sqsum_scratch(e, 1, ctypes.byref(n)),
+        "lip_vjp_wnorm_scratch": lambda e: lib.lip_vjp_wnorm_scratch(e, 1, ctypes.byref(n)),
+    }
+    h = ctypes.c_void_p()
+    assert lib.lip_engine_create(ctypes.byref(h), 10, 2, 3) == 0
+    try:
+        for name, call in calls.items():
+            for engine, status in ((None, LIP_ERR_ARG), (h, LIP_ERR_STATE)):
+                assert call(engine) == status, (name, status)
+                assert lib.lip_last_error().startswith(name.encode() + b":"), (name, lib.lip_last_error())
         assert n.value == -1
     finally:
         assert lib.lip_engine_destroy(h) == 0
