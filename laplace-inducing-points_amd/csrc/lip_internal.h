@@ -197,6 +197,47 @@ bool wgrad_will_overwrite(const WgradP& p, int P);
 // Scratch: the caller's, `*_sqsum_scratch` floats (0 when the launch needs none); bounded by the target grid
 // (SQ_TARGET_BLOCKS), independent of n and of the probe count.
 constexpr int SQ_TARGET_BLOCKS = 512;                  // 2 blocks per CU on the 256 CUs of an MI355X
+
+// The pair walk shared by the per-pair kernels (wgrad_sqsum / wgrad_wnorm tiles, reduce_sqsum / reduce_wnorm): pair
+// q = p * n_img + i; the blocks of group g (blockIdx.y) take pairs [g * per, min(pairs, (g + 1) * per)) in order.
+struct PairGroupP {
+  int pairs, per, n_img;
+};
+// Groups of a launch with `blocks_per_group` blocks per group, enough of them to fill SQ_TARGET_BLOCKS.
+// bound = min(pairs, ceil(SQ_TARGET_BLOCKS / blocks_per_group)) is monotone in `pairs`, so a scratch sized with it for the
+// largest pass serves every smaller one; the launch's G <= bound after rounding to whole groups of `per` pairs.
+struct PairGroups {
+  long long bound;
+  int G, per;
+};
+inline PairGroups pair_groups(long long blocks_per_group, long long pairs) {
+  PairGroups r;
+  r.bound = (SQ_TARGET_BLOCKS + blocks_per_group - 1) / blocks_per_group;
+  if (r.bound > pairs) r.bound = pairs;
+  if (r.bound < 1) r.bound = 1;
+  r.per = (int)((pairs + r.bound - 1) / r.bound);
+  r.G = (int)((pairs + r.per - 1) / r.per);
+  return r;
+}
+// The argument checks of the four per-pair launchers: P > 0 probes of n_img > 0 examples with `rows` > 0 rows each,
+// fewer than 2^31 pairs; a weight gradient also passes its row total R, which the examples must make up (a reduce is
+// given its rows per segment and has no total to check); and a scratch of `need` floats is there when need > 0.
+inline bool pair_launch_ok(int P, int n_img, long long rows) {
+  return P > 0 && n_img > 0 && rows > 0 && (long long)P * n_img < (1ll << 31);
+}
+inline bool pair_launch_ok(int P, int n_img, long long rows, long long R) {
+  return pair_launch_ok(P, n_img, rows) && rows * n_img == R;
+}
+inline bool scratch_fits(long long need, const float* scratch, long long scratch_floats) {
+  return need <= scratch_floats && (need == 0 || scratch);
+}
+// fills `pg` for a checked launch of `blocks_per_group` blocks per group and returns its number of groups G
+inline int pair_launch_groups(PairGroupP& pg, long long blocks_per_group, int P, int n_img) {
+  const PairGroups g = pair_groups(blocks_per_group, (long long)P * n_img);
+  pg.pairs = P * n_img; pg.per = g.per; pg.n_img = n_img;
+  return g.G;
+}
+
 // weight gradient (p as built for the per-example rows, p.seg_rows = OH*OW): the MFMA kernel per (probe, example)
 // tile, or, when OH*OW == 1, the rank-1 route  y[m][c] += sum_i a_i[m]^2 sum_p (s[c] g_pi[c])^2
 long long wgrad_sqsum_scratch(int M, int N, int OHW, long long pairs);

@@ -1637,7 +1637,8 @@ static hipError_t run_igemm_first(const IgemmP& p, int P, hipStream_t st) {
 
 // ------------------------------------------------------------------------------------------
 // weight gradient: the generic kernels (wgrad_kernel, wgrad_sqsum_kernel, wgrad_wnorm_kernel) share one im2col
-// gather and one K loop, WgradTap + wgrad_accumulate_rows; each keeps its own row ranges and epilogue.
+// gather and one K loop, WgradTap + wgrad_accumulate_rows, and one map from accumulator registers to matrix elements
+// (AccMap); wgrad_kernel and wgrad_fast_kernel share the add-into-y store (wgrad_store).
 // ------------------------------------------------------------------------------------------
 // This thread's column m of the im2col matrix (fixed across the K loop) as a kernel tap:
 // vector path (C % 4 == 0, float4 gathers) m = m0 + 4*(tid % (BM/4)); scalar m0 + tid % BM
@@ -1767,6 +1768,84 @@ __device__ __forceinline__ void wgrad_accumulate_rows(const WgradP& prm, const W
   }
 }
 
+// Where a wave's accumulators acc[tm][tn][reg] (mfma_sweep, 32 x 32 sub-tiles) sit in the M x N matrix, for the wave
+// (wm, wn) of the block tile at (m0, n0):  col = n0 + (wn TN + tn) 32 + lane % 32,
+// m = m0 + (wm TM + tm) 32 + 4 (lane / 32) + reg % 4 + 8 (reg / 4).
+template <int TM, int TN>
+struct AccMap {
+  int mb, cb;
+  __device__ __forceinline__ AccMap(int m0, int n0, int wm, int wn, int lane)
+      : mb(m0 + wm * TM * 32 + 4 * (lane >> 5)), cb(n0 + wn * TN * 32 + (lane & 31)) {}
+  __device__ __forceinline__ int col(int tn) const { return cb + tn * 32; }
+  __device__ __forceinline__ int row(int tm, int reg) const { return mb + tm * 32 + (reg & 3) + 8 * (reg >> 2); }
+  // f(tm, tn, reg, m, col) over every element, columns outermost
+  template <class F>
+  __device__ __forceinline__ void each(F&& f) const {
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) f(tm, tn, reg, row(tm, reg), col(tn));
+  }
+};
+
+// y[m][col] += scale[col] * acc of the block's tile, y the (M, N) block of probe p — of example blockIdx.z of probe p
+// when seg_rows is set.  One split: per sub-tile all 16 loads, then the 16 stores (no load behind a store); ksplit > 1:
+// float atomics.  PB (probe-batched columns j = probe j / N, channel j % N): the probe is the column's, p is not used.
+template <bool PB, int TM, int TN>
+__device__ __forceinline__ void wgrad_store(const WgradP& prm, const AccMap<TM, TN>& map, int p, const f32x16 (&acc)[TM][TN]) {
+  const int N = prm.N, M = prm.M;
+  const int NC = PB ? prm.P * N : N;
+  const long long yseg = prm.seg_rows ? (long long)blockIdx.z * prm.seg_ys : 0;
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) {
+    int col = map.col(tn);
+    if (col >= NC) continue;
+    const int pj = PB ? col / N : p;
+    if (PB) col -= pj * N;
+    float* ybase = prm.y + (long long)pj * prm.y_ps + yseg;
+    const float sc = prm.scale ? prm.scale[col] : 1.f;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+      if (prm.ksplit > 1) {
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int m = map.row(tm, reg);
+          if (m < M) atomicAdd(ybase + (unsigned)(m * N + col), acc[tm][tn][reg] * sc);
+        }
+      } else {
+        float old[16];                      // all loads first, then the stores (no load behind a store)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int m = map.row(tm, reg);
+          old[reg] = (m < M) ? ybase[(unsigned)(m * N + col)] : 0.f;
+        }
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int m = map.row(tm, reg);
+          if (m < M) ybase[(unsigned)(m * N + col)] = old[reg] + acc[tm][tn][reg] * sc;
+        }
+      }
+    }
+  }
+}
+
+// this thread's place in its block, and the block's tile (blockIdx.x) of the (M, N) matrix
+template <int WM, int WN, int TM, int TN>
+struct WgradBlock {
+  using T = Tile<WM, WN, TM, TN>;
+  int tid, lane, wave, wm, wn, m0, n0;
+  __device__ __forceinline__ WgradBlock(int N) {
+    tid = threadIdx.x; lane = tid & 63; wave = tid >> 6;
+    wm = wave / WN; wn = wave % WN;
+    const int tiles_n = (N + T::BN - 1) / T::BN;
+    const int tile_n = blockIdx.x % tiles_n, tile_m = blockIdx.x / tiles_n;
+    m0 = tile_m * T::BM; n0 = tile_n * T::BN;
+  }
+  __device__ __forceinline__ AccMap<TM, TN> map() const { return AccMap<TM, TN>(m0, n0, wm, wn, lane); }
+};
+
 // per-probe weight cotangent: block (tile, p, z) reduces rows [z * rows_per, ...) of probe p (split-K, or one example
 // per z when seg_rows is set) and adds s * acc into y
 template <int WM, int WN, int TM, int TN>
@@ -1776,13 +1855,8 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_kernel(const WgradP prm) {
   __shared__ __attribute__((aligned(16))) float As[BK * (BM + 4)];
   __shared__ float Bs[BK * BN];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int N = prm.N, M = prm.M;
-  const int tiles_n = (N + BN - 1) / BN;
-  const int tile_n = blockIdx.x % tiles_n, tile_m = blockIdx.x / tiles_n;
+  const WgradBlock<WM, WN, TM, TN> b(prm.N);
   const int p = blockIdx.y;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
 
   int rows_per = (prm.R + prm.ksplit - 1) / prm.ksplit;
   rows_per = (rows_per + BK - 1) / BK * BK;
@@ -1794,40 +1868,9 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_kernel(const WgradP prm) {
   f32x16 acc[TM][TN];
   zero_acc(acc);
 
-  const WgradTap tap = wgrad_tap<BM>(prm, m0, tid);
-  wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, rbeg, rend, n0, As, Bs, acc);
-
-  const int l31 = lane & 31, lh = lane >> 5;
-  float* ybase = prm.y + (long long)p * prm.y_ps + (prm.seg_rows ? (long long)blockIdx.z * prm.seg_ys : 0);
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn) {
-    const int col = n0 + (wn * TN + tn) * 32 + l31;
-    if (col >= N) continue;
-    const float sc = prm.scale ? prm.scale[col] : 1.f;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-      const int mb = m0 + (wm * TM + tm) * 32 + 4 * lh;
-      if (prm.ksplit > 1) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int m = mb + (reg & 3) + 8 * (reg >> 2);
-          if (m < M) atomicAdd(ybase + (unsigned)(m * N + col), acc[tm][tn][reg] * sc);
-        }
-      } else {
-        float old[16];                      // all loads first, then the stores (no load behind a store)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int m = mb + (reg & 3) + 8 * (reg >> 2);
-          old[reg] = (m < M) ? ybase[(unsigned)(m * N + col)] : 0.f;
-        }
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int m = mb + (reg & 3) + 8 * (reg >> 2);
-          if (m < M) ybase[(unsigned)(m * N + col)] = old[reg] + acc[tm][tn][reg] * sc;
-        }
-      }
-    }
-  }
+  const WgradTap tap = wgrad_tap<BM>(prm, b.m0, b.tid);
+  wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, rbeg, rend, b.n0, As, Bs, acc);
+  wgrad_store<false>(prm, b.map(), p, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2026,43 +2069,7 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_fast_kernel(const WgradP p
         else mfma_sweep<WM, WN, TM, TN, LDA, LDB>(Asb, Bsb, acc, wm, wn, lane);
       });
 
-  const int l31 = lane & 31, lh = lane >> 5;
-  const long long yseg = prm.seg_rows ? (long long)blockIdx.z * prm.seg_ys : 0;
-  float* ybase = prm.y + (long long)p * prm.y_ps + yseg;
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn) {
-    int col = n0 + (wn * TN + tn) * 32 + l31;
-    if (col >= NC) continue;
-    if (PB) {
-      const int pj = col / N;
-      col -= pj * N;
-      ybase = prm.y + (long long)pj * prm.y_ps + yseg;
-    }
-    const float sc = prm.scale ? prm.scale[col] : 1.f;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-      const int mb = m0 + (wm * TM + tm) * 32 + 4 * lh;
-      if (prm.ksplit > 1) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int m = mb + (reg & 3) + 8 * (reg >> 2);
-          if (m < M) atomicAdd(ybase + (unsigned)(m * N + col), acc[tm][tn][reg] * sc);
-        }
-      } else {
-        float old[16];                      // all loads first, then the stores (no load behind a store)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int m = mb + (reg & 3) + 8 * (reg >> 2);
-          old[reg] = (m < M) ? ybase[(unsigned)(m * N + col)] : 0.f;
-        }
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int m = mb + (reg & 3) + 8 * (reg >> 2);
-          if (m < M) ybase[(unsigned)(m * N + col)] = old[reg] + acc[tm][tn][reg] * sc;
-        }
-      }
-    }
-  }
+  wgrad_store<PB>(prm, AccMap<TM, TN>(m0, n0, wm, wn, lane), p, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3309,19 +3316,41 @@ hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st) {
 
 
 // ------------------------------------------------------------------------------------------
-// square-accumulating per-example weight gradient (lip_vjp_sqsum):
-//   y[m][c] += sum_{(p, i) in the block's group} ( s[c] * sum_{pix of example i} im2col(a_i)[pix][m] g_pi[pix][c] )^2
-// Per (probe p, example i) pair, wgrad_accumulate_rows over the OH*OW rows of example i (the row range of
-// wgrad_kernel's seg_rows path).  After each pair the M x N tile is scaled, squared in registers and added to a
-// second register set; the MFMA accumulators are then cleared for the next pair.  grid = (output tiles, groups):
-// block (t, g) takes pairs [g*per, (g+1)*per) in order and stores one partial per group (plain stores, no atomics);
-// sqsum_finish adds the partials in group order, so the result is bitwise reproducible.  f32 MFMA in every
-// precision mode.
+// per-pair weight gradients (lip_vjp_sqsum, lip_vjp_wnorm): for every (probe p, example i) pair the M x N tile
+//   t_pi[m][c] = sum_{pix of example i} im2col(a_i)[pix][m] g_pi[pix][c]
+// is formed in the MFMA accumulators and folded away at once; no (P, n, M, N) intermediate.  grid = (output tiles,
+// groups of pairs, PairGroupP): block (t, g) walks the pairs of group g in order — clear the accumulators,
+// wgrad_accumulate_rows over the OH*OW rows of example i (the row range of wgrad_kernel's seg_rows path), fold(q, acc).
+// No barrier closes a pair: the leading barrier of the next wgrad_accumulate_rows call orders this pair's last sweep,
+// and whatever LDS reads its fold makes after a barrier of its own, before the next pair's LDS stores.
+// f32 MFMA in every precision mode, plain stores, no atomics: both folds are bitwise reproducible.
+// As / Bs are the calling kernel's __shared__ tiles (see wgrad_accumulate_rows for why they are declared there).
 // ------------------------------------------------------------------------------------------
-struct PairGroupP {                     // pair q = p * n_img + i; block group g takes pairs [g*per, min(pairs, (g+1)*per))
-  int pairs, per, n_img;
-};
+template <int WM, int WN, int TM, int TN, class Fold>
+__device__ __forceinline__ void wgrad_pair_walk(const WgradP& prm, const PairGroupP& pg, const WgradBlock<WM, WN, TM, TN>& b,
+                                                float* As, float* Bs, Fold&& fold) {
+  const int q0 = blockIdx.y * pg.per, q1 = min(pg.pairs, q0 + pg.per);
+  const WgradTap tap = wgrad_tap<Tile<WM, WN, TM, TN>::BM>(prm, b.m0, b.tid);
+  f32x16 acc[TM][TN];
+  for (int q = q0; q < q1; ++q) {
+    const int p = q / pg.n_img, i = q - p * pg.n_img;
+    zero_acc(acc);
+    wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, i * prm.OHW, (i + 1) * prm.OHW, b.n0,
+                                          As, Bs, acc);
+    fold(q, acc);
+  }
+}
 
+// this thread's column scales s[col(tn)] (1 past the matrix or without scales)
+template <int TM, int TN>
+__device__ __forceinline__ void acc_col_scales(const WgradP& prm, const AccMap<TM, TN>& map, float (&scv)[TN]) {
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) scv[tn] = (prm.scale && map.col(tn) < prm.N) ? prm.scale[map.col(tn)] : 1.f;
+}
+
+// square sum (lip_vjp_sqsum):  y[m][c] += sum_{(p, i)} (s[c] t_pi[m][c])^2.  Fold: the tile is scaled, squared and
+// added to a second register set.  One partial per group, which sqsum_finish adds in group order; a launch of one
+// group adds into y directly.
 struct SqGroupP : PairGroupP {
   float* partial;                       // [groups][M*N], or null: one group, add into y
 };
@@ -3329,41 +3358,17 @@ struct SqGroupP : PairGroupP {
 template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(WM * WN * 64) void wgrad_sqsum_kernel(const WgradP prm, const SqGroupP sq) {
   using T = Tile<WM, WN, TM, TN>;
-  constexpr int BM = T::BM, BN = T::BN;
-  __shared__ __attribute__((aligned(16))) float As[BK * (BM + 4)];
-  __shared__ float Bs[BK * BN];
+  __shared__ __attribute__((aligned(16))) float As[BK * (T::BM + 4)];
+  __shared__ float Bs[BK * T::BN];
+  const WgradBlock<WM, WN, TM, TN> b(prm.N);
+  const AccMap<TM, TN> map = b.map();
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int N = prm.N, M = prm.M;
-  const int tiles_n = (N + BN - 1) / BN;
-  const int tile_n = blockIdx.x % tiles_n, tile_m = blockIdx.x / tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int grp = blockIdx.y;
-  const int q0 = grp * sq.per, q1 = min(sq.pairs, q0 + sq.per);
-  const int l31 = lane & 31, lh = lane >> 5;
-
-  f32x16 acc[TM][TN], ssq[TM][TN];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ssq[tm][tn][r] = 0.f;
+  f32x16 ssq[TM][TN];
+  zero_acc(ssq);
   float scv[TN];
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn) {
-    const int col = n0 + (wn * TN + tn) * 32 + l31;
-    scv[tn] = (prm.scale && col < N) ? prm.scale[col] : 1.f;
-  }
+  acc_col_scales(prm, map, scv);
 
-  const WgradTap tap = wgrad_tap<BM>(prm, m0, tid);
-  for (int q = q0; q < q1; ++q) {
-    const int p = q / sq.n_img, i = q - p * sq.n_img;
-    zero_acc(acc);
-    // its leading barrier also orders the previous pair's last sweep before these LDS stores
-    wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, i * prm.OHW, (i + 1) * prm.OHW, n0,
-                                          As, Bs, acc);
+  wgrad_pair_walk<WM, WN, TM, TN>(prm, sq, b, As, Bs, [&](int, const f32x16 (&acc)[TM][TN]) {
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -3373,26 +3378,24 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_sqsum_kernel(const WgradP 
           const float v = acc[tm][tn][r] * scv[tn];
           ssq[tm][tn][r] = fmaf(v, v, ssq[tm][tn][r]);
         }
-  }
+  });
 
-  const long long MN = (long long)M * N;
-  float* out = sq.partial ? sq.partial + (long long)grp * MN : prm.y;
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn) {
-    const int col = n0 + (wn * TN + tn) * 32 + l31;
-    if (col >= N) continue;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-      const int mb = m0 + (wm * TM + tm) * 32 + 4 * lh;
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int m = mb + (reg & 3) + 8 * (reg >> 2);
-        if (m >= M) continue;
-        const long long idx = (long long)m * N + col;
-        out[idx] = sq.partial ? ssq[tm][tn][reg] : out[idx] + ssq[tm][tn][reg];
-      }
-    }
-  }
+  const int N = prm.N, M = prm.M;
+  float* out = sq.partial ? sq.partial + (long long)blockIdx.y * M * N : prm.y;
+  map.each([&](int tm, int tn, int reg, int m, int col) {
+    if (m >= M || col >= N) return;
+    const long long idx = (long long)m * N + col;
+    out[idx] = sq.partial ? ssq[tm][tn][reg] : out[idx] + ssq[tm][tn][reg];
+  });
+}
+
+// Offset of a_i[m], the im2col row of a dense layer's single output pixel (OH*OW == 1), within example i's
+// activations; -1 when the tap (kh, kw) of m lies in the padding.
+__device__ __forceinline__ long long dense_tap_offset(const WgradP& prm, int m) {
+  const int tap = m / prm.C, ci = m - tap * prm.C;
+  const int kh = tap / prm.KW, kw = tap - kh * prm.KW;
+  const int ih = kh - prm.pad_h, iw = kw - prm.pad_w;
+  return (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW) ? ((long long)ih * prm.IW + iw) * prm.C + ci : -1;
 }
 
 // Dense weight gradients (OH*OW == 1): the per-example gradient is the outer product of the im2col row a_i (M) and
@@ -3411,13 +3414,7 @@ __global__ __launch_bounds__(256) void wgrad_sqsum_dense_kernel(const WgradP prm
   const int bc = c0 + tid;
   const float sc = (tid < 64 && bc < N && prm.scale) ? prm.scale[bc] : 1.f;
   const int am = m0 + tid - 64;
-  long long aoff = -1;                  // offset of a_i[am] within example i's activations (-1: padding / out of range)
-  if (tid >= 64 && tid < 96 && am < M) {
-    const int tap = am / prm.C, ci = am - tap * prm.C;
-    const int kh = tap / prm.KW, kw = tap - kh * prm.KW;
-    const int ih = kh - prm.pad_h, iw = kw - prm.pad_w;
-    if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW) aoff = ((long long)ih * prm.IW + iw) * prm.C + ci;
-  }
+  const long long aoff = (tid >= 64 && tid < 96 && am < M) ? dense_tap_offset(prm, am) : -1;
   const long long img = (long long)prm.IH * prm.IW * prm.C;
   for (int i = 0; i < n_img; ++i) {
     if (tid < 64) {
@@ -3447,22 +3444,10 @@ __global__ __launch_bounds__(256) void wgrad_sqsum_dense_kernel(const WgradP prm
   }
 }
 
-// groups of (probe, example) pairs for a launch of `blocks_per_group` blocks per group: fill SQ_TARGET_BLOCKS.
-// Returns the group bound min(pairs, ceil(SQ_TARGET_BLOCKS / blocks)) — monotone in `pairs`, so the scratch sized for
-// the largest pass serves every smaller one — and the launch's G <= bound after rounding to whole groups.
-static long long sq_groups(long long blocks_per_group, long long pairs, int& G, int& per) {
-  long long g = (SQ_TARGET_BLOCKS + blocks_per_group - 1) / blocks_per_group;
-  if (g > pairs) g = pairs;
-  if (g < 1) g = 1;
-  per = (int)((pairs + g - 1) / g);
-  G = (int)((pairs + per - 1) / per);
-  return g;
-}
-
+// scratch floats: the monotone group bound of pair_groups (not one launch's G) x the matrix; none for a single group
 long long wgrad_sqsum_scratch(int M, int N, int OHW, long long pairs) {
   if (OHW == 1 || M <= 0 || N <= 0 || pairs <= 0) return 0;
-  int G, per;
-  const long long bound = sq_groups(wgrad_tile_count(M, N), pairs, G, per);
+  const long long bound = pair_groups(wgrad_tile_count(M, N), pairs).bound;
   return bound > 1 ? bound * M * N : 0;
 }
 
@@ -3470,16 +3455,11 @@ template <int WM, int WN, int TM, int TN>
 static hipError_t run_wgrad_sqsum(Tile<WM, WN, TM, TN>, const WgradP& p, int P, int n_img, float* scratch,
                                   long long scratch_floats, hipStream_t st) {
   using T = Tile<WM, WN, TM, TN>;
-  const long long tiles = (long long)((p.M + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN);
-  const long long pairs = (long long)P * n_img;
-  int G, per;
-  sq_groups(tiles, pairs, G, per);
+  const long long tiles = wgrad_tile_count(p.M, p.N);
   SqGroupP sq;
-  sq.pairs = (int)pairs; sq.per = per; sq.n_img = n_img;
-  sq.partial = nullptr;
-  const long long need = G > 1 ? (long long)G * p.M * p.N : 0;
-  if (need > scratch_floats || (need && !scratch)) return hipErrorInvalidValue;
-  if (G > 1) sq.partial = scratch;
+  const int G = pair_launch_groups(sq, tiles, P, n_img);
+  if (!scratch_fits(G > 1 ? (long long)G * p.M * p.N : 0, scratch, scratch_floats)) return hipErrorInvalidValue;
+  sq.partial = G > 1 ? scratch : nullptr;
   LIP_ROUTE("wgrad_sqsum<%d,%d,%d,%d>", WM, WN, TM, TN);
   hipLaunchKernelGGL((wgrad_sqsum_kernel<WM, WN, TM, TN>), dim3((unsigned)tiles, (unsigned)G), dim3(T::NT), 0, st, p, sq);
   hipError_t e = hipGetLastError();
@@ -3488,7 +3468,7 @@ static hipError_t run_wgrad_sqsum(Tile<WM, WN, TM, TN>, const WgradP& p, int P, 
 }
 
 hipError_t launch_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch, long long scratch_floats, hipStream_t st) {
-  if (P <= 0 || n_img <= 0 || p.OHW * n_img != p.R || (long long)P * n_img >= (1ll << 31)) return hipErrorInvalidValue;
+  if (!pair_launch_ok(P, n_img, p.OHW, p.R)) return hipErrorInvalidValue;
   if (p.OHW == 1) {
     dim3 grid((unsigned)((p.N + 63) / 64), (unsigned)((p.M + 31) / 32));
     LIP_ROUTE("wgrad_sqsum_dense");
@@ -3500,15 +3480,10 @@ hipError_t launch_wgrad_sqsum(const WgradP& p, int P, int n_img, float* scratch,
                          [&](auto tile, int) { return run_wgrad_sqsum(tile, p, P, n_img, scratch, scratch_floats, st); });
 }
 
-// ------------------------------------------------------------------------------------------
-// weighted square norm of the per-example weight gradient (lip_vjp_wnorm):
-//   out[(p, i)] += sum_{m, c} w[m][c] ( s[c] * sum_{pix of example i} im2col(a_i)[pix][m] g_pi[pix][c] )^2
-// The per-(probe, example) MFMA tile of wgrad_sqsum_kernel (the same wgrad_accumulate_rows call); the other
-// reduction of its squares: the block's w tile is loaded once into registers, after each pair the tile is scaled,
-// squared, multiplied by w and summed over the tile (lanes by shuffles, waves in wave order through LDS) to ONE float,
-// stored to partial[tile][pair] (plain store).  wnorm_finish adds the tiles of a pair in tile order.  No atomics.
-// grid = (output tiles, groups of pairs); w == null: weight 1.
-// ------------------------------------------------------------------------------------------
+// weighted square norm (lip_vjp_wnorm):  out[(p, i)] += sum_{m, c} w[m][c] (s[c] t_pi[m][c])^2.  The block's w tile
+// times s^2 is loaded once into registers in the accumulator layout (0 outside the matrix); fold: the tile is squared,
+// weighted and summed over the block (lanes by shuffles, waves in wave order through LDS) to ONE float, stored to
+// partial[tile][pair].  wnorm_finish adds the tiles of a pair in tile order.  w == null: weight 1.
 struct WnGroupP : PairGroupP {
   const float* w;                       // the op's (M, N) slice of the weight vector, or null (all ones)
   float* partial;                       // [tiles][pairs]
@@ -3517,47 +3492,24 @@ struct WnGroupP : PairGroupP {
 template <int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(WM * WN * 64) void wgrad_wnorm_kernel(const WgradP prm, const WnGroupP wn_) {
   using T = Tile<WM, WN, TM, TN>;
-  constexpr int BM = T::BM, BN = T::BN;
-  __shared__ __attribute__((aligned(16))) float As[BK * (BM + 4)];
-  __shared__ float Bs[BK * BN];
+  __shared__ __attribute__((aligned(16))) float As[BK * (T::BM + 4)];
+  __shared__ float Bs[BK * T::BN];
   __shared__ float wsum[WM * WN];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
+  const WgradBlock<WM, WN, TM, TN> b(prm.N);
+  const AccMap<TM, TN> map = b.map();
   const int N = prm.N, M = prm.M;
-  const int tiles_n = (N + BN - 1) / BN;
-  const int tile_n = blockIdx.x % tiles_n, tile_m = blockIdx.x / tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int q0 = blockIdx.y * wn_.per, q1 = min(wn_.pairs, q0 + wn_.per);
-  const int l31 = lane & 31, lh = lane >> 5;
 
-  // the block's weights in the accumulator layout, times the squared column scale; 0 outside the (M, N) matrix
-  f32x16 acc[TM][TN], wt[TM][TN];
-#pragma unroll
-  for (int tn = 0; tn < TN; ++tn) {
-    const int col = n0 + (wn * TN + tn) * 32 + l31;
-    const float sc = (prm.scale && col < N) ? prm.scale[col] : 1.f;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-      const int mb = m0 + (wm * TM + tm) * 32 + 4 * lh;
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int m = mb + (reg & 3) + 8 * (reg >> 2);
-        float v = 0.f;
-        if (m < M && col < N) v = (wn_.w ? wn_.w[(long long)m * N + col] : 1.f) * (sc * sc);
-        wt[tm][tn][reg] = v;
-      }
-    }
-  }
+  float scv[TN];
+  acc_col_scales(prm, map, scv);
+  f32x16 wt[TM][TN];
+  map.each([&](int tm, int tn, int reg, int m, int col) {
+    float v = 0.f;
+    if (m < M && col < N) v = (wn_.w ? wn_.w[(long long)m * N + col] : 1.f) * (scv[tn] * scv[tn]);
+    wt[tm][tn][reg] = v;
+  });
 
-  const WgradTap tap = wgrad_tap<BM>(prm, m0, tid);
   float* part = wn_.partial + (long long)blockIdx.x * wn_.pairs;
-  for (int q = q0; q < q1; ++q) {
-    const int p = q / wn_.n_img, i = q - p * wn_.n_img;
-    zero_acc(acc);
-    // its leading barrier also orders the previous pair's last sweep and wave sums before these LDS stores
-    wgrad_accumulate_rows<WM, WN, TM, TN>(prm, tap, prm.g + (long long)p * prm.g_ps, i * prm.OHW, (i + 1) * prm.OHW, n0,
-                                          As, Bs, acc);
+  wgrad_pair_walk<WM, WN, TM, TN>(prm, wn_, b, As, Bs, [&](int q, const f32x16 (&acc)[TM][TN]) {
     float s = 0.f;
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
@@ -3569,15 +3521,15 @@ __global__ __launch_bounds__(WM * WN * 64) void wgrad_wnorm_kernel(const WgradP 
           s = fmaf(wt[tm][tn][r] * v, v, s);
         }
     s = wave_sum(s);
-    if (lane == 0) wsum[wave] = s;
+    if (b.lane == 0) wsum[b.wave] = s;
     __syncthreads();
-    if (tid == 0) {
+    if (b.tid == 0) {
       float t = 0.f;
 #pragma unroll
       for (int k = 0; k < WM * WN; ++k) t += wsum[k];
       part[q] = t;
     }
-  }
+  });
 }
 
 // Dense weight gradients (OH*OW == 1): the per-example gradient is the outer product of a_i (M) and s * g_pi (N), so the
@@ -3597,13 +3549,8 @@ __global__ __launch_bounds__(256) void wgrad_wnorm_dense_kernel(const WgradP prm
   float t = 0.f;
   for (int mb = 0; mb < M; mb += 256) {
     const int m = mb + tid;
-    float a = 0.f;
-    if (m < M) {
-      const int tap = m / prm.C, ci = m - tap * prm.C;
-      const int kh = tap / prm.KW, kw = tap - kh * prm.KW;
-      const int ih = kh - prm.pad_h, iw = kw - prm.pad_w;
-      if (ih >= 0 && ih < prm.IH && iw >= 0 && iw < prm.IW) a = prm.a[(long long)i * img + ((long long)ih * prm.IW + iw) * prm.C + ci];
-    }
+    const long long aoff = m < M ? dense_tap_offset(prm, m) : -1;
+    const float a = aoff >= 0 ? prm.a[(long long)i * img + aoff] : 0.f;
     As2[tid] = a * a;
     __syncthreads();
     const int mend = min(256, M - mb);
@@ -3623,45 +3570,38 @@ __global__ __launch_bounds__(256) void wgrad_wnorm_dense_kernel(const WgradP prm
   }
 }
 
+// (a generic lambda cannot name the template arguments of its tile: this function deduces them for the launch)
+template <int WM, int WN, int TM, int TN>
+static void launch_wgrad_wnorm_tile(Tile<WM, WN, TM, TN>, dim3 grid, const WgradP& p, const WnGroupP& wn, hipStream_t st) {
+  hipLaunchKernelGGL((wgrad_wnorm_kernel<WM, WN, TM, TN>), grid, dim3(WM * WN * 64), 0, st, p, wn);
+}
+
 long long wgrad_wnorm_tiles(int M, int N, int OHW) {
   if (M <= 0 || N <= 0) return 0;
   if (OHW == 1) return (N + 63) / 64;
   return wgrad_tile_count(M, N);
 }
 
-template <int WM, int WN, int TM, int TN>
-static hipError_t run_wgrad_wnorm(Tile<WM, WN, TM, TN>, int route, const WgradP& p, int P, int n_img, const float* w, float* out,
-                                  float* scratch, long long scratch_floats, hipStream_t st) {
-  using T = Tile<WM, WN, TM, TN>;
-  const long long tiles = (long long)((p.M + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN);
-  const long long pairs = (long long)P * n_img;
-  if (tiles * pairs > scratch_floats) return hipErrorInvalidValue;
-  int G, per;
-  sq_groups(tiles, pairs, G, per);
-  WnGroupP wn;
-  wn.w = w; wn.partial = scratch; wn.pairs = (int)pairs; wn.per = per; wn.n_img = n_img;
-  wnorm_route_hit(route);
-  hipLaunchKernelGGL((wgrad_wnorm_kernel<WM, WN, TM, TN>), dim3((unsigned)tiles, (unsigned)G), dim3(T::NT), 0, st, p, wn);
+hipError_t launch_wgrad_wnorm(const WgradP& p, int P, int n_img, const float* w, float* out, float* scratch,
+                              long long scratch_floats, hipStream_t st) {
+  if (!out || !pair_launch_ok(P, n_img, p.OHW, p.R)) return hipErrorInvalidValue;
+  const long long tiles = wgrad_wnorm_tiles(p.M, p.N, p.OHW), pairs = (long long)P * n_img;
+  if (!scratch || !scratch_fits(tiles * pairs, scratch, scratch_floats)) return hipErrorInvalidValue;
+  if (p.OHW == 1) {
+    wnorm_route_hit(WN_WGRAD_DENSE);
+    hipLaunchKernelGGL(wgrad_wnorm_dense_kernel, dim3((unsigned)n_img, (unsigned)tiles), dim3(256), 0, st, p, w, P, n_img, scratch);
+  } else {
+    WnGroupP wn;
+    wn.w = w; wn.partial = scratch;
+    const int G = pair_launch_groups(wn, tiles, P, n_img);
+    with_wgrad_tile(p.M, p.N, [&](auto tile, int route) {
+      wnorm_route_hit(route);
+      launch_wgrad_wnorm_tile(tile, dim3((unsigned)tiles, (unsigned)G), p, wn, st);
+    });
+  }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return launch_wnorm_finish(scratch, (int)tiles, pairs, out, st);
-}
-
-hipError_t launch_wgrad_wnorm(const WgradP& p, int P, int n_img, const float* w, float* out, float* scratch,
-                              long long scratch_floats, hipStream_t st) {
-  if (P <= 0 || n_img <= 0 || p.OHW * n_img != p.R || (long long)P * n_img >= (1ll << 31) || !out || !scratch) return hipErrorInvalidValue;
-  if (p.OHW == 1) {
-    const long long tiles = (p.N + 63) / 64, pairs = (long long)P * n_img;
-    if (tiles * pairs > scratch_floats) return hipErrorInvalidValue;
-    wnorm_route_hit(WN_WGRAD_DENSE);
-    hipLaunchKernelGGL(wgrad_wnorm_dense_kernel, dim3((unsigned)n_img, (unsigned)tiles), dim3(256), 0, st, p, w, P, n_img, scratch);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_wnorm_finish(scratch, (int)tiles, pairs, out, st);
-  }
-  return with_wgrad_tile(p.M, p.N, [&](auto tile, int route) {
-    return run_wgrad_wnorm(tile, route, p, P, n_img, w, out, scratch, scratch_floats, st);
-  });
 }
 
 }  // namespace lip

@@ -83,27 +83,24 @@ hipError_t launch_reduce(const ReduceP& p0, int P, hipStream_t st) {
   return hipGetLastError();
 }
 
-// ---- square-accumulating segmented reduce (lip_vjp_sqsum) ----------------------------------------------------------
-//   red0[c] += sum_{(p, i)} (sum_{r < R} g[p][i][r][c])^2 ,   red1[c] += sum_{(p, i)} (sum_r g[p][i][r][c] xhat[i][r][c])^2
-// Block = `cb` columns x (256 / cb) row lanes and a fixed group of (probe, example) pairs, taken in order: per pair the
-// row lanes sum strided rows, the lane sums meet in LDS and are added in lane order, squared and accumulated by row
-// lane 0.  One partial per group (plain stores) or, for a single group, added into the output directly.
-struct SqRedP {
-  float* part0; float* part1;           // [groups][N] each, or null: one group
-  int pairs, per, n_img, cb;
+// ---- per-pair segmented reduces (lip_vjp_sqsum, lip_vjp_wnorm) -----------------------------------------------------
+// Per (probe p, example i) pair the column sums  u0[c] = sum_{r < R} g[p][i][r][c],  u1[c] = sum_r g[p][i][r][c] xhat[i][r][c].
+// Block = `cb` columns x (256 / cb) row lanes and the pairs of its group (PairGroupP), taken in order: per pair the row
+// lanes sum strided rows and leave their sums in LDS; fold(q, sums) then runs on every thread between two barriers, and
+// sums(u0, u1) adds the row lanes of the caller's column in lane order.  The kernels below differ in the fold only.
+struct RedGroupP : PairGroupP {
+  int cb;
 };
 
-__global__ __launch_bounds__(256) void reduce_sqsum_kernel(const ReduceP prm, const SqRedP sq) {
-  __shared__ float s0[256], s1[256];
-  const int N = prm.N, cb = sq.cb, RL = 256 / cb;
+template <class Fold>
+__device__ __forceinline__ void reduce_pair_walk(const ReduceP& prm, const RedGroupP& pg, float* s0, float* s1, Fold&& fold) {
+  const int N = prm.N, cb = pg.cb, RL = 256 / cb;
   const int cl = threadIdx.x % cb, rl = threadIdx.x / cb;
   const int c = blockIdx.x * cb + cl;
-  const int grp = blockIdx.y;
-  const int q0 = grp * sq.per, q1 = min(sq.pairs, q0 + sq.per);
+  const int q0 = blockIdx.y * pg.per, q1 = min(pg.pairs, q0 + pg.per);
   const bool on = c < N;
-  float a0 = 0.f, a1 = 0.f;
   for (int q = q0; q < q1; ++q) {
-    const int p = q / sq.n_img, i = q - p * sq.n_img;
+    const int p = q / pg.n_img, i = q - p * pg.n_img;
     const long long seg = (long long)i * prm.R * N;
     const float* g = prm.g + (long long)p * prm.g_ps + seg;
     const float* xh = prm.xhat ? prm.xhat + seg : nullptr;
@@ -116,14 +113,33 @@ __global__ __launch_bounds__(256) void reduce_sqsum_kernel(const ReduceP prm, co
       }
     s0[threadIdx.x] = t0; s1[threadIdx.x] = t1;
     __syncthreads();
-    if (rl == 0) {
-      float u0 = 0.f, u1 = 0.f;
+    fold(q, [&](float& u0, float& u1) {
+      u0 = u1 = 0.f;
       for (int k = 0; k < RL; ++k) { u0 += s0[k * cb + cl]; u1 += s1[k * cb + cl]; }
+    });
+    __syncthreads();                    // the next pair's lane sums overwrite s0 / s1
+  }
+}
+
+// square-accumulating:  red0[c] += sum_{(p, i)} u0[c]^2 ,  red1[c] += sum_{(p, i)} u1[c]^2.  Row lane 0 squares and
+// accumulates; one partial per group (plain stores) or, for a single group, added into the output directly.
+struct SqRedP : RedGroupP {
+  float* part0; float* part1;           // [groups][N] each, or null: one group
+};
+
+__global__ __launch_bounds__(256) void reduce_sqsum_kernel(const ReduceP prm, const SqRedP sq) {
+  __shared__ float s0[256], s1[256];
+  const int N = prm.N, grp = blockIdx.y;
+  const int c = blockIdx.x * sq.cb + threadIdx.x % sq.cb, rl = threadIdx.x / sq.cb;
+  float a0 = 0.f, a1 = 0.f;
+  reduce_pair_walk(prm, sq, s0, s1, [&](int, auto sums) {
+    if (rl == 0) {
+      float u0, u1;
+      sums(u0, u1);
       a0 = fmaf(u0, u0, a0); a1 = fmaf(u1, u1, a1);
     }
-    __syncthreads();
-  }
-  if (rl != 0 || !on) return;
+  });
+  if (rl != 0 || c >= N) return;
   if (sq.part0) {
     if (prm.red0) sq.part0[(long long)grp * N + c] = a0;
     if (prm.red1) sq.part1[(long long)grp * N + c] = a1;
@@ -138,41 +154,26 @@ static int sq_cb(int N) {
   while (cb > 1 && cb / 2 >= N) cb >>= 1;
   return cb;
 }
-
-// returns the group bound min(pairs, ceil(SQ_TARGET_BLOCKS / column blocks)) (monotone in `pairs`: the scratch size);
-// the launch's G <= bound after rounding to whole groups
-static long long sq_red_groups(int N, long long pairs, int& cb, int& G, int& per) {
-  cb = sq_cb(N);
-  const long long colblocks = (N + cb - 1) / cb;
-  long long g = (SQ_TARGET_BLOCKS + colblocks - 1) / colblocks;
-  if (g > pairs) g = pairs;
-  if (g < 1) g = 1;
-  per = (int)((pairs + g - 1) / g);
-  G = (int)((pairs + per - 1) / per);
-  return g;
-}
+static long long sq_colblocks(int N) { return (N + sq_cb(N) - 1) / sq_cb(N); }
 
 long long reduce_sqsum_scratch(int N, long long pairs) {
   if (N <= 0 || pairs <= 0) return 0;
-  int cb, G, per;
-  const long long bound = sq_red_groups(N, pairs, cb, G, per);
+  const long long bound = pair_groups(sq_colblocks(N), pairs).bound;
   return bound > 1 ? 2ll * bound * N : 0;
 }
 
 hipError_t launch_reduce_sqsum(const ReduceP& p, int P, float* scratch, long long scratch_floats, hipStream_t st) {
   if (!p.red0 && !p.red1) return hipSuccess;
-  const long long pairs = (long long)P * p.nseg;
-  if (P <= 0 || p.nseg <= 0 || p.N <= 0 || p.R <= 0 || pairs >= (1ll << 31)) return hipErrorInvalidValue;
+  if (p.N <= 0 || !pair_launch_ok(P, p.nseg, p.R)) return hipErrorInvalidValue;
   SqRedP sq;
-  int G, per;
-  sq_red_groups(p.N, pairs, sq.cb, G, per);
-  sq.pairs = (int)pairs; sq.per = per; sq.n_img = p.nseg;
-  sq.part0 = sq.part1 = nullptr;
-  const long long need = G > 1 ? 2ll * G * p.N : 0;
-  if (need > scratch_floats || (need && !scratch)) return hipErrorInvalidValue;
-  if (G > 1) { sq.part0 = scratch; sq.part1 = scratch + (long long)G * p.N; }
+  sq.cb = sq_cb(p.N);
+  const long long tiles = sq_colblocks(p.N);
+  const int G = pair_launch_groups(sq, tiles, P, p.nseg);
+  if (!scratch_fits(G > 1 ? 2ll * G * p.N : 0, scratch, scratch_floats)) return hipErrorInvalidValue;
+  sq.part0 = G > 1 ? scratch : nullptr;
+  sq.part1 = G > 1 ? scratch + (long long)G * p.N : nullptr;
   LIP_ROUTE("reduce_sqsum");
-  hipLaunchKernelGGL(reduce_sqsum_kernel, dim3((unsigned)((p.N + sq.cb - 1) / sq.cb), (unsigned)G), dim3(256), 0, st, p, sq);
+  hipLaunchKernelGGL(reduce_sqsum_kernel, dim3((unsigned)tiles, (unsigned)G), dim3(256), 0, st, p, sq);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || G == 1) return e;
   if (p.red0 && (e = launch_sqsum_finish(sq.part0, G, p.N, p.red0, st)) != hipSuccess) return e;
@@ -197,70 +198,47 @@ hipError_t launch_sqsum_finish(const float* partial, int G, long long len, float
   return hipGetLastError();
 }
 
-// ---- weighted square norm of the segmented reduce (lip_vjp_wnorm) ---------------------------------------------------
-//   out[(p, i)] += sum_c  w0[c] (sum_{r < R} g[p][i][r][c])^2 + w1[c] (sum_r g[p][i][r][c] xhat[i][r][c])^2
-// The block of reduce_sqsum_kernel (cb columns x 256 / cb row lanes, a fixed group of pairs in order); per pair the
-// column sums are squared, weighted and summed over the block's columns (they sit in wave 0: shuffles) to one float,
-// stored to partial[column block][pair].  wnorm_finish adds the column blocks of a pair in order.
-struct WnRedP {
+// weighted square norm:  out[(p, i)] += sum_c  w0[c] u0[c]^2 + w1[c] u1[c]^2.  Per pair the column sums are squared,
+// weighted and summed over the block's columns (they sit in wave 0: shuffles) to one float, stored to
+// partial[column block][pair].  wnorm_finish adds the column blocks of a pair in order.
+struct WnRedP : RedGroupP {
   const float* w0; const float* w1;     // the (N,) weight slices of red0 / red1, or null (all ones)
   int has0, has1;
   float* partial;                       // [column blocks][pairs]
-  int pairs, per, n_img, cb;
 };
 
 __global__ __launch_bounds__(256) void reduce_wnorm_kernel(const ReduceP prm, const WnRedP wn) {
   __shared__ float s0[256], s1[256];
-  const int N = prm.N, cb = wn.cb, RL = 256 / cb;
-  const int cl = threadIdx.x % cb, rl = threadIdx.x / cb;
-  const int c = blockIdx.x * cb + cl;
-  const int q0 = blockIdx.y * wn.per, q1 = min(wn.pairs, q0 + wn.per);
-  const bool on = c < N;
-  const bool lead = rl == 0 && on;      // (rl == 0: threads 0 .. cb - 1, cb <= 64 — all in wave 0)
+  const int c = blockIdx.x * wn.cb + threadIdx.x % wn.cb;
+  const bool lead = threadIdx.x / wn.cb == 0 && c < prm.N;      // (row lane 0: threads 0 .. cb - 1, cb <= 64 — all in wave 0)
   const float w0 = (lead && wn.has0) ? (wn.w0 ? wn.w0[c] : 1.f) : 0.f;
   const float w1 = (lead && wn.has1) ? (wn.w1 ? wn.w1[c] : 1.f) : 0.f;
   float* part = wn.partial + (long long)blockIdx.x * wn.pairs;
-  for (int q = q0; q < q1; ++q) {
-    const int p = q / wn.n_img, i = q - p * wn.n_img;
-    const long long seg = (long long)i * prm.R * N;
-    const float* g = prm.g + (long long)p * prm.g_ps + seg;
-    const float* xh = prm.xhat ? prm.xhat + seg : nullptr;
-    float t0 = 0.f, t1 = 0.f;
-    if (on)
-      for (int r = rl; r < prm.R; r += RL) {
-        const float v = g[(long long)r * N + c];
-        t0 += v;
-        if (xh) t1 = fmaf(v, xh[(long long)r * N + c], t1);
-      }
-    s0[threadIdx.x] = t0; s1[threadIdx.x] = t1;
-    __syncthreads();
+  reduce_pair_walk(prm, wn, s0, s1, [&](int q, auto sums) {
     if (threadIdx.x < 64) {
       float v = 0.f;
       if (lead) {
-        float u0 = 0.f, u1 = 0.f;
-        for (int k = 0; k < RL; ++k) { u0 += s0[k * cb + cl]; u1 += s1[k * cb + cl]; }
+        float u0, u1;
+        sums(u0, u1);
         v = fmaf(w0 * u0, u0, w1 * u1 * u1);
       }
       v = wave_sum(v);
       if (threadIdx.x == 0) part[q] = v;
     }
-    __syncthreads();
-  }
+  });
 }
 
-long long reduce_wnorm_tiles(int N) { return N > 0 ? (N + sq_cb(N) - 1) / sq_cb(N) : 0; }
+long long reduce_wnorm_tiles(int N) { return N > 0 ? sq_colblocks(N) : 0; }
 
 hipError_t launch_reduce_wnorm(const ReduceP& p, int P, bool ones, float* out, float* scratch, long long scratch_floats,
                                hipStream_t st) {
   if (!p.red0 && !p.red1) return hipSuccess;
-  const long long pairs = (long long)P * p.nseg;
-  if (P <= 0 || p.nseg <= 0 || p.N <= 0 || p.R <= 0 || pairs >= (1ll << 31) || !out || !scratch) return hipErrorInvalidValue;
+  if (p.N <= 0 || !out || !pair_launch_ok(P, p.nseg, p.R)) return hipErrorInvalidValue;
   WnRedP wn;
-  int G, per;
-  sq_red_groups(p.N, pairs, wn.cb, G, per);
-  const long long tiles = (p.N + wn.cb - 1) / wn.cb;
-  if (tiles * pairs > scratch_floats) return hipErrorInvalidValue;
-  wn.pairs = (int)pairs; wn.per = per; wn.n_img = p.nseg;
+  wn.cb = sq_cb(p.N);
+  const long long tiles = sq_colblocks(p.N), pairs = (long long)P * p.nseg;
+  const int G = pair_launch_groups(wn, tiles, P, p.nseg);
+  if (!scratch_fits(tiles * pairs, scratch, scratch_floats)) return hipErrorInvalidValue;
   wn.has0 = p.red0 != nullptr; wn.has1 = p.red1 != nullptr;
   wn.w0 = ones ? nullptr : p.red0; wn.w1 = ones ? nullptr : p.red1;
   wn.partial = scratch;

@@ -278,28 +278,26 @@ def test_every_sqsum_route_runs_on_a_non_square_map():
         assert all(net.tensors[u.src][0] != net.tensors[u.src][1] for u in net.units if u.kind == "conv" and u.kh > 1)
 
 
-@pytest.mark.parametrize("which", ["a", "b", "c", "d"])
-def test_sqsum_and_rows_routes(which):
-    """lip_vjp_sqsum element by element against float64 squares of the emulator's per-example rows, lip_vjp_rows
-    against those rows; the census shows the square-sum routes."""
-    net = _net_of(which)
-    n, P = 3, 2
-    eng, tm, slices = _bind(net, n, 7, P)
-    U = torch.randn(P, n, eng.K, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
-    rows = torch.zeros(P, n, eng.D, dtype=torch.float64)
+def _emulator_rows(tm, U):
+    """the float64 per-example rows (P, n, D) of the tape emulator, one example at a time"""
+    P, n = U.shape[:2]
+    rows = torch.zeros(P, n, tm.cn.D, dtype=torch.float64)
     for i in range(n):
         Ui = torch.zeros_like(U)
         Ui[:, i] = U[:, i]
         rows[:, i] = tm.vjp(Ui, nv.HEAD_L, 0.7)
+    return rows
+
+
+def _check_sqsum(eng, U, rows, slices, what):
+    """lip_vjp_sqsum ADDED to a pre-filled buffer, element by element against the float64 squares of `rows`, and a
+    second run bitwise equal"""
     ref = (rows ** 2).sum((0, 1))
-    lib = eng.lib
-    all_routes(lib)                                  # clear the census
     y0 = (torch.rand(eng.D, dtype=torch.float64, generator=torch.Generator().manual_seed(5)) * ref).float().cuda()
     got = eng.vjp_sqsum(U, "l", 0.7, out=y0.clone())  # the square sum is ADDED to y0
     torch.cuda.synchronize()
-    census = set(_census(lib))
     want = y0.double().cpu() + ref
-    _per_tensor(got, want[None], slices, 1e-5, f"sqsum net {which}")
+    _per_tensor(got, want[None], slices, 1e-5, what)
     # element by element: a row element r with error e <= k 2^-24 max|r| (its tensor's rows) moves r^2 by ~2 |r| e, so
     # |y_j - want_j| <= 2^-24 (K_SQ sum_{p,i} |r_pij| max_t|r| + 4 want_j)
     err = (got.double().cpu() - want).abs()
@@ -308,15 +306,131 @@ def test_sqsum_and_rows_routes(which):
     for name, a, b in slices:
         unit[a:b] = 2.0 ** -24 * sabs[a:b] * rows[:, :, a:b].abs().max()
     worst = ((err - 2.0 ** -24 * 4 * want).clamp_min(0) / unit.clamp_min(1e-300)).max().item()
-    print(f"sqsum net {which}: worst error {worst:.3g} x 2^-24 sum|r| max|r|")
+    print(f"{what}: worst error {worst:.3g} x 2^-24 sum|r| max|r|")
     assert (err <= K_SQ * unit + 2.0 ** -24 * 4 * want + 1e-30).all(), \
-        f"sqsum net {which}: worst error {worst:.3g} x 2^-24 sum|r| max|r| > {K_SQ}"
+        f"{what}: worst error {worst:.3g} x 2^-24 sum|r| max|r| > {K_SQ}"
     again = eng.vjp_sqsum(U, "l", 0.7, out=y0.clone())
     assert torch.equal(again, got), "lip_vjp_sqsum is not bitwise reproducible"
+
+
+@pytest.mark.parametrize("which", ["a", "b", "c", "d"])
+def test_sqsum_and_rows_routes(which):
+    """lip_vjp_sqsum element by element against float64 squares of the emulator's per-example rows, lip_vjp_rows
+    against those rows; the census shows the square-sum routes."""
+    net = _net_of(which)
+    n, P = 3, 2
+    eng, tm, slices = _bind(net, n, 7, P)
+    U = torch.randn(P, n, eng.K, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+    rows = _emulator_rows(tm, U)
+    lib = eng.lib
+    all_routes(lib)                                  # clear the census
+    _check_sqsum(eng, U, rows, slices, f"sqsum net {which}")
+    census = set(_census(lib))
     r = eng.vjp_rows(U, "l", 0.7)
     _per_tensor(r, rows.reshape(P * n, -1), slices, 2e-5, f"rows net {which}")
     want = SQSUM_NETS[which]
     assert want <= census, f"net {which}: square-sum routes {sorted(want - census)} not taken (census {sorted(census)})"
+
+
+# ---- several pairs per block: the in-block loop over (probe, example) pairs of the per-pair kernels ----------------
+# At n = 3, P = 2 every group of the nets above holds ONE pair.  47 probes of 11 examples are 517 pairs: with the grouping
+# rule of lip_internal.h every grouped launch of nets a and b then walks 2, 4 or 7 pairs per block and ends on a short
+# group (blocks per group 1: per 2, G 259, last 1; 3: per 4, G 130, last 1; 6: per 7, G 74, last 6).
+MANY_P, MANY_N = 47, 11
+SQ_TARGET_BLOCKS = 512                              # lip_internal.h
+
+
+def _pair_groups(blocks, pairs):
+    """pair_groups of lip_internal.h: (per, G)"""
+    g = max(1, min(pairs, -(-SQ_TARGET_BLOCKS // blocks)))
+    per = -(-pairs // g)
+    return per, -(-pairs // per)
+
+
+def _grouped_launches(net):
+    """(label, blocks per group) of every grouped launch of the per-pair kernels on `net`: the weight-gradient tile
+    of each conv with more than one output pixel (with_wgrad_tile of lip_mfma.hip) and the bias reduces (sq_cb of
+    lip_small.hip)"""
+    for u in net.units:
+        if u.kind != "conv":
+            continue
+        name = u.kernel[-2]
+        M, N = u.kh * u.kw * u.cin, u.cout
+        oh, ow, _ = net.tensors[u.dst]
+        if oh * ow > 1:
+            bm, bn = (64 if M <= 64 else 128), (128 if N > 64 else 64 if N > 32 else 32)
+            yield f"{name} wgrad", -(-M // bm) * -(-N // bn)
+        if u.bias is not None:
+            cb = 64
+            while cb > 1 and cb // 2 >= N:
+                cb //= 2
+            yield f"{name} bias", -(-N // cb)
+
+
+def assert_several_pairs_per_group(net, pairs):
+    launches = list(_grouped_launches(net))
+    assert any(l.endswith("wgrad") for l, _ in launches) and any(l.endswith("bias") for l, _ in launches)
+    for label, blocks in launches:
+        per, G = _pair_groups(blocks, pairs)
+        assert per >= 2 and pairs % per != 0 and G > 1, f"{label}: {blocks} blocks per group, per {per}, G {G}"
+
+
+_MANY = {}
+
+
+def many_pairs(which):
+    """(engine, parameter slices, U, float64 emulator rows) of net `which` at 517 pairs; computed once, shared with
+    tests/test_wnorm.py.  The emulator runs a tape compiled for ONE example on each example in turn (nothing in these
+    nets couples the examples), which costs 1 / n of walking the n-example tape n times."""
+    if which not in _MANY:
+        from lip_amd.engine import LinearizedNet, build_consts, compile_net
+        from lip_amd.toymodels import create_state
+        from lip_amd.utils import flatten_nn_params
+        from tape_emulator import TapeMachine
+        net, P, n = _net_of(which), MANY_P, MANY_N
+        state = create_state(net, 7, dtype=torch.float64)
+        Z = torch.rand(n, *net.tensors[0], dtype=torch.float64, generator=torch.Generator().manual_seed(7))
+        eng = LinearizedNet(state, Z, "classifier", workspace_bytes=1 << 28, max_chunk=P)
+        assert eng.chunk == P, eng.chunk                # one pass: every launch sees all 517 pairs
+        U = torch.randn(P, n, eng.K, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+        cn1 = compile_net(net, 1, state.params)
+        flat, _ = flatten_nn_params(state.params)
+        consts = build_consts(cn1, state.params, state.batch_stats, "cpu", torch.float64)
+        rows = torch.zeros(P, n, eng.D, dtype=torch.float64)
+        for i in range(n):
+            tm = TapeMachine(cn1, flat, consts, Z[i:i + 1], chunk=P)
+            tm.primal()
+            rows[:, i] = tm.vjp(U[:, i:i + 1].contiguous(), nv.HEAD_L, 0.7)
+        slices = _tensor_slices(state.params)
+        # the reference is usable: finite, and every parameter tensor gets a non-zero row from every pair
+        assert bool(rows.isfinite().all())
+        for name, a, b in slices:
+            assert bool((rows[:, :, a:b].abs().amax(-1) > 0).all()), f"{name}: a pair with an all-zero reference row"
+        _MANY[which] = (eng, slices, U, rows)
+    return _MANY[which]
+
+
+@pytest.mark.parametrize("which", ["a", "b"])
+def test_sqsum_several_pairs_per_group_last_group_short(which):
+    """every tile, the dense form and the reduce with 2, 4 or 7 pairs per block and a short last group, element by
+    element against float64 squares of the emulator's per-example rows"""
+    assert_several_pairs_per_group(_net_of(which), MANY_P * MANY_N)
+    eng, slices, U, rows = many_pairs(which)
+    all_routes(eng.lib)                              # clear the census
+    _check_sqsum(eng, U, rows, slices, f"sqsum net {which}, {MANY_P * MANY_N} pairs")
+    census = set(_census(eng.lib))
+    assert SQSUM_NETS[which] <= census, sorted(SQSUM_NETS[which] - census)
+
+
+def test_sqsum_single_group_adds_into_y():
+    """P = 1, n = 1 on net b: one pair, G = 1 — the kernels add into the pre-filled y directly, no finish kernel"""
+    eng, tm, slices = _bind(_net_b(), 1, 7, 1)
+    U = torch.randn(1, 1, eng.K, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+    rows = _emulator_rows(tm, U)
+    all_routes(eng.lib)                              # clear the census
+    _check_sqsum(eng, U, rows, slices, "sqsum net b, one pair")
+    census = set(_census(eng.lib))
+    assert SQSUM_NETS["b"] <= census, sorted(SQSUM_NETS["b"] - census)
 
 
 @pytest.mark.parametrize("which", ["b", "c"])

@@ -393,6 +393,26 @@ def test_non_square_nets_match_float64_rows_of_the_emulator(which):
         assert e <= TOL, e
 
 
+@pytest.mark.parametrize("which", ["a", "b"])
+def test_several_pairs_per_group_last_group_short(which):
+    """517 pairs: every tile, the dense form and the reduce walk 2, 4 or 7 pairs per block and end on a short group
+    (tests/test_kernel_routes.py works the groups out and shares the float64 rows of the tape emulator)"""
+    from test_kernel_routes import MANY_N, MANY_P, assert_several_pairs_per_group, many_pairs
+    assert_several_pairs_per_group(_net_of(which), MANY_P * MANY_N)
+    eng, _, U, rows = many_pairs(which)
+    w = (torch.rand(eng.D, dtype=F64, generator=torch.Generator().manual_seed(4)) + 0.05).float().double()
+    _wnorm_census(eng.lib)                                   # clear
+    for wt in (w.float().cuda(), None):
+        v = eng.vjp_wnorm(U.float().cuda(), wt, "l", 0.7)
+        torch.cuda.synchronize()
+        census = _wnorm_census(eng.lib)
+        assert WNORM_NETS[which] <= set(census), f"{sorted(WNORM_NETS[which] - set(census))} not launched ({census})"
+        ref = (rows ** 2) @ (wt.double().cpu() if wt is not None else torch.ones(eng.D, dtype=F64))
+        e = _err(v.reshape(ref.shape), ref)
+        print(f"net {which}, 517 pairs, w {'given' if wt is not None else 'None'}: max|v - ref| / max ref = {e:.3g}")
+        assert e <= TOL, e
+
+
 @pytest.mark.parametrize("which", ["a", "b", "c", "d"])
 def test_census_shows_every_variant_and_values_match_rows(which):
     net = _net_of(which)
