@@ -270,6 +270,29 @@ int lip_gemm_nn_axpy(const float* T, int64_t ldt, int32_t m, int32_t k, const fl
  * G - (G Q) Q^T of :131.  Out must not alias Y or Z.                                                      */
 int lip_rows_combine(const double* Cm, const float* Y, int64_t ldy, int32_t s, const float* Z, int64_t ldz, float zscale,
                      float* Out, int64_t ldo, int32_t r, int64_t N, void* stream);
+/* Last-layer Laplace: the dense GGN block over theta_L = [bias (K), kernel (F, K) row-major] of a final Dense layer,
+ * from the penultimate features and the softmax probabilities alone (no backward sweep).  G (DL, DL) float64
+ * row-major, DL = (F + 1) K, ADDED into (example chunks sum into one G):
+ *   G[(f K + k)][(g K + l)] += sum_i phit_i[f] phit_i[g] H_i[k][l],   phit_i = [1, Phi[i][0..F)],
+ *   H_i = diag(p_i) - p_i p_i^T (Pr (n, K) float32 given)  or  I (Pr NULL: the Gaussian head).
+ * Phi (n, F) float32, row stride ldphi >= F.  Operands are up-cast before any multiplication and accumulated in
+ * float64 on the float64 matrix pipe; H is split as diag - outer, so the work is K weighted (F + 1)^2 Grams minus one
+ * n-term Gram of the rows phit_i (x) p_i, rebuilt in registers: nothing of size (n, DL) is written.  The examples are
+ * split over blocks whose partial tiles go to scratch (device, caller-owned, >= lip_ll_ggn_scratch(n, F, K) doubles;
+ * the query covers both heads) and are added in index order by a second kernel: no atomics, so the result is bitwise
+ * reproducible, and one triangle of tiles is computed and mirrored, so a symmetric G stays exactly symmetric.  A null
+ * Phi / G / scratch, n, F or K <= 0, ldphi < F or too small a scratch returns LIP_ERR_ARG and leaves G untouched. */
+int lip_ll_ggn(const float* Phi, int64_t ldphi, const float* Pr, int32_t n, int32_t F, int32_t K, double* G,
+               double* scratch, int64_t scratch_doubles, void* stream);
+int lip_ll_ggn_scratch(int32_t n, int32_t F, int32_t K, int64_t* doubles);
+/* The matching test-time quadratic form, float64, out overwritten; S (DL, DL) float64 row-major (the posterior covariance):
+ *   diag == 0: out (B, K, K), out[b][k][l] = sum_{f,g} phit_b[f] phit_b[g] S[(f K + k)][(g K + l)], computed for k <= l
+ *              and mirrored (exactly symmetric);
+ *   diag != 0: out (B, K), the k == l entries only, bitwise those of the full form.
+ * No (B, K, DL) intermediate is written.  A null Phi / S / out, B, F or K <= 0 or ldphi < F returns LIP_ERR_ARG and
+ * leaves out untouched. */
+int lip_ll_predict(const float* Phi, int64_t ldphi, int32_t B, int32_t F, int32_t K, const double* S, double* out,
+                   int32_t diag, void* stream);
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);

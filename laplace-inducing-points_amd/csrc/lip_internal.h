@@ -359,6 +359,12 @@ template <class F> auto with_flag(bool on, F&& f) {
 }
 
 void set_error(const char* fmt, ...);
+// a failed HIP runtime call inside an entry point (code that is `using namespace lip`): record it, return LIP_ERR_HIP
+#define LIP_CHECK_HIP(expr)                                                        \
+  do {                                                                             \
+    hipError_t _e = (expr);                                                        \
+    if (_e != hipSuccess) { set_error("%s: %s", #expr, hipGetErrorString(_e)); return LIP_ERR_HIP; } \
+  } while (0)
 int precision_mode();
 void set_precision_mode(int m);
 void set_split_k_mode(int on);

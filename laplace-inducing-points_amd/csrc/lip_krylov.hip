@@ -666,12 +666,6 @@ static bool same_alignment(const void* a, const void* b) {
 
 using namespace lip;
 
-#define LIP_CHECK_HIP(expr)                                                        \
-  do {                                                                             \
-    hipError_t _e = (expr);                                                        \
-    if (_e != hipSuccess) { set_error("%s: %s", #expr, hipGetErrorString(_e)); return LIP_ERR_HIP; } \
-  } while (0)
-
 extern "C" {
 
 int lip_bdot(const float* X, const float* Y, float* out, int32_t P, int64_t N, void* stream) {

@@ -1,0 +1,255 @@
+// Last-layer Laplace: the dense GGN block of the final Dense layer from the cached penultimate features and softmax
+// probabilities (lip_ll_ggn), and the matching test-time quadratic form (lip_ll_predict).  Everything in float64.
+//
+// With phit_i = [1, phi_i] (Ft = F + 1 entries) and theta_L = [bias (K), kernel (F, K) row-major], flat index r = f K + k:
+//   G[(f,k)][(g,l)] = sum_i phit_i[f] phit_i[g] H_i[k][l],   H_i = diag(p_i) - p_i p_i^T  (softmax)  or  I  (Gaussian).
+// The H = diag - outer split turns the n K rank-one terms of length DL into two plain Grams over the examples:
+//   UU[r][c]      = sum_i U_i[r] U_i[c],          U_i[(f,k)] = phit_i[f] p_i[k]    (DL x DL, lower triangle of tiles)
+//   D[f][(g,l)]   = sum_i phit_i[f] U_i[(g,l)]                                      (Ft x DL, tiles with f <= g)
+//   G[(f,k)][(g,l)] = delta_kl D[min(f,g)][(max(f,g), l)] - UU[max(r,c)][min(r,c)]
+// (Gaussian head: D[f][g] = sum_i phit_i[f] phit_i[g] alone, Kc = 1 column per g.)  U_i[r] is a product of two float32
+// values, exact in float64, so every term is rounded once where the matrix pipe adds it.  Nothing of size (n, DL) is
+// ever written: the operands are rebuilt from Phi and Pr in registers.
+//
+// Work split: block = one 32 x 32 tile x one range of examples (blockIdx.y); its four waves take every fourth 16-example
+// chunk on v_mfma_f64_16x16x4_f64 (the operand and C/D maps of dot_nt_f64_mfma_kernel in lip_krylov.hip) and meet in LDS
+// in wave order.  Every block writes its partial tile to the caller's scratch; ll_assemble_kernel adds the ranges in
+// index order and applies the formula above.  No atomics anywhere: the summation order is a function of (n, F, K) alone,
+// so the result is bitwise reproducible, and both (r, c) and (c, r) read the same partial sums, so G stays symmetric.
+#include "lip_internal.h"
+
+namespace lip {
+
+constexpr int LL_B = 32;                    // tile edge
+constexpr int LL_TILE = LL_B * LL_B;
+constexpr int LL_CHUNK = 16;                // examples per wave step (four MFMA k-steps of 4)
+constexpr int LL_SPAN = 4 * LL_CHUNK;       // examples the four waves of a block cover per round
+typedef double ll_f64x4 __attribute__((ext_vector_type(4)));
+
+struct LLPlan {
+  int DL, Ft, Kc;        // Kc: classes per feature in the column space (K for softmax, 1 for the Gaussian head)
+  int T, Tuu;            // tiles per edge of the DL space; lower-triangle tiles of UU (0 for the Gaussian head)
+  int TF, Tc;            // row tiles of D (over Ft), column tiles of D (over Ft * Kc)
+  long long tiles;       // Tuu + TF * Tc
+  int ys, nper;          // example ranges and examples per range (a multiple of LL_SPAN)
+};
+
+static LLPlan ll_plan(int n, int F, int K, bool softmax) {
+  LLPlan p;
+  p.Ft = F + 1;
+  p.DL = p.Ft * K;
+  p.Kc = softmax ? K : 1;
+  p.T = (p.DL + LL_B - 1) / LL_B;
+  p.Tuu = softmax ? (int)((long long)p.T * (p.T + 1) / 2) : 0;
+  p.TF = (p.Ft + LL_B - 1) / LL_B;
+  p.Tc = (p.Ft * p.Kc + LL_B - 1) / LL_B;
+  p.tiles = (long long)p.Tuu + (long long)p.TF * p.Tc;
+  // split the examples until the launch has ~4 blocks per CU, whole spans per range
+  long long spans = ((long long)n + LL_SPAN - 1) / LL_SPAN, ys = (1024 + p.tiles - 1) / p.tiles;
+  if (ys > spans) ys = spans;
+  if (ys > 4096) ys = 4096;
+  if (ys < 1) ys = 1;
+  p.nper = (int)((spans + ys - 1) / ys) * LL_SPAN;
+  p.ys = (int)(((long long)n + p.nper - 1) / p.nper);
+  return p;
+}
+
+// one operand element: phit_i[f] (* p_i[k] when weighted); f == 0 is the bias feature
+__device__ __forceinline__ double ll_operand(const float* __restrict__ Phi, long long ldphi, const float* __restrict__ Pr,
+                                             int K, int i, int f, int k, bool weighted) {
+  double v = f == 0 ? 1.0 : (double)Phi[(long long)i * ldphi + (f - 1)];
+  if (weighted) v *= (double)Pr[(long long)i * K + k];
+  return v;
+}
+
+__global__ __launch_bounds__(256) void ll_gram_kernel(const float* __restrict__ Phi, long long ldphi,
+                                                      const float* __restrict__ Pr, int n, int K, LLPlan pl,
+                                                      double* __restrict__ part) {
+  __shared__ double red[3 * LL_TILE];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int i16 = lane & 15, q = lane >> 4;
+  const int tile = blockIdx.x;
+  const bool softmax = Pr != nullptr;
+  // rows: flat (f, k) of the DL space for a UU tile, features for a D tile; columns: flat (g, l) with Kc classes
+  bool uu = tile < pl.Tuu;
+  int r0, c0;
+  if (uu) {
+    int tr = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
+    while ((tr + 1) * (tr + 2) / 2 <= tile) ++tr;
+    while (tr * (tr + 1) / 2 > tile) --tr;
+    r0 = tr * LL_B;
+    c0 = (tile - tr * (tr + 1) / 2) * LL_B;
+  } else {
+    const int t = tile - pl.Tuu;
+    r0 = (t / pl.Tc) * LL_B;
+    c0 = (t % pl.Tc) * LL_B;
+    // only f <= g is ever read: a tile whose smallest f lies above its largest g has nothing to compute
+    const int cmax = min(c0 + LL_B - 1, pl.Ft * pl.Kc - 1);
+    if (r0 > cmax / pl.Kc) return;
+  }
+  const int rows = uu ? pl.DL : pl.Ft, cols = pl.Ft * pl.Kc;
+  int rf[2], rk[2], cf[2], ck[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int r = min(r0 + 16 * t + i16, rows - 1), c = min(c0 + 16 * t + i16, cols - 1);   // clamped: never read back
+    rf[t] = uu ? r / K : r;
+    rk[t] = uu ? r % K : 0;
+    cf[t] = c / pl.Kc;
+    ck[t] = c % pl.Kc;
+  }
+  const int ib = blockIdx.y * pl.nper, ie = min(ib + pl.nper, n);
+  ll_f64x4 acc[2][2];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  for (int i0 = ib + LL_CHUNK * wave; i0 < ie; i0 += LL_SPAN) {
+    double a[4][2], b[4][2];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int i = i0 + 4 * s + q;                  // k-step s of the chunk: this lane's example
+      const bool ok = i < ie;
+      const int ic = ok ? i : ie - 1;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const double av = ll_operand(Phi, ldphi, Pr, K, ic, rf[t], rk[t], uu);
+        const double bv = ll_operand(Phi, ldphi, Pr, K, ic, cf[t], ck[t], softmax);
+        a[s][t] = ok ? av : 0.0;
+        b[s][t] = ok ? bv : 0.0;
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][0], b[s][0], acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][0], b[s][1], acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][1], b[s][0], acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][1], b[s][1], acc[1][1], 0, 0, 0);
+    }
+  }
+  // C/D map of v_mfma_f64_16x16x4_f64: register r of lane l holds (row = (l >> 4) + 4 r, col = l & 15)
+  if (wave > 0) {
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[(wave - 1) * LL_TILE + (16 * tm + q + 4 * r) * LL_B + 16 * tn + i16] = acc[tm][tn][r];
+  }
+  __syncthreads();
+  if (wave == 0) {
+    double* mine = part + ((long long)blockIdx.y * pl.tiles + tile) * LL_TILE;
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int e = (16 * tm + q + 4 * r) * LL_B + 16 * tn + i16;
+          mine[e] = ((acc[tm][tn][r] + red[e]) + red[LL_TILE + e]) + red[2 * LL_TILE + e];
+        }
+  }
+}
+
+// G[r][c] += delta_kl D[min(f,g)][(max(f,g), l)] - UU[max(r,c)][min(r,c)], each a sum over the example ranges in order
+__global__ __launch_bounds__(256) void ll_assemble_kernel(const double* __restrict__ part, int K, LLPlan pl,
+                                                          double* __restrict__ G) {
+  const int c = blockIdx.x * 16 + (threadIdx.x & 15), r = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (r >= pl.DL || c >= pl.DL) return;
+  const int hi = max(r, c), lo = min(r, c);
+  const int f = hi / K, k = hi % K, g = lo / K, l = lo % K;                 // g <= f
+  double uu = 0.0, d = 0.0;
+  if (pl.Tuu > 0) {
+    const int th = hi / LL_B, tl = lo / LL_B;
+    const double* src = part + (long long)(th * (th + 1) / 2 + tl) * LL_TILE + (hi % LL_B) * LL_B + lo % LL_B;
+    for (int y = 0; y < pl.ys; ++y) uu += src[(long long)y * pl.tiles * LL_TILE];
+  }
+  if (k == l) {
+    const int col = f * pl.Kc + (pl.Kc > 1 ? l : 0);
+    const double* src = part + ((long long)pl.Tuu + (long long)(g / LL_B) * pl.Tc + col / LL_B) * LL_TILE +
+                        (g % LL_B) * LL_B + col % LL_B;
+    for (int y = 0; y < pl.ys; ++y) d += src[(long long)y * pl.tiles * LL_TILE];
+  }
+  G[(long long)r * pl.DL + c] += d - uu;
+}
+
+// out[b][k][l] = sum_g phit_b[g] (sum_f phit_b[f] S[(f,k)][(g,l)]),  l >= k, mirrored.  Block = (b, k); a wave per l; a
+// lane per g (every 64th), the inner sum over f serial per lane, the lanes' partial sums met by a fixed butterfly.  The
+// diag form runs l = k alone through the same code, so it equals the diagonal of the full form bitwise.
+__global__ __launch_bounds__(256) void ll_predict_kernel(const float* __restrict__ Phi, long long ldphi, int F, int K,
+                                                         const double* __restrict__ S, double* __restrict__ out, int diag) {
+  const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int Ft = F + 1;
+  const long long DL = (long long)Ft * K;
+  const float* phi = Phi + (long long)b * ldphi;
+  const int lend = diag ? k + 1 : K;
+  for (int l = k + wave; l < lend; l += 4) {
+    double s = 0.0;
+    for (int g = lane; g < Ft; g += 64) {
+      const double* col = S + (long long)k * DL + (long long)g * K + l;       // S[(f, k)][(g, l)], f = 0
+      double t = col[0];
+      for (int f = 1; f < Ft; ++f) t = fma((double)phi[f - 1], col[(long long)f * K * DL], t);
+      s = fma(g == 0 ? 1.0 : (double)phi[g - 1], t, s);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (lane == 0) {
+      if (diag) out[(long long)b * K + k] = s;
+      else {
+        out[((long long)b * K + k) * K + l] = s;
+        out[((long long)b * K + l) * K + k] = s;
+      }
+    }
+  }
+}
+
+}  // namespace lip
+
+using namespace lip;
+
+static bool ll_shape_ok(int32_t n, int32_t F, int32_t K) {
+  return n > 0 && F > 0 && K > 0 && ((long long)F + 1) * K <= 0x7fffffffll;
+}
+
+extern "C" {
+
+int lip_ll_ggn_scratch(int32_t n, int32_t F, int32_t K, int64_t* doubles) {
+  if (!doubles || !ll_shape_ok(n, F, K)) { set_error("lip_ll_ggn_scratch: bad argument"); return LIP_ERR_ARG; }
+  // the larger of the two heads' plans, so one buffer serves either
+  const LLPlan a = ll_plan(n, F, K, true), b = ll_plan(n, F, K, false);
+  const long long da = a.tiles * a.ys * LL_TILE, db = b.tiles * b.ys * LL_TILE;
+  *doubles = da > db ? da : db;
+  return LIP_OK;
+}
+
+int lip_ll_ggn(const float* Phi, int64_t ldphi, const float* Pr, int32_t n, int32_t F, int32_t K, double* G,
+               double* scratch, int64_t scratch_doubles, void* stream) {
+  if (!Phi || !G || !scratch || !ll_shape_ok(n, F, K) || ldphi < F) { set_error("lip_ll_ggn: bad argument"); return LIP_ERR_ARG; }
+  const LLPlan pl = ll_plan(n, F, K, Pr != nullptr);
+  const long long need = pl.tiles * pl.ys * LL_TILE;
+  if (scratch_doubles < need) {
+    set_error("lip_ll_ggn: scratch of %lld doubles, %lld needed (lip_ll_ggn_scratch)", (long long)scratch_doubles, need);
+    return LIP_ERR_ARG;
+  }
+  if (pl.tiles > 0x7fffffffll || (pl.DL + 15) / 16 > 65535) { set_error("lip_ll_ggn: (F + 1) K = %d is too large", pl.DL); return LIP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ll_gram_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.ys), dim3(256), 0, st, Phi, (long long)ldphi, Pr,
+                     n, K, pl, scratch);
+  LIP_CHECK_HIP(hipGetLastError());
+  const unsigned gb = (unsigned)((pl.DL + 15) / 16);
+  hipLaunchKernelGGL(ll_assemble_kernel, dim3(gb, gb), dim3(256), 0, st, (const double*)scratch, K, pl, G);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_ll_predict(const float* Phi, int64_t ldphi, int32_t B, int32_t F, int32_t K, const double* S, double* out,
+                   int32_t diag, void* stream) {
+  if (!Phi || !S || !out || !ll_shape_ok(B, F, K) || ldphi < F || K > 65535) { set_error("lip_ll_predict: bad argument"); return LIP_ERR_ARG; }
+  hipLaunchKernelGGL(ll_predict_kernel, dim3((unsigned)B, (unsigned)K), dim3(256), 0, (hipStream_t)stream, Phi,
+                     (long long)ldphi, F, K, S, out, (int)diag);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+}  // extern "C"

@@ -73,6 +73,46 @@ class CompiledNet:
     input_off: int
     meta: Dict[str, Any] = dataclasses.field(default_factory=dict)   # per-tensor offsets the second-order pass needs
 
+    def last_unit(self) -> Unit:
+        """the final unit, a plain Dense (:func:`last_dense_unit`)"""
+        return last_dense_unit(self.net)
+
+    def last_layer(self) -> Tuple[int, int, int]:
+        """``(offset, F, K)`` of the final Dense layer (:func:`last_layer_of`)"""
+        return last_layer_of(self.net, self.offsets)
+
+
+def last_dense_unit(net: NetSpec) -> Unit:
+    """The final unit, which must be a plain Dense: a conv unit with a bias, no BN, no residual, no activation, whose
+    window covers its whole source (a 1 x 1 source, or the flattened feature map of ``flat_kernel``) so that the
+    output is 1 x 1.  Anything else raises ``ValueError``: the last-layer posterior needs a head linear in theta_L."""
+    u = net.units[-1] if net.units else None
+    if u is None or u.kind != "conv" or u.dst != net.out:
+        raise ValueError("last-layer Laplace needs a final Dense unit; the network ends in "
+                         f"{'nothing' if u is None else repr(u.kind)}")
+    ih, iw, _ = net.tensors[u.src]
+    plain = (u.bias is not None and u.bn_scale is None and u.res is None and u.act == "none" and
+             tuple(net.tensors[u.dst][:2]) == (1, 1) and (u.kh, u.kw) == (ih, iw) and u.pad_h == 0 and u.pad_w == 0)
+    if not plain:
+        raise ValueError("last-layer Laplace needs a plain final Dense (bias, no BN, no residual, act='none', 1x1 "
+                         f"output); got act={u.act!r}, bias={u.bias is not None}, bn={u.bn_scale is not None}, "
+                         f"res={u.res is not None}, window {u.kh}x{u.kw} on a {ih}x{iw} source")
+    return u
+
+
+def last_layer_of(net: NetSpec, layout: Dict[Tuple, Tuple[int, Tuple[int, ...]]]) -> Tuple[int, int, int]:
+    """``(offset, F, K)`` of the final Dense: theta_L = theta[offset : offset + (F + 1) K] = [bias (K), kernel (F, K)
+    row-major], F the flattened width of its source; ``layout`` maps a parameter path to (flat offset, shape) as
+    ``param_layout`` gives them.  Raises ``ValueError`` when the last unit is not a plain Dense
+    (:func:`last_dense_unit`) or when bias and kernel are not adjacent in the flat layout in that order."""
+    u = last_dense_unit(net)
+    F, K = u.kh * u.kw * u.cin, u.cout
+    boff, koff = layout[u.bias][0], layout[u.kernel][0]
+    if koff != boff + K:
+        raise ValueError(f"last-layer Laplace needs the final bias (offset {boff}, {K} entries) directly before its "
+                         f"kernel (offset {koff}) in the flat parameter order")
+    return boff, F, K
+
 
 def _seg(a, b, IH, IW, Cc, KH, KW, stride, pad_h, pad_w, mode):
     return dict(a=a, b=b, IH=IH, IW=IW, C=Cc, KH=KH, KW=KW, stride=stride, pad_h=pad_h, pad_w=pad_w, mode=mode)
@@ -645,6 +685,39 @@ class LinearizedNet:
     def probs(self) -> torch.Tensor:
         o = self.cn.prob_off
         return self.prim[o:o + self.n * self.K].reshape(self.n, self.K).clone()
+
+    def last_layer(self) -> Tuple[int, int, int]:
+        """``(offset, F, K)`` of the final Dense layer (:meth:`CompiledNet.last_layer`)"""
+        return self.cn.last_layer()
+
+    def features(self) -> torch.Tensor:
+        """(n, F) penultimate activations phi_i, the input of the final Dense, read from the cached primal pass; for a
+        Dense on a feature map (``flat_kernel``) the flattened (h w c) source tensor, contiguous in ``prim`` already"""
+        _, F, _ = self.cn.last_layer()
+        o = self.cn.a_off[self.cn.last_unit().src]
+        return self.prim[o:o + self.n * F].reshape(self.n, F).clone()
+
+    def last_layer_ggn(self, out: torch.Tensor) -> torch.Tensor:
+        """ADD sum_i phit_i phit_i^T (x) H_i of this binding's examples into ``out`` (DL, DL) float64, DL = (F + 1) K:
+        the GGN block of theta_L = [bias, kernel] of the final Dense (``lip_ll_ggn``), H_i = diag(p_i) - p_i p_i^T for
+        the classifier and I for the regressor, from the cached features and probabilities: no backward sweep, no
+        per-example rows, bitwise reproducible and exactly symmetric."""
+        _, F, K = self.cn.last_layer()
+        DL = (F + 1) * K
+        if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (DL, DL)):
+            raise ValueError(f"out must be a contiguous float64 device matrix of {DL} x {DL}")
+        scratch = self._scratches.get("lip_ll_ggn_scratch")
+        if scratch is None:
+            doubles = C.c_int64(0)
+            nv.check(self.lib.lip_ll_ggn_scratch(self.n, F, K, C.byref(doubles)), "lip_ll_ggn_scratch")
+            scratch = self._scratches["lip_ll_ggn_scratch"] = torch.empty(max(1, doubles.value), device=self.device,
+                                                                          dtype=torch.float64)
+        cn = self.cn
+        phi = self.prim[cn.a_off[cn.last_unit().src]:]
+        pr = self.prim[cn.prob_off:] if cn.classifier else None
+        nv.check(self.lib.lip_ll_ggn(phi.data_ptr(), F, 0 if pr is None else pr.data_ptr(), self.n, F, K, out.data_ptr(),
+                                     scratch.data_ptr(), scratch.numel(), nv.stream_ptr()), "lip_ll_ggn")
+        return out
 
     # ------------------------------------------------------------------------------ measurement
     def profile(self, enable: bool):

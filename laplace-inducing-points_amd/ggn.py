@@ -42,6 +42,7 @@ def engine_key(state, Z, model_type):
 
 
 _EVICTION_HOOKS = []          # callables(key) run when a binding leaves the cache (the sampler drops its parts)
+_CLEAR_HOOKS = []             # callables() run by clear_engine_cache (caches whose entries may outlive their binding)
 
 
 _SHARED_WORK = {}
@@ -101,6 +102,8 @@ def clear_engine_cache():
         _ENGINE_CACHE.pop(key)
         for hook in _EVICTION_HOOKS:
             hook(key)
+    for hook in _CLEAR_HOOKS:
+        hook()
 
 
 class BlockOperator:
@@ -251,6 +254,13 @@ def compute_ggn_diag(state, Z, model_type, full_set_size=None, example_chunk: Op
         E = torch.eye(eng.K, device=eng.device, dtype=torch.float32)[:, None, :].expand(eng.K, eng.n, eng.K)
         eng.vjp_sqsum(E.contiguous(), "l", 1.0, out=Y)
     return Y.mul_(recal)
+
+
+def compute_ggn_last_layer(state, Z, model_type, full_set_size=None, example_chunk: Optional[int] = None) -> torch.Tensor:
+    """The dense GGN block of the final Dense layer, (DL, DL) float64 with DL = (F + 1) K, scaled like
+    :func:`compute_ggn_vp` and chunked like :func:`compute_ggn_diag` (:func:`last_layer.compute_ggn_last_layer`)."""
+    from . import last_layer
+    return last_layer.compute_ggn_last_layer(state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk)
 
 
 FACTOR_BYTES_LIMIT = 64 << 30

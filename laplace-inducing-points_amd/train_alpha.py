@@ -90,21 +90,45 @@ def update_alpha(log_alpha: float, opt_state, opt: Adam, *lm_args):
     return log_alpha + upd, new_state
 
 
-def fit_alpha(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200):
-    """The alpha hyper-steps of ``train_map_then_alpha`` (``:76-78,91-100``) for a fixed theta; the spectrum of
-    W^T W is computed once and reused by every step."""
-    N = full_set_size or X.shape[0]
-    lam, D, theta2 = _spectrum(X, state, model_type)
+def _fit_from_spectrum(lam, D, theta2, rescale, alpha0, alpha_lr, steps):
+    """``steps`` Adam ascent steps on log alpha from a spectrum: ``(alpha, [(alpha, value) before each step])``"""
     opt = Adam(alpha_lr)
     st = opt.init()
     la = math.log(alpha0)
     history = []
     for _ in range(steps):
-        v, g = _lml_from_spectrum(math.exp(la), lam, D, theta2, N / X.shape[0])
+        v, g = _lml_from_spectrum(math.exp(la), lam, D, theta2, rescale)
         history.append((math.exp(la), v))
         upd, st = opt.update(-g, st)
         la += upd
     return math.exp(la), history
+
+
+def fit_alpha(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200):
+    """The alpha hyper-steps of ``train_map_then_alpha`` (``:76-78,91-100``) for a fixed theta; the spectrum of
+    W^T W is computed once and reused by every step."""
+    N = full_set_size or X.shape[0]
+    lam, D, theta2 = _spectrum(X, state, model_type)
+    return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
+
+
+def log_marginal_likelihood_last_layer(alpha, X, state, model_type: str, full_set_size: Optional[int] = None) -> float:
+    """:func:`log_marginal_likelihood` of the last-layer model (every earlier layer frozen): the spectrum is that of the
+    dense last-layer GGN (``last_layer.compute_ggn_last_layer`` at N/M = 1), D = DL = (F + 1) K and
+    ||theta||^2 = ||theta_L||^2.  Not a reference function."""
+    from .last_layer import _spectrum_last_layer
+    N = full_set_size or X.shape[0]
+    lam, DL, theta2 = _spectrum_last_layer(X, state, model_type)
+    return _lml_from_spectrum(float(alpha), lam, DL, theta2, N / X.shape[0])[0]
+
+
+def fit_alpha_last_layer(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2,
+                         steps: int = 200):
+    """:func:`fit_alpha` on the last-layer evidence: ``(alpha, history)``; the spectrum is computed once."""
+    from .last_layer import _spectrum_last_layer
+    N = full_set_size or X.shape[0]
+    lam, DL, theta2 = _spectrum_last_layer(X, state, model_type)
+    return _fit_from_spectrum(lam, DL, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
 # ---- layer-wise precisions ------------------------------------------------------------------------------------------
