@@ -217,8 +217,11 @@ def lanczos_tridiag(matvec: Callable[[torch.Tensor], torch.Tensor], V0: torch.Te
     c1 = torch.empty(P, k, device=dev, dtype=torch.float32)
     c2 = torch.empty(P, k, device=dev, dtype=torch.float32)
     nrm2 = bdot(V0, V0)
-    nv.check(lib.lip_scale_store(nv.ptr(V0), nv.ptr(nrm2), nv.ptr(Qbuf), 0, P, k, N, ldq, st), "lip_scale_store")
-    alive = torch.ones(P, device=dev, dtype=torch.bool)
+    # a zero start row is a probe broken down from the beginning (as in funm_lanczos_dense): zero basis rows, diag 1,
+    # off 0, instead of 0 * rsqrt(0) = NaN in its basis and, through diag, in the batched eigh of the whole block
+    alive = nrm2 > 0
+    safe = torch.where(alive, nrm2, torch.full_like(nrm2, float("inf")))
+    nv.check(lib.lip_scale_store(nv.ptr(V0), nv.ptr(safe), nv.ptr(Qbuf), 0, P, k, N, ldq, st), "lip_scale_store")
     for j in range(k):
         w = matvec(Q[:, j].contiguous()).contiguous()      # (P, N) copy of basis row j (N may be < ldq)
         _chk(w)
@@ -444,7 +447,9 @@ def bidiag(matvec: Callable, vecmat: Callable, V0: torch.Tensor, k: int, n_out: 
     ``src/train_inducing.py:156``).  ``matvec``: (P, N) -> (P, n_out); ``vecmat``: (P, n_out) -> (P, N).
     Returns (alphas (P, k), betas (P, k-1)) and, with ``return_bases``, the bases V (P, k, N) and U (P, k, n_out)
     (views of the padded storage) and the projection coefficients of the two Gram-Schmidt passes of every step
-    ((cu1, cu2, cv1, cv2), each (P, k, k)) — what the adjoint recurrence of ``stochastic_grad.py`` walks back over."""
+    ((cu1, cu2, cv1, cv2), each (P, k, k)) — what the adjoint recurrence of ``stochastic_grad.py`` walks back over.
+    There is no breakdown guard (the reference has none: k stays within the rank); only a zero start row is taken out:
+    zero bases, alphas 1, betas 0, so that its term of :func:`slq_logdet_product` is 0 and nothing of it is NaN."""
     lib = nv.load()
     P, N = _chk(V0).shape
     st = nv.stream_ptr()
@@ -457,7 +462,13 @@ def bidiag(matvec: Callable, vecmat: Callable, V0: torch.Tensor, k: int, n_out: 
     c2 = torch.empty(P, k, device=dev, dtype=torch.float32)
     coef = [torch.zeros(P, k, k, device=dev, dtype=torch.float32) for _ in range(4)] if return_bases else None   # cu1, cu2, cv1, cv2
     nrm2 = bdot(V0, V0)
-    nv.check(lib.lip_scale_store(nv.ptr(V0), nv.ptr(nrm2), nv.ptr(Vb), 0, P, k, N, ldv, st), "lip_scale_store")
+    alive = nrm2 > 0
+    inf = torch.full_like(nrm2, float("inf"))
+
+    def store(w, n2, Qb, j, n, ld):                        # row j = w / ||w||; w * rsqrt(inf) = 0 for a zero start row
+        safe = torch.where(alive, n2, inf)
+        nv.check(lib.lip_scale_store(nv.ptr(w), nv.ptr(safe), nv.ptr(Qb), j, P, k, n, ld, st), "lip_scale_store")
+    store(V0, nrm2, Vb, 0, N, ldv)
     for j in range(k):
         v = Vb[:, j, :N].contiguous()
         u = _chk(matvec(v).contiguous())
@@ -468,14 +479,15 @@ def bidiag(matvec: Callable, vecmat: Callable, V0: torch.Tensor, k: int, n_out: 
         else:
             nrm2 = bdot(u, u)
         alphas[:, j] = torch.sqrt(nrm2)
-        nv.check(lib.lip_scale_store(nv.ptr(u), nv.ptr(nrm2), nv.ptr(Ub), j, P, k, n_out, ldu, st), "lip_scale_store")
+        store(u, nrm2, Ub, j, n_out, ldu)
         if j + 1 < k:
             w = _chk(vecmat(Ub[:, j, :n_out].contiguous()).contiguous())
             _cgs2(lib, Vb, ldv, w, P, j + 1, k, N, c1, c2, nrm2, st)
             if coef is not None:
                 coef[2][:, j, :j + 1], coef[3][:, j, :j + 1] = c1[:, :j + 1], c2[:, :j + 1]
             betas[:, j] = torch.sqrt(nrm2)
-            nv.check(lib.lip_scale_store(nv.ptr(w), nv.ptr(nrm2), nv.ptr(Vb), j + 1, P, k, N, ldv, st), "lip_scale_store")
+            store(w, nrm2, Vb, j + 1, N, ldv)
+    alphas = torch.where(alive[:, None], alphas, torch.ones_like(alphas))      # (the norms of a zero start row are all 0)
     if return_bases:
         return alphas, betas, Vb[:, :, :N], Ub[:, :, :n_out], tuple(coef)
     return alphas, betas
