@@ -43,6 +43,10 @@ struct lip_engine {
   mutable std::vector<hipEvent_t> ev_pool;
   mutable size_t ev_used = 0;
   mutable std::vector<int> ev_kind;   // kind of the op bracketed by events (2i, 2i+1)
+  // Winograd transforms of the binding's shared kernels and primal activations (lip_bindcache.h): filled lazily by the
+  // sweeps' launches, stale after a primal pass, freed on re-binding and destruction; null with LIP_NOBINDCACHE
+  BindCache* cache = new_bind_cache();
+  ~lip_engine() { delete cache; }
 };
 
 namespace {
@@ -90,6 +94,9 @@ inline RunCtx weighted_norm(RunCtx c, float* scratch, long long floats, bool won
   c.mode = Sweep::WNORM; c.scratch = scratch; c.scratch_floats = floats; c.wones = wones; c.wout = wout;
   return c;
 }
+
+// an operand the binding fixes between two primal passes: the weights / constants, or the primal tape's activations
+inline bool bound_space(const lip_ref_t& r) { return (r.space == LIP_SP_THETA || r.space == LIP_SP_CONST || r.space == LIP_SP_PRIM) && r.pstride == 0; }
 
 inline float* resolve(const RunCtx& c, const lip_ref_t& r) {
   switch (r.space) {
@@ -246,7 +253,9 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       }
       if (p.e1 && !p.xhat) { set_error("IGEMM: e1 without xhat"); return LIP_ERR_ARG; }
       if (p.red1 && !p.xhat2) { set_error("IGEMM: red1 without xhat2"); return LIP_ERR_ARG; }
-      return launch_with_reductions(c, p, [&](const IgemmP& q) { return launch_igemm(q, c.P, c.st); }, "IGEMM launch",
+      unsigned fixed_b = 0;
+      for (int s = 0; s < op.nseg; ++s) fixed_b |= bound_space(op.seg[s].b) ? 1u << s : 0u;
+      return launch_with_reductions(c, p, [&](const IgemmP& q) { return launch_igemm(q, c.P, c.st, c.e->cache, fixed_b); }, "IGEMM launch",
                                     op.n_img, p.OHW, p.N, p.xhat2);
     }
     case LIP_OP_WGRAD: {
@@ -259,7 +268,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
           RUN_CHECK(launch_wgrad_wnorm(p, c.P, op.n_img, c.wones ? nullptr : p.y, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm wgrad launch");
           break;
         case Sweep::SQSUM: RUN_CHECK(launch_wgrad_sqsum(p, c.P, op.n_img, c.scratch, c.scratch_floats, c.st), "square-sum wgrad launch"); break;
-        default: RUN_CHECK(launch_wgrad(p, c.P, c.st), "wgrad launch");
+        default: RUN_CHECK(launch_wgrad(p, c.P, c.st, bound_space(op.seg[0].a) ? c.e->cache : nullptr), "wgrad launch");
       }
       return LIP_OK;
     }
@@ -543,6 +552,7 @@ int lip_engine_bind(lip_engine_t* e, const float* theta, const float* consts, fl
   }
   // re-binding only a (grown) workspace keeps the cached primal pass valid
   if (e->theta != theta || e->consts != consts || e->prim != prim) e->primal_done = false;
+  if (e->cache) e->cache->release();
   e->theta = theta; e->consts = consts; e->prim = prim; e->work = work;
   e->work_pp = work_floats_per_probe; e->max_chunk = max_probes_per_chunk;
   return LIP_OK;
@@ -550,7 +560,11 @@ int lip_engine_bind(lip_engine_t* e, const float* theta, const float* consts, fl
 
 int lip_engine_primal(lip_engine_t* e, void* stream) {
   if (!e || !e->theta || !e->prim) { set_error("lip_engine_primal: engine not bound"); return LIP_ERR_STATE; }
+  // the pass rewrites PRIM from a THETA that may have changed in place: whatever the cache holds is stale from here on
+  // (dropped before the launches and after them, so nothing a failed pass left half-written is taken for current)
+  if (e->cache) e->cache->invalidate();
   const int rc = run_tape(RunCtx{e, nullptr, nullptr, nullptr, 1, 0, 1.f, (hipStream_t)stream}, LIP_TAPE_PRIMAL, false);
+  if (e->cache) e->cache->invalidate();
   if (rc == LIP_OK) e->primal_done = true;
   return rc;
 }

@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <utility>
 #include "lip.h"
+#include "lip_bindcache.h"
 
 namespace lip {
 
@@ -166,8 +167,14 @@ __host__ __device__ __forceinline__ bool head_scales(int classifier, int mode) {
 }
 
 // ---- launchers (return hipError_t of the launch) ------------------------------------------
-hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st);
-hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st);
+// cache: the engine's cache of binding-fixed Winograd transforms, or null (per-launch transforms).  launch_igemm takes
+// the transformed weights of segment s from it when bit s of fixed_b is set (the engine sets it where the segment's
+// shared B operand lives in THETA / CONST); launch_wgrad is handed a cache only when p.a lives in PRIM / CONST.  The
+// cache never changes the route of a launch, only where the Winograd kernels' transformed operand comes from.
+hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st, BindCache* cache = nullptr, unsigned fixed_b = 0);
+hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st, BindCache* cache = nullptr);
+// a cache with the device allocator and the per-engine cap of bind_cache_policy(), or null when the policy is off
+BindCache* new_bind_cache();
 hipError_t launch_reduce(const ReduceP& p, int P, hipStream_t st);
 hipError_t launch_pool_fwd(const PoolP& p, int P, hipStream_t st);
 hipError_t launch_pool_bwd(const PoolP& p, int P, hipStream_t st);

@@ -1434,9 +1434,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
 // gathers the im2col rows of its 64 output rows ONCE into MFMA operand registers (lane (i = row, k = lane >> 5) of
 // k-step kk holds element 2 kk + k; zero past K), keeps the epilogue's probe-independent operands (x-hat, act') of
 // its 64 x 32 tile in registers too, and walks over the probes of its probe group: per probe 14 coalesced dword
-// loads of the weight tangent (the B operand straight into the MFMA registers), 2 x 14 MFMAs, one fused
-// BN-tangent / act' epilogue, 32 row-segment stores.  No LDS, no barrier; output-write bound.
+// loads of the weight tangent, 2 x 14 MFMAs, one fused BN-tangent / act' epilogue.  No LDS, no barrier; output-write bound.
+// The weight tangent is the MFMA's A operand and the im2col rows its B operand, so the 32 x 32 tile comes out TRANSPOSED:
+// lane (l31, lh) holds output row l31 and register q its channel 4 lh + (q & 3) + 8 (q >> 2) — four consecutive
+// channels per register quad, stored (and x-hat / act' / scale / e0 / e1 loaded) 16 bytes at a time: 8 stores per
+// probe and lane where the row-major tile took 32 dword stores (0.69 -> 0.48 ms per 256-probe block; a lane's store is
+// a quarter of a 128-byte row, and that measured well enough that the exchange through LDS for whole lines was not
+// built).  Every sum keeps its k order.  The 16-byte accesses are typed 4-byte aligned: global memory takes a dwordx4
+// at any dword address, and the per-probe e0 / e1 rows of the CIFAR net start D = 1 084 586 floats apart.
 // ------------------------------------------------------------------------------------------
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ void first_ld4(const float* __restrict__ ptr, float (&v)[4]) {
+  const f32x4u t = *reinterpret_cast<const f32x4u*>(ptr);
+  v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+}
+
 template <int KK>
 __global__ __launch_bounds__(256) void igemm_first_kernel(const IgemmP prm, int P, int pgroups) {
   constexpr int TM = 2;
@@ -1448,7 +1460,7 @@ __global__ __launch_bounds__(256) void igemm_first_kernel(const IgemmP prm, int 
   const int rgroup = (int)blockIdx.x * 4 + wave;               // 64 output rows per wave
   const int r0 = rgroup * 64;
   if (r0 >= R) return;
-  // ---- A: im2col rows of this lane's TM rows, gathered once (rows >= R and taps outside the image read element 0 and are zeroed)
+  // ---- im2col rows of this lane's TM rows, gathered once (rows >= R and taps outside the image read element 0 and are zeroed)
   float areg[TM][KK];
   const int KWC = sg.KW * sg.C;
 #pragma unroll
@@ -1468,33 +1480,40 @@ __global__ __launch_bounds__(256) void igemm_first_kernel(const IgemmP prm, int 
       areg[tm][kk] = ok ? t : 0.f;
     }
   }
-  // ---- probe-independent epilogue operands of the wave's two 32 x 32 tiles, in the accumulator layout
-  const bool has_e1 = prm.e1 != nullptr, has_d = prm.dphi != nullptr;
-  float xh[TM][16], dv[TM][16];
-  unsigned eoff[TM];                                           // element offset of accumulator register 0
-  bool full = r0 + 64 <= R;                                    // uniform
+  // ---- probe-independent epilogue operands of the wave's two 32 x 32 tiles, in the (transposed) accumulator layout
+  const bool has_e0 = prm.e0 != nullptr, has_e1 = prm.e1 != nullptr, has_d = prm.dphi != nullptr;
+  float xh[TM][4][4], dv[TM][4][4], sc[4][4];
+  unsigned eoff[TM];                                           // element offset of register quad 0: (row, channel 4 lh)
+  bool rok[TM];                                                // this lane's row of tile tm exists
+  const bool full = r0 + 64 <= R;                              // uniform
 #pragma unroll
   for (int tm = 0; tm < TM; ++tm) {
-    eoff[tm] = (unsigned)((r0 + 32 * tm + 4 * lh) * 32 + l31);
+    const int r = r0 + 32 * tm + l31;
+    rok[tm] = r < R;
+    eoff[tm] = (unsigned)(min(r, R - 1) * 32 + 4 * lh);
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int r = r0 + 32 * tm + 4 * lh + (q & 3) + 8 * (q >> 2);
-      const unsigned e = (unsigned)(min(r, R - 1) * 32 + l31);
-      xh[tm][q] = has_e1 ? prm.xhat[e] : 0.f;
-      dv[tm][q] = has_d ? prm.dphi[e] : 1.f;
+    for (int g = 0; g < 4; ++g) {
+      if (has_e1) first_ld4(prm.xhat + eoff[tm] + 8 * g, xh[tm][g]);
+      else { xh[tm][g][0] = 0.f; xh[tm][g][1] = 0.f; xh[tm][g][2] = 0.f; xh[tm][g][3] = 0.f; }
+      if (has_d) first_ld4(prm.dphi + eoff[tm] + 8 * g, dv[tm][g]);
+      else { dv[tm][g][0] = 1.f; dv[tm][g][1] = 1.f; dv[tm][g][2] = 1.f; dv[tm][g][3] = 1.f; }
     }
   }
-  const float sc = prm.scale ? prm.scale[l31] : 1.f;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    if (prm.scale) first_ld4(prm.scale + 4 * lh + 8 * g, sc[g]);
+    else { sc[g][0] = 1.f; sc[g][1] = 1.f; sc[g][2] = 1.f; sc[g][3] = 1.f; }
+  }
   // ---- the probes of this wave's group
   const int pg = (int)blockIdx.y;
   const int per = (P + pgroups - 1) / pgroups;
   const int p_end = min(P, (pg + 1) * per);
-  const unsigned bl = (unsigned)(lh * 32 + l31);               // lane part of the B offset: row (2 kk + lh), column l31
+  const unsigned bl = (unsigned)(lh * 32 + l31);               // lane part of the weight-tangent offset: row (2 kk + lh), column l31
   auto load_b = [&](int p, float (&b)[KK]) {
     const float* __restrict__ bp = sg.b + (long long)p * sg.b_ps;          // wave-uniform
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
-      const bool pair = 2 * kk + 1 < K;                                     // uniform; the last k-step of an odd K reads row K - 1 (A is zero there)
+      const bool pair = 2 * kk + 1 < K;                                     // uniform; the last k-step of an odd K reads row K - 1 (the im2col operand is zero there)
       b[kk] = (bp + (pair ? 2 * kk * 32 : (2 * kk < K ? (K - 1) * 32 : 0)))[pair ? bl : (unsigned)l31];
     }
   };
@@ -1504,22 +1523,34 @@ __global__ __launch_bounds__(256) void igemm_first_kernel(const IgemmP prm, int 
   load_b(p, b);
   for (; p < p_end; ++p) {
     load_b(min(p + 1, p_end - 1), bn);
-    const float e0v = prm.e0 ? prm.e0[(long long)p * prm.e0_ps + l31] : 0.f;
-    const float e1v = has_e1 ? prm.e1[(long long)p * prm.e1_ps + l31] : 0.f;
+    float e0v[4][4], e1v[4][4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (has_e0) first_ld4(prm.e0 + (long long)p * prm.e0_ps + 4 * lh + 8 * g, e0v[g]);
+      else { e0v[g][0] = 0.f; e0v[g][1] = 0.f; e0v[g][2] = 0.f; e0v[g][3] = 0.f; }
+      if (has_e1) first_ld4(prm.e1 + (long long)p * prm.e1_ps + 4 * lh + 8 * g, e1v[g]);
+      else { e1v[g][0] = 0.f; e1v[g][1] = 0.f; e1v[g][2] = 0.f; e1v[g][3] = 0.f; }
+    }
     f32x16 acc[TM];
     zero_acc(acc);
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk)
 #pragma unroll
-      for (int tm = 0; tm < TM; ++tm) acc[tm] = __builtin_amdgcn_mfma_f32_32x32x2f32(areg[tm][kk], b[kk], acc[tm], 0, 0, 0);
+      for (int tm = 0; tm < TM; ++tm) acc[tm] = __builtin_amdgcn_mfma_f32_32x32x2f32(b[kk], areg[tm][kk], acc[tm], 0, 0, 0);
     float* __restrict__ out = prm.out + (long long)p * prm.out_ps;          // wave-uniform
 #pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
+    for (int tm = 0; tm < TM; ++tm) {
+      if (!full && !rok[tm]) continue;
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float v = (acc[tm][q] * sc + e0v + e1v * xh[tm][q]) * dv[tm][q];
-        if (full || r0 + 32 * tm + 4 * lh + (q & 3) + 8 * (q >> 2) < R) (out + ((q & 3) + 8 * (q >> 2)) * 32)[eoff[tm]] = v;
+      for (int g = 0; g < 4; ++g) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (acc[tm][4 * g + j] * sc[g][j] + e0v[g][j] + e1v[g][j] * xh[tm][g][j]) * dv[tm][g][j];
+        f32x4u t;
+        t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
+        *reinterpret_cast<f32x4u*>(out + eoff[tm] + 8 * g) = t;
       }
+    }
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) b[kk] = bn[kk];
   }
@@ -2235,11 +2266,15 @@ static hipError_t run_wgrad_skinny(const WgradP& p0, int P, hipStream_t st) {
 // ------------------------------------------------------------------------------------------
 // weight gradient of the first layer (round 3): M = KH KW C <= 32 rows (27 for the CIFAR nets), 32 output columns, the
 // reduction over ALL R = n OH OW rows.  The generic kernel ran it at 18 TFLOP/s (1.25 ms per 256-probe block).  A wave
-// owns one probe and one share of the rows and sweeps it in chunks of 2 KC rows: the A operand is the TRANSPOSED
-// im2col block — lane (i = tap m, k = row parity) gathers a[pixel(row), tap m] — the B operand the cotangent rows
-// g_p[row][n] (coalesced 128-byte rows straight into the MFMA registers); KC MFMAs per chunk into one 32 x 32
-// accumulator, the next chunk's operands requested before the sweep; at the end the 27 x 32 valid entries are added
-// to Y with float atomics (one per row share).  No LDS, no barrier; bound by the read of g (R N floats per probe).
+// owns TWO probes and one share of the rows and sweeps it in chunks of 2 KC rows: the A operand is the TRANSPOSED
+// im2col block — lane (i = tap m, k = row parity) gathers a[pixel(row), tap m] — gathered once for both probes (it
+// does not depend on the probe, and these loops pay per memory instruction: one gather per probe was as many
+// instructions as the stream of g itself); the B operands are the two probes' cotangent rows g_p[row][n] (coalesced
+// 128-byte rows straight into the MFMA registers); 2 KC MFMAs per chunk into two 32 x 32 accumulators, the next
+// chunk's operands requested before the sweep; at the end the 27 x 32 valid entries of each probe are added to Y with
+// float atomics (one per row share).  An odd probe count: the last wave reads its one probe for both streams and
+// drops the second result.  No LDS, no barrier; bound by the read of g (R N floats per probe).
+// LIP_EXP_WGFIRST_NOA (timing-only builds): the A gather compiled out, to see which stream limits the kernel.
 // ------------------------------------------------------------------------------------------
 template <int KC>
 __global__ __launch_bounds__(256) void wgrad_first_kernel(const WgradP prm, int rsplit) {
@@ -2247,9 +2282,11 @@ __global__ __launch_bounds__(256) void wgrad_first_kernel(const WgradP prm, int 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
   const int M = prm.M, N = prm.N, R = prm.R;
-  const int item = (int)blockIdx.x * 4 + wave;                 // (probe, row share)
-  const int p = item / rsplit, share = item - p * rsplit;
+  const int item = (int)blockIdx.x * 4 + wave;                 // (probe pair, row share)
+  const int pp = item / rsplit, share = item - pp * rsplit;
+  const int p = 2 * pp;
   if (p >= prm.P) return;
+  const bool two = p + 1 < prm.P;                              // uniform
   int rows_per = (R + rsplit - 1) / rsplit;
   rows_per = (rows_per + 2 * KC - 1) / (2 * KC) * (2 * KC);
   const int rbeg = share * rows_per, rend = min(R, rbeg + rows_per);
@@ -2260,34 +2297,46 @@ __global__ __launch_bounds__(256) void wgrad_first_kernel(const WgradP prm, int 
   const int tap = mm / prm.C, c = mm - tap * prm.C, kh = tap / prm.KW, kw = tap - kh * prm.KW;
   const int th = kh - prm.pad_h, tw = kw - prm.pad_w;
   const float* __restrict__ gp = prm.g + (long long)p * prm.g_ps;            // wave-uniform
+  const float* __restrict__ gq = two ? gp + prm.g_ps : gp;
   const unsigned col = (unsigned)min(l31, N - 1);
-  f32x16 acc;
+  f32x16 acc, acq;
 #pragma unroll
-  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-  auto load = [&](int r0, float (&a)[KC], float (&b)[KC]) __attribute__((always_inline)) {
+  for (int q = 0; q < 16; ++q) { acc[q] = 0.f; acq[q] = 0.f; }
+  auto load = [&](int r0, float (&a)[KC], float (&b)[KC], float (&bq)[KC]) __attribute__((always_inline)) {
 #pragma unroll
     for (int kk = 0; kk < KC; ++kk) {
       const int r = r0 + 2 * kk + lh;
       const int rc = min(r, R - 1);
+#ifdef LIP_EXP_WGFIRST_NOA
+      a[kk] = (mv && r < rend) ? 1.f : 0.f;
+#else
       const int i = prm.dOHW.div(rc), rem = rc - i * prm.OHW;
       const int oh = prm.dOW.div(rem), ow = rem - oh * prm.OW;
       const int ih = oh * prm.stride + th, iw = ow * prm.stride + tw;
       const bool ok = mv && r < rend && (unsigned)ih < (unsigned)prm.IH && (unsigned)iw < (unsigned)prm.IW;
       const float t = prm.a[ok ? (unsigned)(((i * prm.IH + ih) * prm.IW + iw) * prm.C + c) : 0u];
       a[kk] = ok ? t : 0.f;                                                  // rows past the share are zero in A: B may read any valid row
+#endif
       b[kk] = gp[(unsigned)rc * (unsigned)N + col];
+      bq[kk] = gq[(unsigned)rc * (unsigned)N + col];
     }
   };
-  float a0[KC], b0[KC], a1[KC], b1[KC];
-  load(rbeg, a0, b0);
+  float a0[KC], b0[KC], c0[KC], a1[KC], b1[KC], c1[KC];
+  load(rbeg, a0, b0, c0);
   for (int r0 = rbeg; r0 < rend; r0 += 4 * KC) {
-    if (r0 + 2 * KC < rend) load(r0 + 2 * KC, a1, b1);
+    if (r0 + 2 * KC < rend) load(r0 + 2 * KC, a1, b1, c1);
 #pragma unroll
-    for (int kk = 0; kk < KC; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[kk], b0[kk], acc, 0, 0, 0);
+    for (int kk = 0; kk < KC; ++kk) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[kk], b0[kk], acc, 0, 0, 0);
+      acq = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[kk], c0[kk], acq, 0, 0, 0);
+    }
     if (r0 + 2 * KC >= rend) break;
-    if (r0 + 4 * KC < rend) load(r0 + 4 * KC, a0, b0);
+    if (r0 + 4 * KC < rend) load(r0 + 4 * KC, a0, b0, c0);
 #pragma unroll
-    for (int kk = 0; kk < KC; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[kk], b1[kk], acc, 0, 0, 0);
+    for (int kk = 0; kk < KC; ++kk) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[kk], b1[kk], acc, 0, 0, 0);
+      acq = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[kk], c1[kk], acq, 0, 0, 0);
+    }
   }
   const float sc = prm.scale ? prm.scale[col] : 1.f;
   float* __restrict__ yb = prm.y + (long long)p * prm.y_ps;
@@ -2295,7 +2344,10 @@ __global__ __launch_bounds__(256) void wgrad_first_kernel(const WgradP prm, int 
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int m = 4 * lh + (q & 3) + 8 * (q >> 2);
-      if (m < M) atomicAdd(yb + (unsigned)(m * N + l31), acc[q] * sc);
+      if (m < M) {
+        atomicAdd(yb + (unsigned)(m * N + l31), acc[q] * sc);
+        if (two) atomicAdd(yb + prm.y_ps + (unsigned)(m * N + l31), acq[q] * sc);
+      }
     }
   }
 }
@@ -2309,11 +2361,12 @@ static hipError_t run_wgrad_first(const WgradP& p0, int P, hipStream_t st) {
   WgradP p = p0;
   p.P = P;
   constexpr int KC = 32;
-  int rsplit = (2 * 4 * cu_count() + P - 1) / P;                              // ~2 waves per SIMD
+  const int pairs = (P + 1) / 2;                                              // a wave takes two probes
+  int rsplit = (2 * 4 * cu_count() + pairs - 1) / pairs;                      // ~2 waves per SIMD's worth of items, as before (at 272 registers one is resident at a time)
   const int maxsplit = p.R / (8 * 2 * KC) > 0 ? p.R / (8 * 2 * KC) : 1;       // >= 8 chunks per share
   if (rsplit > maxsplit) rsplit = maxsplit;
   if (rsplit < 1) rsplit = 1;
-  const long long items = (long long)P * rsplit;
+  const long long items = (long long)pairs * rsplit;
   LIP_ROUTE("wgrad_first<%d>", KC);
   hipLaunchKernelGGL((wgrad_first_kernel<KC>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, p, rsplit);
   return hipGetLastError();
@@ -2514,7 +2567,28 @@ static bool wgrad_wino_ok(const WgradP& p, int P) {
 
 bool wgrad_will_overwrite(const WgradP& p, int P) { return wgrad_skinny_ok(p) || (wgrad_wino_ok(p, P) && wgrad_wino_splits(p, P) == 1); }
 
-static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st) {
+// The engine's transform cache (lip_bindcache.h) on the device allocator, switched and capped by bind_cache_policy()
+BindCache* new_bind_cache() {
+  const BindCachePolicy& pol = bind_cache_policy();
+  if (pol.off) return nullptr;
+  return new BindCache([](size_t bytes) -> void* {
+                         void* ptr = nullptr;
+                         if (hipMalloc(&ptr, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+                         return ptr;
+                       },
+                       [](void* ptr) { (void)hipFree(ptr); }, pol.cap_bytes);
+}
+
+// The cache's buffer for `key`, to be filled when `fill` comes back true — or null: no cache, a stream under capture
+// (a captured fill runs when the graph does, not now), another stream than the cache's, the cap, a failed allocation.
+static BindCache::Hit bind_cache_get(BindCache* cache, const BindKey& key, size_t floats, hipStream_t st) {
+  if (!cache) return BindCache::Hit{nullptr, false};
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return BindCache::Hit{nullptr, false}; }
+  return cache->get(key, floats, (const void*)st);
+}
+
+static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st, BindCache* cache) {
   WgWinoP q;
   const int OH = p.OHW / p.OW, TH = OH / 2, TW = p.OW / 2;
   const int T = p.R / 4, groups = (T + 7) / 8;
@@ -2524,14 +2598,20 @@ static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st) {
   q.dTPI = FastDiv((unsigned)q.tpi); q.dTW = FastDiv((unsigned)TW);
   q.H = OH; q.W = p.OW; q.C = p.C; q.N = p.N;
   const size_t vfloats = (size_t)16 * q.TQ * p.C * 4;
-  float* vt = stream_scratch(vfloats, st);
+  // Vt depends on the primal activations and the tile split only: once per binding when the engine has a cache
+  const BindCache::Hit hit = bind_cache_get(cache, BindKey{p.a, 2, {OH, p.OW, p.C, T, q.TQ}}, vfloats, st);
+  float* vt = hit.buf ? hit.buf : stream_scratch(vfloats, st);
   if (!vt) return hipErrorOutOfMemory;
   q.vt = vt; q.vt_bytes = (unsigned)(vfloats * 4);
   q.g = p.g; q.g_ps = p.g_ps; q.g_bytes = (unsigned)((long long)p.R * p.N * 4);
   q.y = p.y; q.y_ps = p.y_ps; q.scale = p.scale;
   q.overwrite = (p.overwrite && S == 1) ? 1 : 0; q.v = p.v; q.v_ps = p.v_ps; q.alpha = p.alpha;
   if (p.overwrite && S != 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(wino_input_transform_kernel, dim3((unsigned)(((long long)q.TQ * p.C + 255) / 256)), dim3(256), 0, st, p.a, vt, OH, p.OW, p.C, TH, TW, T, q.TQ);
+  if (!hit.buf || hit.fill) {
+    hipLaunchKernelGGL(wino_input_transform_kernel, dim3((unsigned)(((long long)q.TQ * p.C + 255) / 256)), dim3(256), 0, st, p.a, vt, OH, p.OW, p.C, TH, TW, T, q.TQ);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { if (hit.buf) cache->forget(hit.buf); return e; }
+  }
   const size_t shmem = 12 * 1024 * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
@@ -3089,27 +3169,44 @@ static bool igemm_wino_ok(const IgemmP& p, int P) {
   return true;
 }
 
-static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st) {
+static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st, BindCache* cache, unsigned fixed_b) {
   IgemmP q = p;
   WinoX wx;
   const int OH = p.OHW / p.OW;
   const long long n_img = p.R / p.OHW;
+  // U of a shared kernel that the binding fixes: once per binding when the engine has a cache; the others (per-probe
+  // weight tangents, shared operands outside THETA / CONST, no cache entry) into this stream's scratch, per launch
+  BindCache::Hit hit[3];
   size_t need = 0;
-  for (int s = 0; s < p.nseg; ++s) need += (size_t)(p.seg[s].b_ps ? P : 1) * 16 * p.seg[s].C * p.N;
-  float* scratch = stream_scratch(need, st);
-  if (!scratch) return hipErrorOutOfMemory;
+  for (int s = 0; s < p.nseg; ++s) {
+    const SegP& g = p.seg[s];
+    const size_t un = (size_t)16 * g.C * p.N;
+    hit[s] = (!g.b_ps && (fixed_b >> s & 1)) ? bind_cache_get(cache, BindKey{g.b, g.mode == 1 ? 1 : 0, {g.C, p.N, 0, 0, 0}}, un, st)
+                                             : BindCache::Hit{nullptr, false};
+    if (!hit[s].buf) need += (size_t)(g.b_ps ? P : 1) * un;
+  }
+  float* scratch = need ? stream_scratch(need, st) : nullptr;
+  if (need && !scratch) {
+    for (int s = 0; s < p.nseg; ++s)
+      if (hit[s].buf && hit[s].fill) cache->forget(hit[s].buf);
+    return hipErrorOutOfMemory;
+  }
   size_t off = 0;
   for (int s = 0; s < p.nseg; ++s) {
     const SegP& g = p.seg[s];
     const long long un = 16ll * g.C * p.N;
     const int PW = g.b_ps ? P : 1;
-    hipLaunchKernelGGL(wino_weight_transform_kernel, dim3((unsigned)(((g.C / 4) * p.N + 255) / 256), (unsigned)PW), dim3(256), 0, st,
-                       g.b, g.b_ps, scratch + off, un, g.C, p.N, g.mode == 1 ? 1 : 0);
-    q.seg[s].b = scratch + off;
+    float* u = hit[s].buf ? hit[s].buf : scratch + off;
+    if (!hit[s].buf || hit[s].fill) {
+      hipLaunchKernelGGL(wino_weight_transform_kernel, dim3((unsigned)(((g.C / 4) * p.N + 255) / 256), (unsigned)PW), dim3(256), 0, st,
+                         g.b, g.b_ps, u, un, g.C, p.N, g.mode == 1 ? 1 : 0);
+      if (hit[s].buf && hipPeekAtLastError() != hipSuccess) cache->forget(hit[s].buf);
+    }
+    q.seg[s].b = u;
     q.seg[s].b_ps = g.b_ps ? un : 0;
     wx.a_bytes[s] = (unsigned)(n_img * p.OHW * g.C * 4);
     wx.u_bytes[s] = (unsigned)(un * 4);
-    off += (size_t)PW * un;
+    if (!hit[s].buf) off += (size_t)PW * un;
   }
   for (int s = p.nseg; s < 3; ++s) { wx.a_bytes[s] = 0; wx.u_bytes[s] = 0; }
   const WinoGeom g = wino_geom(OH, p.OW, n_img);
@@ -3139,11 +3236,11 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st) {
+hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st, BindCache* cache, unsigned fixed_b) {
   if (igemm_first_ok(p, P)) return run_igemm_first(p, P, st);
   if (igemm_wino_ok(p, P)) {
     // (no scratch for the transformed weights — a 17th stream, or the allocation failed: the direct kernels below)
-    const hipError_t e = run_igemm_wino(p, P, st);
+    const hipError_t e = run_igemm_wino(p, P, st, cache, fixed_b);
     if (e != hipErrorOutOfMemory) return e;
     (void)hipGetLastError();
   }
@@ -3281,7 +3378,7 @@ static hipError_t run_wgrad_pb(const WgradP& p, int P, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st) {
+hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st, BindCache* cache) {
   if (wgrad_first_ok(p, P)) return run_wgrad_first(p, P, st);
   if (wgrad_skinny_ok(p)) {
     if (p.R <= 16) return run_wgrad_skinny<2, 8>(p, P, st);
@@ -3289,7 +3386,7 @@ hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st) {
     return run_wgrad_skinny<2, 32>(p, P, st);
   }
   if (wgrad_wino_ok(p, P)) {
-    const hipError_t e = run_wgrad_wino(p, P, st);
+    const hipError_t e = run_wgrad_wino(p, P, st, cache);
     if (e != hipErrorOutOfMemory) return e;             // (no scratch for the transformed activations: the direct kernels)
     (void)hipGetLastError();
   }

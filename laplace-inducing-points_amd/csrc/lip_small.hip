@@ -6,7 +6,8 @@ namespace lip {
 
 // ---- per-channel column sums: red0[p][c] += sum_r g[p][r][c] ; red1[p][c] += sum_r g*xhat --------
 // (bias / BN-parameter cotangents that could not be fused into an igemm epilogue)
-// Blocks take `rpb` rows (128, fewer when the grid would not fill the chip).  Whenever N % 4 == 0 and the rows are 16-byte
+// Blocks take `rpb` rows (512, fewer when the grid would not fill the chip: at 128 a block of the CIFAR sweep lived for
+// one memory latency and its set-up and LDS / global atomics weighed as much as its loads).  Whenever N % 4 == 0 and the rows are 16-byte
 // aligned a thread owns one column quad: float4 loads, private sums, four LDS atomics at the end.  (The first version
 // did one LDS atomic and a 64-bit modulo per ELEMENT once N > 256: 0.3 - 0.4 TB/s on ResNet-50's 512 - 2048-channel
 // layers, 4.6 ms of its 173 ms sweep.)
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceP prm) {
 hipError_t launch_reduce(const ReduceP& p0, int P, hipStream_t st) {
   ReduceP p = p0;
   const long long segs = (long long)P * (p.nseg > 0 ? p.nseg : 1);
-  p.rpb = 128;
+  p.rpb = 512;
   while (p.rpb > 16 && (long long)((p.R + p.rpb - 1) / p.rpb) * segs < 2048) p.rpb >>= 1;
   dim3 grid((p.R + p.rpb - 1) / p.rpb, P, p.nseg > 0 ? p.nseg : 1);
   // with N % 4 == 0 every row block and segment of a probe starts on the alignment of the probe's first row
@@ -289,14 +290,35 @@ int wnorm_routes_read(int64_t* counts, int n, const char** names) {
 
 // ---- mean pool over pixels: out[p][i][c] = inv * sum_pix in[p][i][pix][c]  (jnp.mean(x,(1,2))) ------
 __global__ __launch_bounds__(256) void pool_fwd_kernel(const PoolP prm) {
-  extern __shared__ float sm[];           // [C + 256]
+  extern __shared__ float sm[];           // [C + 1024]: the sums, then the partial sums of SP_FIXED [256] / narrow SP_QUAD [G][C]
   const int C = prm.C, i = blockIdx.x, p = blockIdx.y;
   for (int c = threadIdx.x; c < C; c += 256) sm[c] = 0.f;
   __syncthreads();
   const float* in = prm.in + (long long)p * prm.in_ps + (long long)i * prm.HW * C;
   const long long cnt = (long long)prm.HW * C;
   const int path = pool_fwd_path(C, in);
-  if (path == SP_QUAD) {
+  if (path == SP_QUAD && (C >> 2) < 256) {
+    // fewer than 256 channel quads: 256 / Q pixel groups side by side (as reduce_kernel's row groups), thread (cq, g)
+    // adds pixels g, g + G, ... of its quad; the groups' partial sums meet in LDS and are added in group order (no float
+    // atomics: the tangent stays the same from run to run)
+    const int Q = C >> 2, G = 256 / Q, cq = threadIdx.x % Q, g = threadIdx.x / Q;
+    float* part = sm + C;                 // [G][C]
+    if (g < G) {
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+      for (int px = g; px < prm.HW; px += G) {
+        const float4 v = *reinterpret_cast<const float4*>(in + (long long)px * C + 4 * cq);
+        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+      }
+      *reinterpret_cast<float4*>(part + g * C + 4 * cq) = a;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+      float t = 0.f;
+      for (int k = 0; k < G; ++k) t += part[k * C + c];
+      sm[c] = t;
+    }
+  } else if (path == SP_QUAD) {
     // a thread owns whole channel quads: float4 loads down the pixels, no LDS traffic (wide layers: the per-element
     // LDS atomic + modulo of the general branch ran ResNet-50's 2048-channel pool at 0.3 TB/s)
     for (int cq = threadIdx.x; cq < (C >> 2); cq += 256) {
@@ -339,14 +361,14 @@ hipError_t launch_pool_fwd(const PoolP& p, int P, hipStream_t st) {
   for (int q = 1; q < P && q < 4; ++q)
     if (pool_fwd_path(p.C, p.in + (long long)q * p.in_ps) != path) path = SP_MIXED;
   LIP_ROUTE_PATH("pool_fwd", path);
-  hipLaunchKernelGGL(pool_fwd_kernel, dim3(p.n, P, 1), dim3(256), (p.C + 256) * sizeof(float), st, p);
+  hipLaunchKernelGGL(pool_fwd_kernel, dim3(p.n, P, 1), dim3(256), (p.C + 1024) * sizeof(float), st, p);
   return hipGetLastError();
 }
 
 // ---- pool backward: out[p][i][pix][c] = dphi[i][pix][c] * inv * in[p][i][c], plus reductions ------------
 constexpr int PB_PIX = 16;
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const PoolP prm) {
-  extern __shared__ float sm[];           // [2*C]
+  extern __shared__ float sm[];           // [2*C], and [2][1024] partial sums behind them when C / 4 < 256
   const int C = prm.C, i = blockIdx.y, p = blockIdx.z;
   float* s0 = sm; float* s1 = sm + C;
   const bool red = prm.red0 || prm.red1;
@@ -366,12 +388,20 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const PoolP prm) {
   const bool fixed_c = path == SP_FIXED;
   float a0 = 0.f, a1 = 0.f;
   if (path == SP_QUAD) {
-    // wide layers: a thread owns whole channel quads for all the block's pixels; sums stay in registers and go to the
-    // per-probe totals directly (no LDS, no per-element atomics)
-    for (int cq = threadIdx.x; cq < (C >> 2); cq += 256) {
+    // a thread owns a channel quad; sums stay in registers (no per-element atomics).  256 or more quads: a thread walks
+    // all the block's pixels and adds to the per-probe totals directly.  Fewer: G = 256 / Q pixel groups side by side,
+    // thread (cq, g) takes pixels g, g + G, ..., the groups leave their sums in LDS and one thread per channel adds them
+    // (in group order) to the per-probe totals: as many global atomics as before
+    const int Q = C >> 2;
+    const bool narrow = Q < 256;
+    const int G = narrow ? 256 / Q : 1, g = narrow ? (int)threadIdx.x / Q : 0;
+    const int Gn = min(G, npix);                                 // groups that have a pixel
+    const bool via_lds = red && Gn > 1;
+    float* part0 = sm + 2 * C; float* part1 = part0 + 1024;      // [Gn][C] each, G C <= 1024
+    for (int cq = narrow ? (int)threadIdx.x - g * Q : (int)threadIdx.x; cq < Q && g < Gn; cq += 256) {
       const float4 u = *reinterpret_cast<const float4*>(in + 4 * cq);
       float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0;
-      for (int px = 0; px < npix; ++px) {
+      for (int px = g; px < npix; px += G) {
         const long long o = (long long)px * C + 4 * cq;
         float4 v = make_float4(u.x * prm.inv, u.y * prm.inv, u.z * prm.inv, u.w * prm.inv);
         if (prm.dphi) {
@@ -387,10 +417,23 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const PoolP prm) {
           }
         }
       }
+      if (via_lds) {
+        *reinterpret_cast<float4*>(part0 + g * C + 4 * cq) = r0;
+        if (prm.red1) *reinterpret_cast<float4*>(part1 + g * C + 4 * cq) = r1;
+        continue;
+      }
       if (prm.red0) { float* d0 = prm.red0 + (long long)p * prm.red0_ps + 4 * cq;
         atomicAdd(d0, r0.x); atomicAdd(d0 + 1, r0.y); atomicAdd(d0 + 2, r0.z); atomicAdd(d0 + 3, r0.w); }
       if (prm.red1) { float* d1 = prm.red1 + (long long)p * prm.red1_ps + 4 * cq;
         atomicAdd(d1, r1.x); atomicAdd(d1 + 1, r1.y); atomicAdd(d1 + 2, r1.z); atomicAdd(d1 + 3, r1.w); }
+    }
+    if (!via_lds) return;
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+      float t0 = 0.f, t1 = 0.f;
+      for (int k = 0; k < Gn; ++k) { t0 += part0[k * C + c]; if (prm.red1) t1 += part1[k * C + c]; }
+      if (prm.red0) atomicAdd(prm.red0 + (long long)p * prm.red0_ps + c, t0);
+      if (prm.red1) atomicAdd(prm.red1 + (long long)p * prm.red1_ps + c, t1);
     }
     return;
   }
@@ -428,7 +471,8 @@ hipError_t launch_pool_bwd(const PoolP& p, int P, hipStream_t st) {
   for (int q = 1; q < P && q < 4; ++q)
     if (pool_bwd_path(p.C, p.in + (long long)q * p.in_ps, p.out + (long long)q * p.out_ps, p.dphi, p.xhat) != path) path = SP_MIXED;
   LIP_ROUTE_PATH("pool_bwd", path);
-  hipLaunchKernelGGL(pool_bwd_kernel, grid, dim3(256), 2 * p.C * sizeof(float), st, p);
+  const bool groups = (path == SP_QUAD || path == SP_MIXED) && (p.C >> 2) < 256;     // the quad path's pixel groups leave partial sums in LDS
+  hipLaunchKernelGGL(pool_bwd_kernel, grid, dim3(256), (2 * p.C + (groups ? 2048 : 0)) * sizeof(float), st, p);
   return hipGetLastError();
 }
 
