@@ -293,6 +293,29 @@ int lip_ll_ggn_scratch(int32_t n, int32_t F, int32_t K, int64_t* doubles);
  * leaves out untouched. */
 int lip_ll_predict(const float* Phi, int64_t ldphi, int32_t B, int32_t F, int32_t K, const double* S, double* out,
                    int32_t diag, void* stream);
+/* Kronecker-factored last layer: the two factors of G_kron = c A (x) Bf over theta_L (flat index f K + k), ADDED into
+ * A (F + 1, F + 1) and Bf (K, K), float64 row-major (example chunks sum into one pair):
+ *   A[f][g] += sum_i phit_i[f] phit_i[g],   phit_i = [1, Phi[i][0..F)]   (the bias is feature 0),
+ *   Bf[k][l] += sum_i delta_kl p_i[k] - p_i[k] p_i[l]   (Pr (n, K) float32 given)  or  n delta_kl   (Pr NULL).
+ * Both are read off plain Grams of the augmented rows [1, phi_i] and [1, p_i], up-cast before any multiplication and
+ * accumulated on the float64 matrix pipe by the tile loop of lip_ll_ggn: nothing of size (n, F + 1) or (n, K) in float64
+ * is written, the examples are split over blocks whose partial tiles go to scratch (>= lip_ll_kron_factors_scratch
+ * doubles; the query covers both heads) and are added in index order, no atomics: bitwise reproducible, and one triangle
+ * of tiles is computed and mirrored, so symmetric factors stay exactly symmetric.  A null Phi / A / Bf / scratch, n, F
+ * or K <= 0, ldphi < F or too small a scratch returns LIP_ERR_ARG and leaves A and Bf untouched. */
+int lip_ll_kron_factors(const float* Phi, int64_t ldphi, const float* Pr, int32_t n, int32_t F, int32_t K, double* A,
+                        double* Bf, double* scratch, int64_t scratch_doubles, void* stream);
+int lip_ll_kron_factors_scratch(int32_t n, int32_t F, int32_t K, int64_t* doubles);
+/* The predictive of the factored posterior S = sum_{j,l} (V_j V_j^T) (x) (Ub_l Ub_l^T) R[j][l]; V (F + 1, F + 1),
+ * R (F + 1, K), Ub (K, K) float64 row-major.  Per test point: u = V^T phit, s_l = sum_j u_j^2 R[j][l] (both on the float64
+ * matrix pipe, kept in scratch: B (F + 1 + K) doubles, lip_ll_kron_predict_scratch), then
+ *   diag == 0: out (B, K, K), out[b][k][m] = sum_l Ub[k][l] Ub[m][l] s_b[l], computed for k <= m and mirrored;
+ *   diag != 0: out (B, K), the k == m entries only, bitwise those of the full form.
+ * Nothing of size (B, K, DL) and no (DL, DL) matrix is formed.  A null pointer, B, F or K <= 0, ldphi < F or too small
+ * a scratch returns LIP_ERR_ARG and leaves out untouched. */
+int lip_ll_kron_predict(const float* Phi, int64_t ldphi, int32_t B, int32_t F, int32_t K, const double* V, const double* R,
+                        const double* Ub, double* out, int32_t diag, double* scratch, int64_t scratch_doubles, void* stream);
+int lip_ll_kron_predict_scratch(int32_t B, int32_t F, int32_t K, int64_t* doubles);
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);

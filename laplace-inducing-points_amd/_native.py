@@ -100,6 +100,11 @@ SIGNATURES = {
     "lip_ll_ggn": (C.c_int, [_V, C.c_int64, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int64, _V]),
     "lip_ll_ggn_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "lip_ll_predict": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int32, _V]),
+    "lip_ll_kron_factors": (C.c_int, [_V, C.c_int64, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, C.c_int64, _V]),
+    "lip_ll_kron_factors_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_ll_kron_predict": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, C.c_int32, _V, C.c_int64,
+                                      _V]),
+    "lip_ll_kron_predict_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "lip_fill_rademacher": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_fill_normal": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
 }

@@ -16,6 +16,9 @@
 // in wave order.  Every block writes its partial tile to the caller's scratch; ll_assemble_kernel adds the ranges in
 // index order and applies the formula above.  No atomics anywhere: the summation order is a function of (n, F, K) alone,
 // so the result is bitwise reproducible, and both (r, c) and (c, r) read the same partial sums, so G stays symmetric.
+//
+// The Kronecker-factored posterior (lip_ll_kron_factors, lip_ll_kron_predict; second half of the file) takes the same
+// tile loop, ll_gram_tile, with another operand functor: its two factors are plain Grams of [1, phi_i] and [1, p_i].
 #include "lip_internal.h"
 
 namespace lip {
@@ -34,6 +37,16 @@ struct LLPlan {
   int ys, nper;          // example ranges and examples per range (a multiple of LL_SPAN)
 };
 
+// split n examples over ys ranges of nper (whole spans) until a launch of `tiles` tiles has ~4 blocks per CU
+static void ll_split(int n, long long tiles, int& ys_out, int& nper) {
+  long long spans = ((long long)n + LL_SPAN - 1) / LL_SPAN, ys = (1024 + tiles - 1) / tiles;
+  if (ys > spans) ys = spans;
+  if (ys > 4096) ys = 4096;
+  if (ys < 1) ys = 1;
+  nper = (int)((spans + ys - 1) / ys) * LL_SPAN;
+  ys_out = (int)(((long long)n + nper - 1) / nper);
+}
+
 static LLPlan ll_plan(int n, int F, int K, bool softmax) {
   LLPlan p;
   p.Ft = F + 1;
@@ -44,13 +57,7 @@ static LLPlan ll_plan(int n, int F, int K, bool softmax) {
   p.TF = (p.Ft + LL_B - 1) / LL_B;
   p.Tc = (p.Ft * p.Kc + LL_B - 1) / LL_B;
   p.tiles = (long long)p.Tuu + (long long)p.TF * p.Tc;
-  // split the examples until the launch has ~4 blocks per CU, whole spans per range
-  long long spans = ((long long)n + LL_SPAN - 1) / LL_SPAN, ys = (1024 + p.tiles - 1) / p.tiles;
-  if (ys > spans) ys = spans;
-  if (ys > 4096) ys = 4096;
-  if (ys < 1) ys = 1;
-  p.nper = (int)((spans + ys - 1) / ys) * LL_SPAN;
-  p.ys = (int)(((long long)n + p.nper - 1) / p.nper);
+  ll_split(n, p.tiles, p.ys, p.nper);
   return p;
 }
 
@@ -62,43 +69,37 @@ __device__ __forceinline__ double ll_operand(const float* __restrict__ Phi, long
   return v;
 }
 
-__global__ __launch_bounds__(256) void ll_gram_kernel(const float* __restrict__ Phi, long long ldphi,
-                                                      const float* __restrict__ Pr, int n, int K, LLPlan pl,
-                                                      double* __restrict__ part) {
-  __shared__ double red[3 * LL_TILE];
+// The operand pair of one lane of ll_gram_kernel: rows are flat (f, k) of the DL space for a UU tile and features for a
+// D tile; columns are flat (g, l) with Kc classes per feature.  t picks the 16-wide half of the 32-wide tile.
+struct LLHeadOperands {
+  const float* __restrict__ Phi;
+  long long ldphi;
+  const float* __restrict__ Pr;
+  int K;
+  bool uu, softmax;
+  int rf[2], rk[2], cf[2], ck[2];
+  __device__ __forceinline__ double row(int i, int t) const { return ll_operand(Phi, ldphi, Pr, K, i, rf[t], rk[t], uu); }
+  __device__ __forceinline__ double col(int i, int t) const { return ll_operand(Phi, ldphi, Pr, K, i, cf[t], ck[t], softmax); }
+};
+
+// The operand pair of one lane of a plain Gram of the augmented rows xt_i = [1, X[i][0..C)]: index 0 is the constant.
+struct LLAugOperands {
+  const float* __restrict__ X;
+  long long ld;
+  int r[2], c[2];
+  __device__ __forceinline__ double at(int i, int j) const { return j == 0 ? 1.0 : (double)X[(long long)i * ld + (j - 1)]; }
+  __device__ __forceinline__ double row(int i, int t) const { return at(i, r[t]); }
+  __device__ __forceinline__ double col(int i, int t) const { return at(i, c[t]); }
+};
+
+// One 32 x 32 partial tile sum_{i in [ib, ie)} row_i col_i^T of a block: its four waves take every fourth 16-example
+// chunk on v_mfma_f64_16x16x4_f64, meet in LDS (red, 3 tiles) in wave order, and wave 0 writes the tile to mine.
+template <class Operands>
+__device__ __forceinline__ void ll_gram_tile(const Operands& op, int ib, int ie, double* __restrict__ red,
+                                             double* __restrict__ mine) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i16 = lane & 15, q = lane >> 4;
-  const int tile = blockIdx.x;
-  const bool softmax = Pr != nullptr;
-  // rows: flat (f, k) of the DL space for a UU tile, features for a D tile; columns: flat (g, l) with Kc classes
-  bool uu = tile < pl.Tuu;
-  int r0, c0;
-  if (uu) {
-    int tr = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
-    while ((tr + 1) * (tr + 2) / 2 <= tile) ++tr;
-    while (tr * (tr + 1) / 2 > tile) --tr;
-    r0 = tr * LL_B;
-    c0 = (tile - tr * (tr + 1) / 2) * LL_B;
-  } else {
-    const int t = tile - pl.Tuu;
-    r0 = (t / pl.Tc) * LL_B;
-    c0 = (t % pl.Tc) * LL_B;
-    // only f <= g is ever read: a tile whose smallest f lies above its largest g has nothing to compute
-    const int cmax = min(c0 + LL_B - 1, pl.Ft * pl.Kc - 1);
-    if (r0 > cmax / pl.Kc) return;
-  }
-  const int rows = uu ? pl.DL : pl.Ft, cols = pl.Ft * pl.Kc;
-  int rf[2], rk[2], cf[2], ck[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int r = min(r0 + 16 * t + i16, rows - 1), c = min(c0 + 16 * t + i16, cols - 1);   // clamped: never read back
-    rf[t] = uu ? r / K : r;
-    rk[t] = uu ? r % K : 0;
-    cf[t] = c / pl.Kc;
-    ck[t] = c % pl.Kc;
-  }
-  const int ib = blockIdx.y * pl.nper, ie = min(ib + pl.nper, n);
   ll_f64x4 acc[2][2];
 #pragma unroll
   for (int tm = 0; tm < 2; ++tm)
@@ -113,8 +114,8 @@ __global__ __launch_bounds__(256) void ll_gram_kernel(const float* __restrict__ 
       const int ic = ok ? i : ie - 1;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const double av = ll_operand(Phi, ldphi, Pr, K, ic, rf[t], rk[t], uu);
-        const double bv = ll_operand(Phi, ldphi, Pr, K, ic, cf[t], ck[t], softmax);
+        const double av = op.row(ic, t);
+        const double bv = op.col(ic, t);
         a[s][t] = ok ? av : 0.0;
         b[s][t] = ok ? bv : 0.0;
       }
@@ -138,7 +139,6 @@ __global__ __launch_bounds__(256) void ll_gram_kernel(const float* __restrict__ 
   }
   __syncthreads();
   if (wave == 0) {
-    double* mine = part + ((long long)blockIdx.y * pl.tiles + tile) * LL_TILE;
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -149,6 +149,51 @@ __global__ __launch_bounds__(256) void ll_gram_kernel(const float* __restrict__ 
           mine[e] = ((acc[tm][tn][r] + red[e]) + red[LL_TILE + e]) + red[2 * LL_TILE + e];
         }
   }
+}
+
+// (row, column) of lower-triangle tile number `tile`, rows first: tile = tr (tr + 1) / 2 + tc, tc <= tr
+__device__ __forceinline__ void ll_tri_tile(int tile, int& tr, int& tc) {
+  tr = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
+  while ((tr + 1) * (tr + 2) / 2 <= tile) ++tr;
+  while (tr * (tr + 1) / 2 > tile) --tr;
+  tc = tile - tr * (tr + 1) / 2;
+}
+
+__global__ __launch_bounds__(256) void ll_gram_kernel(const float* __restrict__ Phi, long long ldphi,
+                                                      const float* __restrict__ Pr, int n, int K, LLPlan pl,
+                                                      double* __restrict__ part) {
+  __shared__ double red[3 * LL_TILE];
+  const int i16 = threadIdx.x & 15;
+  const int tile = blockIdx.x;
+  LLHeadOperands op;
+  op.Phi = Phi, op.ldphi = ldphi, op.Pr = Pr, op.K = K;
+  op.softmax = Pr != nullptr;
+  op.uu = tile < pl.Tuu;
+  int r0, c0;
+  if (op.uu) {
+    int tr, tc;
+    ll_tri_tile(tile, tr, tc);
+    r0 = tr * LL_B;
+    c0 = tc * LL_B;
+  } else {
+    const int t = tile - pl.Tuu;
+    r0 = (t / pl.Tc) * LL_B;
+    c0 = (t % pl.Tc) * LL_B;
+    // only f <= g is ever read: a tile whose smallest f lies above its largest g has nothing to compute
+    const int cmax = min(c0 + LL_B - 1, pl.Ft * pl.Kc - 1);
+    if (r0 > cmax / pl.Kc) return;
+  }
+  const int rows = op.uu ? pl.DL : pl.Ft, cols = pl.Ft * pl.Kc;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int r = min(r0 + 16 * t + i16, rows - 1), c = min(c0 + 16 * t + i16, cols - 1);   // clamped: never read back
+    op.rf[t] = op.uu ? r / K : r;
+    op.rk[t] = op.uu ? r % K : 0;
+    op.cf[t] = c / pl.Kc;
+    op.ck[t] = c % pl.Kc;
+  }
+  const int ib = blockIdx.y * pl.nper;
+  ll_gram_tile(op, ib, min(ib + pl.nper, n), red, part + ((long long)blockIdx.y * pl.tiles + tile) * LL_TILE);
 }
 
 // G[r][c] += delta_kl D[min(f,g)][(max(f,g), l)] - UU[max(r,c)][min(r,c)], each a sum over the example ranges in order
@@ -204,6 +249,161 @@ __global__ __launch_bounds__(256) void ll_predict_kernel(const float* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------------------------- Kronecker factors
+// A = sum_i phit_i phit_i^T and Bf = sum_i diag(p_i) - p_i p_i^T are both read off plain Grams of augmented rows:
+// phit_i = [1, phi_i] is one already, and with pt_i = [1, p_i] the Gram P = sum_i pt_i pt_i^T holds sum_i p_i[k] in
+// P[k + 1][0] and sum_i p_i[k] p_i[l] in P[k + 1][l + 1].  One launch computes the lower-triangle tiles of both.
+struct LLKronPlan {
+  int Ft, Kt;            // edge of the two Grams; Kt = K + 1, or 0 for the Gaussian head (Bf = n I needs no Gram)
+  int tilesA, tilesB;    // lower-triangle 32 x 32 tiles of each
+  long long tiles;
+  int ys, nper;
+};
+
+static LLKronPlan ll_kron_plan(int n, int F, int K, bool softmax) {
+  LLKronPlan p;
+  p.Ft = F + 1;
+  p.Kt = softmax ? K + 1 : 0;
+  const long long ta = (p.Ft + LL_B - 1) / LL_B, tb = (p.Kt + LL_B - 1) / LL_B;
+  p.tilesA = (int)(ta * (ta + 1) / 2);
+  p.tilesB = (int)(tb * (tb + 1) / 2);
+  p.tiles = (long long)p.tilesA + p.tilesB;
+  ll_split(n, p.tiles, p.ys, p.nper);
+  return p;
+}
+
+__global__ __launch_bounds__(256) void ll_kron_gram_kernel(const float* __restrict__ Phi, long long ldphi,
+                                                           const float* __restrict__ Pr, int n, int K, LLKronPlan pl,
+                                                           double* __restrict__ part) {
+  __shared__ double red[3 * LL_TILE];
+  const int i16 = threadIdx.x & 15;
+  const int tile = blockIdx.x;
+  const bool isA = tile < pl.tilesA;
+  int tr, tc;
+  ll_tri_tile(isA ? tile : tile - pl.tilesA, tr, tc);
+  LLAugOperands op;
+  op.X = isA ? Phi : Pr;
+  op.ld = isA ? ldphi : (long long)K;
+  const int dim = isA ? pl.Ft : pl.Kt;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    op.r[t] = min(tr * LL_B + 16 * t + i16, dim - 1);                                        // clamped: never read back
+    op.c[t] = min(tc * LL_B + 16 * t + i16, dim - 1);
+  }
+  const int ib = blockIdx.y * pl.nper;
+  ll_gram_tile(op, ib, min(ib + pl.nper, n), red, part + ((long long)blockIdx.y * pl.tiles + tile) * LL_TILE);
+}
+
+// out[r][c] += P[max + shift][min + shift]                              (shift = 0: A from the Gram of phit)
+// out[r][c] += delta_rc P[r + 1][0] - P[max + 1][min + 1]               (shift = 1: Bf from the Gram of [1, p])
+// P the lower-triangle tiles starting at tile0, each entry a sum over the example ranges in index order
+__global__ __launch_bounds__(256) void ll_kron_assemble_kernel(const double* __restrict__ part, long long tiles, int ys,
+                                                               int tile0, int dim, int shift, double* __restrict__ out) {
+  const int c = blockIdx.x * 16 + (threadIdx.x & 15), r = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (r >= dim || c >= dim) return;
+  const int hi = max(r, c) + shift, lo = min(r, c) + shift;
+  const int th = hi / LL_B, tl = lo / LL_B;
+  const double* src = part + ((long long)tile0 + th * (th + 1) / 2 + tl) * LL_TILE + (hi % LL_B) * LL_B + lo % LL_B;
+  double v = 0.0;
+  for (int y = 0; y < ys; ++y) v += src[(long long)y * tiles * LL_TILE];
+  if (shift) {
+    double d = 0.0;
+    if (r == c) {
+      const double* sd = part + ((long long)tile0 + th * (th + 1) / 2) * LL_TILE + (hi % LL_B) * LL_B;
+      for (int y = 0; y < ys; ++y) d += sd[(long long)y * tiles * LL_TILE];
+    }
+    v = d - v;
+  }
+  out[(long long)r * dim + c] += v;
+}
+
+__global__ void ll_diag_add_kernel(double* __restrict__ M, int dim, double v) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < dim) M[(long long)k * dim + k] += v;
+}
+
+// ------------------------------------------------------------------------------------------- Kronecker predictive
+// C[b][c] = sum_j a(b, j) Bm[j][c], b < B, j < J, c < N (Bm row-major); a(b, j) = phit_b[j] from Phi, or U[b][j]^2 with
+// SQUARED.  A wave per 16 x 16 tile of C on v_mfma_f64_16x16x4_f64: lane l holds a(row l & 15, j0 + (l >> 4)) and
+// Bm[j0 + (l >> 4)][col l & 15]; result register r of lane l is (row (l >> 4) + 4 r, col l & 15).
+template <bool SQUARED>
+__global__ __launch_bounds__(256) void ll_kron_gemm_kernel(const float* __restrict__ Phi, long long ldphi,
+                                                           const double* __restrict__ U, int B, int J,
+                                                           const double* __restrict__ Bm, int N, double* __restrict__ C) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const int ct = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), rt = blockIdx.y;
+  if (ct * 16 >= N) return;
+  const int b = min(rt * 16 + i16, B - 1), c = min(ct * 16 + i16, N - 1);      // clamped: never written back
+  auto a_of = [&](int j) -> double {
+    if (SQUARED) {
+      const double u = U[(long long)b * J + j];
+      return u * u;
+    }
+    return j == 0 ? 1.0 : (double)Phi[(long long)b * ldphi + (j - 1)];
+  };
+  ll_f64x4 acc = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  int j0 = 0;
+  // eight k-steps per round, every load issued before the first product; the sum stays in j order
+  for (; j0 + 32 <= J; j0 += 32) {
+    double av[8], bv[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int j = j0 + 4 * s + q;
+      av[s] = a_of(j);
+      bv[s] = Bm[(long long)j * N + c];
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0);
+  }
+  for (; j0 < J; j0 += 4) {
+    const int j = j0 + q;
+    const bool ok = j < J;
+    const int jc = ok ? j : J - 1;
+    const double av = a_of(jc), bv = Bm[(long long)jc * N + c];
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ok ? av : 0.0, ok ? bv : 0.0, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = rt * 16 + q + 4 * r, col = ct * 16 + i16;
+    if (row < B && col < N) C[(long long)row * N + col] = acc[r];
+  }
+}
+
+// One entry out[b][k][m] = sum_l Ub[k][l] Ub[m][l] s_b[l] by one wave: a lane per l (every 64th), the lanes' partial sums
+// met by a fixed butterfly.  Both forms below go through it, so the diag form equals the diagonal of the full form bitwise.
+__device__ __forceinline__ double ll_kron_cov_entry(const double* __restrict__ uk, const double* __restrict__ um,
+                                                    const double* __restrict__ s, int K, int lane) {
+  double t = 0.0;
+  for (int l = lane; l < K; l += 64) t = fma(uk[l] * um[l], s[l], t);
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) t += __shfl_xor(t, w, 64);
+  return t;
+}
+
+// full form: block = (b, k), a wave per m >= k, mirrored
+__global__ __launch_bounds__(256) void ll_kron_cov_kernel(const double* __restrict__ Ub, const double* __restrict__ S, int K,
+                                                          double* __restrict__ out) {
+  const int b = blockIdx.x, k = blockIdx.y, lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int m = k + wave; m < K; m += 4) {
+    const double t = ll_kron_cov_entry(Ub + (long long)k * K, Ub + (long long)m * K, S + (long long)b * K, K, lane);
+    if (lane == 0) {
+      out[((long long)b * K + k) * K + m] = t;
+      out[((long long)b * K + m) * K + k] = t;
+    }
+  }
+}
+
+// diag form: block = (four test points, k), a wave per test point, m = k
+__global__ __launch_bounds__(256) void ll_kron_var_kernel(const double* __restrict__ Ub, const double* __restrict__ S, int B,
+                                                          int K, double* __restrict__ out) {
+  const int k = blockIdx.y, lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (b >= B) return;
+  const double t = ll_kron_cov_entry(Ub + (long long)k * K, Ub + (long long)k * K, S + (long long)b * K, K, lane);
+  if (lane == 0) out[(long long)b * K + k] = t;
+}
+
 }  // namespace lip
 
 using namespace lip;
@@ -248,6 +448,89 @@ int lip_ll_predict(const float* Phi, int64_t ldphi, int32_t B, int32_t F, int32_
   if (!Phi || !S || !out || !ll_shape_ok(B, F, K) || ldphi < F || K > 65535) { set_error("lip_ll_predict: bad argument"); return LIP_ERR_ARG; }
   hipLaunchKernelGGL(ll_predict_kernel, dim3((unsigned)B, (unsigned)K), dim3(256), 0, (hipStream_t)stream, Phi,
                      (long long)ldphi, F, K, S, out, (int)diag);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_ll_kron_factors_scratch(int32_t n, int32_t F, int32_t K, int64_t* doubles) {
+  if (!doubles || !ll_shape_ok(n, F, K)) { set_error("lip_ll_kron_factors_scratch: bad argument"); return LIP_ERR_ARG; }
+  // the softmax plan has the tiles of the Gaussian one and more, but the split differs: take the larger
+  const LLKronPlan a = ll_kron_plan(n, F, K, true), b = ll_kron_plan(n, F, K, false);
+  const long long da = a.tiles * a.ys * LL_TILE, db = b.tiles * b.ys * LL_TILE;
+  *doubles = da > db ? da : db;
+  return LIP_OK;
+}
+
+int lip_ll_kron_factors(const float* Phi, int64_t ldphi, const float* Pr, int32_t n, int32_t F, int32_t K, double* A,
+                        double* Bf, double* scratch, int64_t scratch_doubles, void* stream) {
+  if (!Phi || !A || !Bf || !scratch || !ll_shape_ok(n, F, K) || ldphi < F) {
+    set_error("lip_ll_kron_factors: bad argument");
+    return LIP_ERR_ARG;
+  }
+  const LLKronPlan pl = ll_kron_plan(n, F, K, Pr != nullptr);
+  const long long need = pl.tiles * pl.ys * LL_TILE;
+  if (scratch_doubles < need) {
+    set_error("lip_ll_kron_factors: scratch of %lld doubles, %lld needed (lip_ll_kron_factors_scratch)",
+              (long long)scratch_doubles, need);
+    return LIP_ERR_ARG;
+  }
+  const unsigned ga = (unsigned)((pl.Ft + 15) / 16), gb = (unsigned)((K + 15) / 16);
+  if (pl.tiles > 0x7fffffffll || ga > 65535 || gb > 65535) {
+    set_error("lip_ll_kron_factors: F = %d, K = %d is too large", (int)F, (int)K);
+    return LIP_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ll_kron_gram_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.ys), dim3(256), 0, st, Phi, (long long)ldphi,
+                     Pr, n, K, pl, scratch);
+  LIP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ll_kron_assemble_kernel, dim3(ga, ga), dim3(256), 0, st, (const double*)scratch, pl.tiles, pl.ys, 0,
+                     pl.Ft, 0, A);
+  LIP_CHECK_HIP(hipGetLastError());
+  if (Pr)
+    hipLaunchKernelGGL(ll_kron_assemble_kernel, dim3(gb, gb), dim3(256), 0, st, (const double*)scratch, pl.tiles, pl.ys,
+                       pl.tilesA, (int)K, 1, Bf);
+  else
+    hipLaunchKernelGGL(ll_diag_add_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, Bf, (int)K, (double)n);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_ll_kron_predict_scratch(int32_t B, int32_t F, int32_t K, int64_t* doubles) {
+  if (!doubles || !ll_shape_ok(B, F, K)) { set_error("lip_ll_kron_predict_scratch: bad argument"); return LIP_ERR_ARG; }
+  *doubles = (long long)B * ((long long)F + 1 + K);                 // u (B, F + 1) and s (B, K)
+  return LIP_OK;
+}
+
+int lip_ll_kron_predict(const float* Phi, int64_t ldphi, int32_t B, int32_t F, int32_t K, const double* V, const double* R,
+                        const double* Ub, double* out, int32_t diag, double* scratch, int64_t scratch_doubles, void* stream) {
+  if (!Phi || !V || !R || !Ub || !out || !scratch || !ll_shape_ok(B, F, K) || ldphi < F || K > 65535 ||
+      ((long long)B + 15) / 16 > 65535) {
+    set_error("lip_ll_kron_predict: bad argument");
+    return LIP_ERR_ARG;
+  }
+  const int Ft = F + 1;
+  const long long need = (long long)B * ((long long)Ft + K);
+  if (scratch_doubles < need) {
+    set_error("lip_ll_kron_predict: scratch of %lld doubles, %lld needed (lip_ll_kron_predict_scratch)",
+              (long long)scratch_doubles, need);
+    return LIP_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double* u = scratch;
+  double* s = scratch + (long long)B * Ft;
+  const unsigned gy = (unsigned)((B + 15) / 16);
+  // u = phit V, then s = (u o u) R
+  hipLaunchKernelGGL(ll_kron_gemm_kernel<false>, dim3((unsigned)((Ft + 63) / 64), gy), dim3(256), 0, st, Phi, (long long)ldphi,
+                     (const double*)nullptr, (int)B, Ft, V, Ft, u);
+  LIP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ll_kron_gemm_kernel<true>, dim3((unsigned)((K + 63) / 64), gy), dim3(256), 0, st, (const float*)nullptr,
+                     0ll, (const double*)u, (int)B, Ft, R, (int)K, s);
+  LIP_CHECK_HIP(hipGetLastError());
+  if (diag)
+    hipLaunchKernelGGL(ll_kron_var_kernel, dim3((unsigned)((B + 3) / 4), (unsigned)K), dim3(256), 0, st, Ub, (const double*)s,
+                       (int)B, (int)K, out);
+  else
+    hipLaunchKernelGGL(ll_kron_cov_kernel, dim3((unsigned)B, (unsigned)K), dim3(256), 0, st, Ub, (const double*)s, (int)K, out);
   LIP_CHECK_HIP(hipGetLastError());
   return LIP_OK;
 }

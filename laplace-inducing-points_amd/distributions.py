@@ -8,6 +8,8 @@ Supports a batch of distributions: loc (..., k), covariance (..., k, k).
 ``MultivariateNormalDiag`` (not in the reference) is the diagonal-covariance twin that ``posterior_lla_diag`` returns:
 ``.mean() .variance() .stddev() .sample(sample_shape, seed)`` and no (k, k) ``covariance()``, which would not fit at
 the sizes a diagonal posterior is used for.
+
+``KroneckerNormal`` (not in the reference) is the factored Gaussian that ``posterior_lla_last_layer_kron`` returns.
 """
 from __future__ import annotations
 
@@ -73,3 +75,53 @@ class MultivariateNormalDiag:
         shape = tuple(sample_shape) + tuple(torch.broadcast_shapes(self.loc.shape, self._var.shape))
         eps = torch.randn(shape, dtype=self.loc.dtype, device=self.loc.device, generator=g)
         return self.loc + self.stddev() * eps
+
+
+class KroneckerNormal:
+    """N(loc, S) over a (Ft, K) block flattened row-major (index f K + k), with the covariance in factored form
+    S[(f,k)][(g,m)] = sum_{j,l} V[f][j] V[g][j] Ub[k][l] Ub[m][l] R[j][l]; V (Ft, Ft), R (Ft, K) positive, Ub (K, K),
+    loc (Ft K,).  ``spectrum`` = (lam (Ft,), mu (K,), c) with R = 1 / (c lam mu^T + 1), when known, keeps the
+    log-determinant free of the cancellation in log R."""
+    def __init__(self, loc: torch.Tensor, V: torch.Tensor, R: torch.Tensor, Ub: torch.Tensor, spectrum=None):
+        Ft, K = R.shape
+        if tuple(V.shape) != (Ft, Ft) or tuple(Ub.shape) != (K, K) or loc.shape[-1] != Ft * K:
+            raise ValueError(f"V {tuple(V.shape)}, R {tuple(R.shape)}, Ub {tuple(Ub.shape)} and loc {tuple(loc.shape)} do "
+                             f"not describe one ({Ft}, {K}) block")
+        self.loc, self.V, self.R, self.Ub, self.spectrum = loc, V, R, Ub, spectrum
+
+    def mean(self) -> torch.Tensor:
+        return self.loc
+
+    def variance(self) -> torch.Tensor:
+        return ((self.V * self.V) @ self.R @ (self.Ub * self.Ub).T).reshape(-1)
+
+    def stddev(self) -> torch.Tensor:
+        return torch.sqrt(self.variance())
+
+    def covariance(self) -> torch.Tensor:
+        from .last_layer import LAST_LAYER_MAX_DIM
+        Ft, K = self.R.shape
+        if Ft * K > LAST_LAYER_MAX_DIM:
+            raise ValueError(f"a dense {Ft * K} x {Ft * K} covariance is not built (more than LAST_LAYER_MAX_DIM = "
+                             f"{LAST_LAYER_MAX_DIM} parameters): use variance(), sample() or the factors V, R, Ub")
+        W = torch.kron(self.V, self.Ub)
+        return (W * self.R.reshape(-1)[None, :]) @ W.T
+
+    def log_det_precision_ratio(self) -> torch.Tensor:
+        """log det(prior^-1 posterior precision) = -sum log R = sum log1p(c lam mu)"""
+        if self.spectrum is not None:
+            lam, mu, c = self.spectrum
+            return torch.log1p(c * lam[:, None] * mu[None, :]).sum()
+        return -torch.log(self.R).sum()
+
+    def sample(self, sample_shape=(), seed=None) -> torch.Tensor:
+        """loc + vec(V (E o sqrt(R)) Ub^T), E standard normal of shape sample_shape + (Ft, K)"""
+        if isinstance(sample_shape, int):
+            sample_shape = (sample_shape,)
+        g = None
+        if seed is not None:
+            g = torch.Generator(device=self.loc.device).manual_seed(int(seed))
+        Ft, K = self.R.shape
+        E = torch.randn(tuple(sample_shape) + (Ft, K), dtype=self.loc.dtype, device=self.loc.device, generator=g)
+        dW = self.V @ (E * torch.sqrt(self.R)) @ self.Ub.T
+        return self.loc + dW.reshape(tuple(sample_shape) + (Ft * K,))

@@ -719,6 +719,29 @@ class LinearizedNet:
                                      scratch.data_ptr(), scratch.numel(), nv.stream_ptr()), "lip_ll_ggn")
         return out
 
+    def last_layer_kron_factors(self, A: torch.Tensor, Bf: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """ADD this binding's examples into the two Kronecker factors of the last-layer curvature
+        (``lip_ll_kron_factors``): A (F + 1, F + 1) += sum_i phit_i phit_i^T and Bf (K, K) += sum_i diag(p_i) - p_i p_i^T
+        for the classifier, n I for the regressor; both float64, from the cached features and probabilities, bitwise
+        reproducible and exactly symmetric."""
+        _, F, K = self.cn.last_layer()
+        for name, t, d in (("A", A, F + 1), ("Bf", Bf, K)):
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (d, d)):
+                raise ValueError(f"{name} must be a contiguous float64 device matrix of {d} x {d}")
+        scratch = self._scratches.get("lip_ll_kron_factors_scratch")
+        if scratch is None:
+            doubles = C.c_int64(0)
+            nv.check(self.lib.lip_ll_kron_factors_scratch(self.n, F, K, C.byref(doubles)), "lip_ll_kron_factors_scratch")
+            scratch = self._scratches["lip_ll_kron_factors_scratch"] = torch.empty(max(1, doubles.value), device=self.device,
+                                                                                   dtype=torch.float64)
+        cn = self.cn
+        phi = self.prim[cn.a_off[cn.last_unit().src]:]
+        pr = self.prim[cn.prob_off:] if cn.classifier else None
+        nv.check(self.lib.lip_ll_kron_factors(phi.data_ptr(), F, 0 if pr is None else pr.data_ptr(), self.n, F, K,
+                                              A.data_ptr(), Bf.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                              nv.stream_ptr()), "lip_ll_kron_factors")
+        return A, Bf
+
     # ------------------------------------------------------------------------------ measurement
     def profile(self, enable: bool):
         nv.check(self.lib.lip_engine_profile(self.h, int(enable)), "lip_engine_profile")

@@ -263,6 +263,13 @@ def compute_ggn_last_layer(state, Z, model_type, full_set_size=None, example_chu
     return last_layer.compute_ggn_last_layer(state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk)
 
 
+def compute_kron_factors_last_layer(state, Z, model_type, example_chunk: Optional[int] = None):
+    """``(A (F + 1, F + 1), Bf (K, K), M)``: the Kronecker factors of the last-layer curvature, float64, unscaled
+    (:func:`last_layer_kron.compute_kron_factors_last_layer`)."""
+    from . import last_layer_kron
+    return last_layer_kron.compute_kron_factors_last_layer(state, Z, model_type, example_chunk=example_chunk)
+
+
 FACTOR_BYTES_LIMIT = 64 << 30
 
 

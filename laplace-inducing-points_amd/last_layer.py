@@ -28,18 +28,19 @@ from .utils import flatten_nn_params, param_layout
 LAST_LAYER_MAX_DIM = 8192
 
 
-def last_layer_slice(state) -> Tuple[int, int, int]:
+def last_layer_slice(state, max_dim: Optional[int] = LAST_LAYER_MAX_DIM) -> Tuple[int, int, int]:
     """``(offset, F, K)`` of the final Dense layer of ``state.net`` in the flat parameter vector, from the layer program
     and ``param_layout`` alone (pure Python, no GPU, nothing written).  Raises ``ValueError`` when the network does not
-    end in a plain Dense, or when DL = (F + 1) K exceeds ``LAST_LAYER_MAX_DIM`` — before anything is allocated."""
+    end in a plain Dense, or when DL = (F + 1) K exceeds ``max_dim`` (``None``: no cap, for the factored posterior of
+    ``last_layer_kron.py``) — before anything is allocated."""
     net = getattr(state, "net", None)
     if net is None:
         raise TypeError("the last-layer posterior needs state.net (a NetSpec layer program)")
     off, F, K = last_layer_of(net, {path: (o, shape) for path, o, shape in param_layout(state.params)})
     DL = (F + 1) * K
-    if DL > LAST_LAYER_MAX_DIM:
+    if max_dim is not None and DL > max_dim:
         raise ValueError(f"the last layer has (F + 1) K = ({F} + 1) * {K} = {DL} parameters, more than "
-                         f"LAST_LAYER_MAX_DIM = {LAST_LAYER_MAX_DIM}: a dense {DL} x {DL} covariance is not built; this is "
+                         f"LAST_LAYER_MAX_DIM = {max_dim}: a dense {DL} x {DL} covariance is not built; this is "
                          f"where a Kronecker-factored posterior is needed")
     return off, F, K
 

@@ -17,6 +17,8 @@ from .engine import LinearizedNet
 from .ggn import BlockOperator, compute_ggn_dense, compute_ggn_diag, compute_ggn_vp, get_engine
 from .last_layer import (LAST_LAYER_MAX_DIM, posterior_lla_last_layer, predict_lla_last_layer,     # noqa: F401
                          predict_lla_last_layer_scalable)                                         # beside their diagonal twins
+from .last_layer_kron import (posterior_lla_last_layer_kron, predict_lla_last_layer_kron,            # noqa: F401
+                              predict_lla_last_layer_kron_scalable)
 from .prior import check_dim, is_grouped
 from .sample import sample, sample_diag
 from .utils import flatten_nn_params

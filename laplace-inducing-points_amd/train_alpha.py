@@ -131,6 +131,26 @@ def fit_alpha_last_layer(X, state, model_type, full_set_size=None, alpha0: float
     return _fit_from_spectrum(lam, DL, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
+def log_marginal_likelihood_last_layer_kron(alpha, X, state, model_type: str, full_set_size: Optional[int] = None) -> float:
+    """:func:`log_marginal_likelihood_last_layer` under the Kronecker-factored curvature c A (x) Bf
+    (``last_layer_kron.py``; no size cap): the spectrum is outer(lam_A, mu_B) / M from two small ``eigvalsh`` calls.
+    Scalar alpha.  Not a reference function."""
+    from .last_layer_kron import _spectrum_last_layer_kron
+    N = full_set_size or X.shape[0]
+    lam, DL, theta2 = _spectrum_last_layer_kron(X, state, model_type)
+    return _lml_from_spectrum(float(alpha), lam, DL, theta2, N / X.shape[0])[0]
+
+
+def fit_alpha_last_layer_kron(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2,
+                              steps: int = 200):
+    """:func:`fit_alpha` on the Kronecker-factored last-layer evidence: ``(alpha, history)``; the factors and their two
+    eigendecompositions are computed once."""
+    from .last_layer_kron import _spectrum_last_layer_kron
+    N = full_set_size or X.shape[0]
+    lam, DL, theta2 = _spectrum_last_layer_kron(X, state, model_type)
+    return _fit_from_spectrum(lam, DL, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
+
+
 # ---- layer-wise precisions ------------------------------------------------------------------------------------------
 def grouped_spectrum(X, state, model_type, prior: GroupedPrior):
     """``(grams (G, d, d) float64, sizes (G,), theta_sqnorms (G,) float64)`` of the factor built at N/M = 1 like
