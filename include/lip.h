@@ -316,6 +316,38 @@ int lip_ll_kron_factors_scratch(int32_t n, int32_t F, int32_t K, int64_t* double
 int lip_ll_kron_predict(const float* Phi, int64_t ldphi, int32_t B, int32_t F, int32_t K, const double* V, const double* R,
                         const double* Ub, double* out, int32_t diag, double* scratch, int64_t scratch_doubles, void* stream);
 int lip_ll_kron_predict_scratch(int32_t B, int32_t F, int32_t K, int64_t* doubles);
+/* Subnetwork Laplace: the dense GGN block over an index set idx (S entries of the flat parameter vector, device int64)
+ * from per-example factor rows W (R, ldw) float32, ldw >= D: the rows lip_vjp_rows writes for one-hot probes in
+ * LIP_HEAD_L mode.  G (S, S) float64 row-major, ADDED into (example chunks and class chunks sum into one G):
+ *   G[a][c] += sum_{r < R} W[r][idx[a]] W[r][idx[c]].
+ * A gather kernel first writes the compact (R, S) float32 panel into scratch (every scattered column read once, the
+ * writes coalesced); the tile loop of lip_ll_ggn then runs over the panel: operands up-cast before any multiplication,
+ * accumulated on the float64 matrix pipe, the rows split over blocks whose partial tiles go to scratch (device,
+ * caller-owned, >= lip_sub_gram_scratch(R, S) doubles) and are added in index order by a second kernel: no atomics, so
+ * the result is bitwise reproducible, and one triangle of tiles is computed and mirrored, so a symmetric G stays exactly
+ * symmetric.  The gather clamps every index into [0, D): an index outside gives a wrong number, never an out-of-bounds
+ * read (callers validate).  A null W / idx / G / scratch, R, S or D <= 0, ldw < D or too small a scratch returns
+ * LIP_ERR_ARG and leaves G untouched. */
+int lip_sub_gram_scratch(int32_t R, int32_t S, int64_t* doubles);
+/* The first stage of lip_sub_gram on its own: panel (R, S) float32 row-major, overwritten, panel[r][a] = W[r][idx[a]]
+ * with the same clamp.  Same argument checks; panel is left untouched on LIP_ERR_ARG. */
+int lip_sub_gather(const float* W, int64_t ldw, int64_t D, int32_t R, const int64_t* idx, int32_t S, float* panel,
+                   void* stream);
+int lip_sub_gram(const float* W, int64_t ldw, int64_t D, int32_t R, const int64_t* idx, int32_t S, double* G, double* scratch,
+                 int64_t scratch_doubles, void* stream);
+/* The matching test-time quadratic form, float64, out overwritten.  Jr (K B, ldj) float32, ldj >= D, row k B + b the
+ * Jacobian row of output k at test point b (the (P = K, n = B, D) block lip_vjp_rows writes for one-hot probes in
+ * LIP_HEAD_IN mode); Sigma (S, S) float64 row-major (the posterior covariance over theta[idx]):
+ *   diag == 0: out (B, K, K), out[b][k][l] = sum_{a,c} Jr[k B + b][idx[a]] Sigma[a][c] Jr[l B + b][idx[c]], computed for
+ *              k <= l and mirrored (exactly symmetric);
+ *   diag != 0: out (B, K), the k == l entries only, bitwise those of the full form.
+ * The gathered float32 panel and T = panel Sigma ((K B, S) float64) live in scratch (>= lip_sub_predict_scratch(B, K, S)
+ * doubles); nothing larger is written.  Both products run on the float64 matrix pipe.  Indices are clamped as in
+ * lip_sub_gram.  A null pointer, B, K, S or D <= 0, ldj < D or too small a scratch returns LIP_ERR_ARG and leaves out
+ * untouched. */
+int lip_sub_predict_scratch(int32_t B, int32_t K, int32_t S, int64_t* doubles);
+int lip_sub_predict(const float* Jr, int64_t ldj, int64_t D, int32_t B, int32_t K, const int64_t* idx, int32_t S,
+                    const double* Sigma, double* out, int32_t diag, double* scratch, int64_t scratch_doubles, void* stream);
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);

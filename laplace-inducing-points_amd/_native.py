@@ -105,6 +105,12 @@ SIGNATURES = {
     "lip_ll_kron_predict": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, C.c_int32, _V, C.c_int64,
                                       _V]),
     "lip_ll_kron_predict_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_sub_gram_scratch": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_sub_gram": (C.c_int, [_V, C.c_int64, C.c_int64, C.c_int32, _V, C.c_int32, _V, _V, C.c_int64, _V]),
+    "lip_sub_gather": (C.c_int, [_V, C.c_int64, C.c_int64, C.c_int32, _V, C.c_int32, _V, _V]),
+    "lip_sub_predict_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_sub_predict": (C.c_int, [_V, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _V, C.c_int32, _V, _V, C.c_int32, _V,
+                                  C.c_int64, _V]),
     "lip_fill_rademacher": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_fill_normal": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
 }

@@ -1,0 +1,315 @@
+// Subnetwork Laplace: the dense GGN block over an arbitrary index set idx (S entries of the flat parameter vector) from
+// the per-example rows lip_vjp_rows writes (lip_sub_gram), and the matching test-time quadratic form (lip_sub_predict).
+// Everything after the gather in float64.
+//
+//   G[a][c]        += sum_{r < R} W[r][idx[a]] W[r][idx[c]]
+//   out[b][k][l]    = sum_{a,c} Jr[k B + b][idx[a]] Sigma[a][c] Jr[l B + b][idx[c]]
+//
+// Both start with sub_gather_kernel: the S scattered 4-byte columns of every row are read ONCE and written as a compact
+// (rows, S) float32 panel in the caller's scratch, coalesced.  Every later stage reads the panel: the 16 lanes of a
+// k-step of the Gram read 64 contiguous bytes.  Gathering inside the tile loop instead would re-read each scattered
+// column once per tile row of G (S / 32 times).  The gather clamps every index into [0, D): a bad index gives a wrong
+// number, never an out-of-bounds read.
+//
+// Gram: ll_gram_tile (lip_gramtile.h, the tile loop of lip_ll_ggn) over the lower triangle of 32 x 32 tiles x ranges of
+// rows; every block writes its partial tile to scratch and sub_assemble_kernel adds the ranges in index order, both
+// (a, c) and (c, a) from the same partial sums: no atomics, bitwise reproducible, exactly symmetric.
+//
+// Predict: T = panel Sigma ((K B, S) float64, in scratch; a wave per 32 x 32 tile on v_mfma_f64_16x16x4_f64), then per
+// test point the K x K product T_b panel_b^T on the same instruction, tiles with k-tile <= l-tile, entries k <= l written
+// and mirrored.  The diag form runs the diagonal tiles of the same kernel and keeps k == l, so it equals the diagonal of
+// the full form bitwise.  The panel rows are stored point-major (b K + k) so that a point's K rows are adjacent.
+#include "lip_internal.h"
+#include "lip_gramtile.h"
+
+namespace lip {
+
+// panel[(row map)(r)][a] = W[r][clamp(idx[a])];  KB == 0: rows in place;  KB = (K, B): source row k B + b -> b K + k
+__global__ __launch_bounds__(256) void sub_gather_kernel(const float* __restrict__ W, long long ldw, long long D,
+                                                         long long R, const long long* __restrict__ idx, int S, int K,
+                                                         int B, float* __restrict__ panel) {
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= S) return;
+  long long j = idx[a];
+  j = j < 0 ? 0 : (j >= D ? D - 1 : j);
+  for (long long r = blockIdx.y; r < R; r += gridDim.y) {
+    const long long dst = K > 0 ? (r % B) * K + r / B : r;
+    panel[dst * S + a] = W[r * ldw + j];
+  }
+}
+
+// The operand pair of one lane of a plain Gram of the panel's columns
+struct SubPanelOperands {
+  const float* __restrict__ P;
+  long long ld;
+  int r[2], c[2];
+  __device__ __forceinline__ double row(int i, int t) const { return (double)P[(long long)i * ld + r[t]]; }
+  __device__ __forceinline__ double col(int i, int t) const { return (double)P[(long long)i * ld + c[t]]; }
+};
+
+struct SubPlan {
+  int T;                 // tiles per edge
+  long long tiles;       // lower-triangle tiles
+  int ys, nper;          // row ranges and rows per range (a multiple of LL_SPAN)
+};
+
+static SubPlan sub_plan(int R, int S) {
+  SubPlan p;
+  p.T = (S + LL_B - 1) / LL_B;
+  p.tiles = (long long)p.T * (p.T + 1) / 2;
+  ll_split(R, p.tiles, p.ys, p.nper);
+  return p;
+}
+
+__global__ __launch_bounds__(256) void sub_gram_kernel(const float* __restrict__ panel, int R, int S, SubPlan pl,
+                                                       double* __restrict__ part) {
+  __shared__ double red[3 * LL_TILE];
+  const int i16 = threadIdx.x & 15;
+  const int tile = blockIdx.x;
+  int tr, tc;
+  ll_tri_tile(tile, tr, tc);
+  SubPanelOperands op;
+  op.P = panel, op.ld = S;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    op.r[t] = min(tr * LL_B + 16 * t + i16, S - 1);                                          // clamped: never read back
+    op.c[t] = min(tc * LL_B + 16 * t + i16, S - 1);
+  }
+  const int ib = blockIdx.y * pl.nper;
+  ll_gram_tile(op, ib, min(ib + pl.nper, R), red, part + ((long long)blockIdx.y * pl.tiles + tile) * LL_TILE);
+}
+
+// G[a][c] += P[max(a, c)][min(a, c)], P the lower-triangle tiles, each entry a sum over the row ranges in index order
+__global__ __launch_bounds__(256) void sub_assemble_kernel(const double* __restrict__ part, long long tiles, int ys, int S,
+                                                           double* __restrict__ G) {
+  const int c = blockIdx.x * 16 + (threadIdx.x & 15), r = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (r >= S || c >= S) return;
+  const int hi = max(r, c), lo = min(r, c);
+  const int th = hi / LL_B, tl = lo / LL_B;
+  const double* src = part + ((long long)th * (th + 1) / 2 + tl) * LL_TILE + (hi % LL_B) * LL_B + lo % LL_B;
+  double v = 0.0;
+  for (int y = 0; y < ys; ++y) v += src[(long long)y * tiles * LL_TILE];
+  G[(long long)r * S + c] += v;
+}
+
+// T (rows, S) = panel (rows, S) Sigma (S, S).  A wave per 32 x 32 tile of T (four 16 x 16 MFMA tiles), a block per four
+// column tiles.  Lane l holds panel[row l & 15][j0 + (l >> 4)] and Sigma[j0 + (l >> 4)][col l & 15]; result register r of
+// lane l is (row (l >> 4) + 4 r, col l & 15).  The sum stays in j order.
+__global__ __launch_bounds__(256) void sub_tsigma_kernel(const float* __restrict__ panel, long long rows, int S,
+                                                         const double* __restrict__ Sigma, double* __restrict__ T) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const int ct = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long r0 = (long long)blockIdx.y * 32;
+  if (ct * 32 >= S) return;
+  const float* pa[2];
+  const double* pb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const long long r = r0 + 16 * t + i16;
+    pa[t] = panel + (r < rows ? r : rows - 1) * S;                                           // clamped: never written back
+    pb[t] = Sigma + min(ct * 32 + 16 * t + i16, S - 1);
+  }
+  ll_f64x4 acc[2][2];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  int j0 = 0;
+  // four k-steps per round, every load issued before the first product
+  for (; j0 + 16 <= S; j0 += 16) {
+    double a[4][2], b[4][2];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int j = j0 + 4 * s + q;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        a[s][t] = (double)pa[t][j];
+        b[s][t] = pb[t][(long long)j * S];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+          acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][tm], b[s][tn], acc[tm][tn], 0, 0, 0);
+  }
+  for (; j0 < S; j0 += 4) {
+    const int j = j0 + q;
+    const bool ok = j < S;
+    const int jc = ok ? j : S - 1;
+    double a[2], b[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const double av = (double)pa[t][jc], bv = pb[t][(long long)jc * S];
+      a[t] = ok ? av : 0.0;
+      b[t] = ok ? bv : 0.0;
+    }
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+  }
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long long row = r0 + 16 * tm + q + 4 * r;
+        const int col = ct * 32 + 16 * tn + i16;
+        if (row < rows && col < S) T[row * S + col] = acc[tm][tn][r];
+      }
+}
+
+// out[b][k][l] = sum_a T[b K + k][a] panel[b K + l][a].  Block = (test point b, four tile pairs); a wave per 16 x 16 tile
+// (kt, lt), kt <= lt (diag: kt == lt), of the K x K product.  Entries k <= l are written and mirrored; diag keeps k == l.
+__global__ __launch_bounds__(256) void sub_quad_kernel(const double* __restrict__ T, const float* __restrict__ panel, int K,
+                                                       int S, double* __restrict__ out, int diag) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const int b = blockIdx.x;
+  const int pair = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int KT = (K + 15) / 16;
+  int kt, lt;
+  if (diag) {
+    if (pair >= KT) return;
+    kt = lt = pair;
+  } else {
+    if (pair >= KT * (KT + 1) / 2) return;
+    ll_tri_tile(pair, lt, kt);                                                               // lt >= kt
+  }
+  const double* ta = T + ((long long)b * K + min(kt * 16 + i16, K - 1)) * S;                 // clamped: never written back
+  const float* pb = panel + ((long long)b * K + min(lt * 16 + i16, K - 1)) * S;
+  ll_f64x4 acc = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  int a0 = 0;
+  for (; a0 + 16 <= S; a0 += 16) {
+    double av[4], bv[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      av[s] = ta[a0 + 4 * s + q];
+      bv[s] = (double)pb[a0 + 4 * s + q];
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0);
+  }
+  for (; a0 < S; a0 += 4) {
+    const int a = a0 + q;
+    const bool ok = a < S;
+    const int ac = ok ? a : S - 1;
+    const double av = ta[ac], bv = (double)pb[ac];
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ok ? av : 0.0, ok ? bv : 0.0, acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int k = kt * 16 + q + 4 * r, l = lt * 16 + i16;
+    if (k >= K || l >= K) continue;
+    if (diag) {
+      if (k == l) out[(long long)b * K + k] = acc[r];
+    } else if (k <= l) {
+      out[((long long)b * K + k) * K + l] = acc[r];
+      out[((long long)b * K + l) * K + k] = acc[r];
+    }
+  }
+}
+
+static long long sub_panel_doubles(long long rows, int S) { return (rows * S + 1) / 2; }
+
+static void sub_gather(const float* W, long long ldw, long long D, long long R, const int64_t* idx, int S, int K, int B,
+                       float* panel, hipStream_t st) {
+  const unsigned gy = (unsigned)(R < 65535 ? R : 65535);
+  hipLaunchKernelGGL(sub_gather_kernel, dim3((unsigned)((S + 255) / 256), gy), dim3(256), 0, st, W, ldw, D, R,
+                     (const long long*)idx, S, K, B, panel);
+}
+
+}  // namespace lip
+
+using namespace lip;
+
+static bool sub_rows_ok(int32_t B, int32_t K, int32_t S) {
+  return B > 0 && K > 0 && S > 0 && (long long)B * K <= 0x7fffffffll;
+}
+
+extern "C" {
+
+int lip_sub_gather(const float* W, int64_t ldw, int64_t D, int32_t R, const int64_t* idx, int32_t S, float* panel,
+                   void* stream) {
+  if (!W || !idx || !panel || R <= 0 || S <= 0 || D <= 0 || ldw < D) { set_error("lip_sub_gather: bad argument"); return LIP_ERR_ARG; }
+  sub_gather(W, (long long)ldw, (long long)D, R, idx, S, 0, 0, panel, (hipStream_t)stream);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_sub_gram_scratch(int32_t R, int32_t S, int64_t* doubles) {
+  if (!doubles || R <= 0 || S <= 0) { set_error("lip_sub_gram_scratch: bad argument"); return LIP_ERR_ARG; }
+  const SubPlan pl = sub_plan(R, S);
+  *doubles = sub_panel_doubles(R, S) + pl.tiles * pl.ys * LL_TILE;
+  return LIP_OK;
+}
+
+int lip_sub_gram(const float* W, int64_t ldw, int64_t D, int32_t R, const int64_t* idx, int32_t S, double* G,
+                 double* scratch, int64_t scratch_doubles, void* stream) {
+  if (!W || !idx || !G || !scratch || R <= 0 || S <= 0 || D <= 0 || ldw < D) {
+    set_error("lip_sub_gram: bad argument");
+    return LIP_ERR_ARG;
+  }
+  const SubPlan pl = sub_plan(R, S);
+  const long long pd = sub_panel_doubles(R, S), need = pd + pl.tiles * pl.ys * LL_TILE;
+  if (scratch_doubles < need) {
+    set_error("lip_sub_gram: scratch of %lld doubles, %lld needed (lip_sub_gram_scratch)", (long long)scratch_doubles, need);
+    return LIP_ERR_ARG;
+  }
+  if (pl.tiles > 0x7fffffffll || (S + 15) / 16 > 65535) { set_error("lip_sub_gram: S = %d is too large", (int)S); return LIP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  float* panel = (float*)scratch;
+  double* part = scratch + pd;
+  sub_gather(W, (long long)ldw, (long long)D, R, idx, S, 0, 0, panel, st);
+  LIP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(sub_gram_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.ys), dim3(256), 0, st, (const float*)panel, (int)R,
+                     (int)S, pl, part);
+  LIP_CHECK_HIP(hipGetLastError());
+  const unsigned gb = (unsigned)((S + 15) / 16);
+  hipLaunchKernelGGL(sub_assemble_kernel, dim3(gb, gb), dim3(256), 0, st, (const double*)part, pl.tiles, pl.ys, (int)S, G);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_sub_predict_scratch(int32_t B, int32_t K, int32_t S, int64_t* doubles) {
+  if (!doubles || !sub_rows_ok(B, K, S)) { set_error("lip_sub_predict_scratch: bad argument"); return LIP_ERR_ARG; }
+  const long long rows = (long long)B * K;
+  *doubles = sub_panel_doubles(rows, S) + rows * S;                  // the float32 panel and T (K B, S)
+  return LIP_OK;
+}
+
+int lip_sub_predict(const float* Jr, int64_t ldj, int64_t D, int32_t B, int32_t K, const int64_t* idx, int32_t S,
+                    const double* Sigma, double* out, int32_t diag, double* scratch, int64_t scratch_doubles, void* stream) {
+  if (!Jr || !idx || !Sigma || !out || !scratch || !sub_rows_ok(B, K, S) || D <= 0 || ldj < D) {
+    set_error("lip_sub_predict: bad argument");
+    return LIP_ERR_ARG;
+  }
+  const long long rows = (long long)B * K, pd = sub_panel_doubles(rows, S), need = pd + rows * S;
+  if (scratch_doubles < need) {
+    set_error("lip_sub_predict: scratch of %lld doubles, %lld needed (lip_sub_predict_scratch)", (long long)scratch_doubles,
+              need);
+    return LIP_ERR_ARG;
+  }
+  const long long KT = ((long long)K + 15) / 16, pairs = diag ? KT : KT * (KT + 1) / 2;
+  if ((rows + 31) / 32 > 65535 || (pairs + 3) / 4 > 65535) {
+    set_error("lip_sub_predict: B = %d, K = %d is too large", (int)B, (int)K);
+    return LIP_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* panel = (float*)scratch;
+  double* T = scratch + pd;
+  sub_gather(Jr, (long long)ldj, (long long)D, rows, idx, S, K, B, panel, st);
+  LIP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(sub_tsigma_kernel, dim3((unsigned)((S + 127) / 128), (unsigned)((rows + 31) / 32)), dim3(256), 0, st,
+                     (const float*)panel, rows, (int)S, Sigma, T);
+  LIP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(sub_quad_kernel, dim3((unsigned)B, (unsigned)((pairs + 3) / 4)), dim3(256), 0, st, (const double*)T,
+                     (const float*)panel, (int)K, (int)S, out, (int)diag);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+}  // extern "C"

@@ -742,6 +742,104 @@ class LinearizedNet:
                                               nv.stream_ptr()), "lip_ll_kron_factors")
         return A, Bf
 
+    # ------------------------------------------------------------------------------ subnetwork
+    ROW_BLOCK_BYTES = 2 << 30          # cap of a (P, n, D) float32 row block: the rule of ggn.materialize_factor
+
+    def _sub_index(self, idx: torch.Tensor) -> torch.Tensor:
+        """(S,) contiguous device int64 copy of ``idx``, checked against [0, D) before any launch"""
+        idx = torch.as_tensor(idx).reshape(-1)
+        if idx.numel() == 0 or idx.dtype not in (torch.int64, torch.int32):
+            raise ValueError("idx must be a non-empty integer index tensor")
+        if int(idx.min()) < 0 or int(idx.max()) >= self.D:
+            raise ValueError(f"idx must lie in [0, {self.D})")
+        return idx.to(device=self.device, dtype=torch.int64).contiguous()
+
+    def _sub_scratch(self, query: str, *shape: int) -> torch.Tensor:
+        """float64 scratch of ``lip_sub_gram`` / ``lip_sub_predict``: one buffer per query, kept and grown on demand"""
+        doubles = C.c_int64(0)
+        nv.check(getattr(self.lib, query)(*[int(s) for s in shape], C.byref(doubles)), query)
+        scratch = self._scratches.get(query)
+        if scratch is None or scratch.numel() < doubles.value:
+            scratch = self._scratches[query] = torch.empty(max(1, doubles.value), device=self.device, dtype=torch.float64)
+        return scratch
+
+    def _class_blocks(self, class_chunk: Optional[int]):
+        """(k0, k1) class blocks whose (k1 - k0, n, D) float32 rows stay under ``ROW_BLOCK_BYTES``"""
+        pc = max(1, min(self.K, (self.ROW_BLOCK_BYTES // (4 * self.D)) // self.n))
+        if class_chunk is not None:
+            if class_chunk < 1:
+                raise ValueError("class_chunk must be positive")
+            pc = min(pc, int(class_chunk))
+        return [(k0, min(self.K, k0 + pc)) for k0 in range(0, self.K, pc)]
+
+    def _one_hot_rows(self, k0: int, k1: int, mode: str) -> torch.Tensor:
+        """(k1 - k0, n, D) rows of :meth:`vjp_rows` for the probes e_k, k0 <= k < k1, on every example"""
+        E = torch.eye(self.K, device=self.device, dtype=torch.float32)[k0:k1, None, :].expand(k1 - k0, self.n, self.K)
+        return self.vjp_rows(E.contiguous(), mode)
+
+    def subnetwork_gram(self, idx: torch.Tensor, out: torch.Tensor, class_chunk: Optional[int] = None) -> torch.Tensor:
+        """ADD sum_i (J_i^T H_i J_i)[idx][:, idx] of this binding's examples into ``out`` (S, S) float64: the GGN block
+        over the flat-parameter indices ``idx``.  One-hot probes e_k on every example go through :meth:`vjp_rows` ('l') in
+        class blocks whose (Pc, n, D) float32 rows stay under 2 GiB (``class_chunk`` caps Pc further); each block's
+        rows are gathered to a compact (Pc n, S) panel and Gram-multiplied in float64 (``lip_sub_gram``): bitwise
+        reproducible and exactly symmetric."""
+        idx = self._sub_index(idx)
+        S = idx.numel()
+        if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (S, S)):
+            raise ValueError(f"out must be a contiguous float64 device matrix of {S} x {S}")
+        for k0, k1 in self._class_blocks(class_chunk):
+            rows = self._one_hot_rows(k0, k1, "l")
+            R = (k1 - k0) * self.n
+            scratch = self._sub_scratch("lip_sub_gram_scratch", R, S)
+            nv.check(self.lib.lip_sub_gram(rows.data_ptr(), self.D, self.D, R, idx.data_ptr(), S, out.data_ptr(),
+                                           scratch.data_ptr(), scratch.numel(), nv.stream_ptr()), "lip_sub_gram")
+        return out
+
+    def subnetwork_predict(self, idx: torch.Tensor, Sigma: torch.Tensor, diag: bool = False,
+                           class_chunk: Optional[int] = None) -> torch.Tensor:
+        """J_S(x) Sigma J_S(x)^T for every point of this binding, J_S the Jacobian columns ``idx``: (n, K, K) float64, or
+        (n, K) for ``diag`` (``lip_sub_predict`` on the 'raw' rows of :meth:`vjp_rows`).  The diag form runs in class
+        blocks like :meth:`subnetwork_gram`.  The full form needs all K rows of a point at once: when the (K, n, D)
+        float32 rows exceed 2 GiB it runs in chunks of points, and when the K rows of ONE point exceed it, it raises
+        ``ValueError`` before allocating."""
+        idx = self._sub_index(idx)
+        S, K, n = idx.numel(), self.K, self.n
+        if not (Sigma.is_cuda and Sigma.dtype == torch.float64 and Sigma.is_contiguous() and tuple(Sigma.shape) == (S, S)):
+            raise ValueError(f"Sigma must be a contiguous float64 device matrix of {S} x {S}")
+        if diag:
+            blocks = self._class_blocks(class_chunk)
+        else:
+            fit = (self.ROW_BLOCK_BYTES // (4 * self.D)) // K
+            if fit < 1:
+                raise ValueError(f"the full predictive needs the K = {K} Jacobian rows of a point at once: {K} x {self.D} "
+                                 f"floats exceed the row-block cap (use diag)")
+            blocks = [(0, K)]
+        out = torch.empty((n, K) if diag else (n, K, K), device=self.device, dtype=torch.float64)
+        if not diag and fit < n:
+            # the rows of all n points do not fit: chunks of `fit` points, each assembled from class-block sweeps (a sweep
+            # always covers every bound example, so the sweeps repeat per point chunk: bind fewer points to avoid it)
+            for b0 in range(0, n, fit):
+                b1 = min(n, b0 + fit)
+                Jr = torch.empty(K, b1 - b0, self.D, device=self.device, dtype=torch.float32)
+                for k0, k1 in self._class_blocks(class_chunk):
+                    Jr[k0:k1] = self._one_hot_rows(k0, k1, "raw")[:, b0:b1]
+                scratch = self._sub_scratch("lip_sub_predict_scratch", b1 - b0, K, S)
+                nv.check(self.lib.lip_sub_predict(Jr.data_ptr(), self.D, self.D, b1 - b0, K, idx.data_ptr(), S,
+                                                  Sigma.data_ptr(), out[b0:b1].data_ptr(), 0, scratch.data_ptr(),
+                                                  scratch.numel(), nv.stream_ptr()), "lip_sub_predict")
+            return out
+        for k0, k1 in blocks:
+            rows = self._one_hot_rows(k0, k1, "raw")
+            Kc = k1 - k0
+            scratch = self._sub_scratch("lip_sub_predict_scratch", n, Kc, S)
+            part = out if Kc == K else torch.empty(n, Kc, device=self.device, dtype=torch.float64)
+            nv.check(self.lib.lip_sub_predict(rows.data_ptr(), self.D, self.D, n, Kc, idx.data_ptr(), S, Sigma.data_ptr(),
+                                              part.data_ptr(), int(diag), scratch.data_ptr(), scratch.numel(),
+                                              nv.stream_ptr()), "lip_sub_predict")
+            if part is not out:
+                out[:, k0:k1] = part
+        return out
+
     # ------------------------------------------------------------------------------ measurement
     def profile(self, enable: bool):
         nv.check(self.lib.lip_engine_profile(self.h, int(enable)), "lip_engine_profile")

@@ -139,18 +139,23 @@ def auroc_ood(state, id_probs: torch.Tensor, ood_loader: Iterable, Z, alpha, ful
 
 
 def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, model_type="classifier",
-                        posterior: str = "diag"):
+                        posterior: str = "diag", indices=None):
     """:func:`eval_dataset_extended` without draws: the class probabilities are the probit predictive
     (``lla.probit_predictive``) of the closed-form output variances — ``posterior="diag"``: the diagonal Laplace
     posterior (``lla.predict_lla_diag``), ``"inducing"``: the inducing-point posterior (``lla.predict_lla_variances``),
     ``"last_layer"``: the dense last-layer posterior (``lla.predict_lla_last_layer``, fitted once for all batches),
-    ``"last_layer_kron"``: its Kronecker-factored twin without the size cap (``lla.predict_lla_last_layer_kron``).
+    ``"last_layer_kron"``: its Kronecker-factored twin without the size cap (``lla.predict_lla_last_layer_kron``),
+    ``"subnetwork"``: the dense posterior over the flat-parameter indices ``indices`` (``lla.predict_lla_subnetwork``,
+    fitted once for all batches; ``indices`` is read by this value alone).
     -> (NLL, accuracy, Brier, ECE, probs, labels)"""
-    from .lla import (predict_lla_diag, predict_lla_last_layer, predict_lla_last_layer_kron, predict_lla_variances,
-                      probit_predictive)
+    from .lla import (predict_lla_diag, predict_lla_last_layer, predict_lla_last_layer_kron, predict_lla_subnetwork,
+                      predict_lla_variances, probit_predictive)
+    if posterior == "subnetwork" and indices is None:
+        raise ValueError("posterior='subnetwork' needs indices")
     predict = {"diag": predict_lla_diag, "inducing": predict_lla_variances,
                "last_layer": lambda *a, **kw: predict_lla_last_layer(*a, cov="diag", **kw),
-               "last_layer_kron": lambda *a, **kw: predict_lla_last_layer_kron(*a, cov="diag", **kw)}[posterior]
+               "last_layer_kron": lambda *a, **kw: predict_lla_last_layer_kron(*a, cov="diag", **kw),
+               "subnetwork": lambda *a, **kw: predict_lla_subnetwork(*a, indices, cov="diag", **kw)}[posterior]
     all_probs, all_labels = [], []
     for x_b, y_b in dataloader:
         probs = probit_predictive(*predict(state, x_b, Z, model_type, alpha, full_set_size=full_set_size))

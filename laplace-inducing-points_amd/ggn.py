@@ -270,6 +270,20 @@ def compute_kron_factors_last_layer(state, Z, model_type, example_chunk: Optiona
     return last_layer_kron.compute_kron_factors_last_layer(state, Z, model_type, example_chunk=example_chunk)
 
 
+def compute_ggn_subnetwork(state, Z, model_type, indices, full_set_size=None, example_chunk: Optional[int] = None) -> torch.Tensor:
+    """The dense GGN block over the flat-parameter indices ``indices``, (S, S) float64, scaled like
+    :func:`compute_ggn_vp` and chunked like :func:`compute_ggn_diag` (:func:`subnetwork.compute_ggn_subnetwork`)."""
+    from . import subnetwork
+    return subnetwork.compute_ggn_subnetwork(state, Z, model_type, indices, full_set_size=full_set_size,
+                                             example_chunk=example_chunk)
+
+
+def subnetwork_indices(state, select, size=None, **kw) -> torch.Tensor:
+    """The sorted index set of a subnetwork posterior (:func:`subnetwork.subnetwork_indices`)."""
+    from . import subnetwork
+    return subnetwork.subnetwork_indices(state, select, size, **kw)
+
+
 FACTOR_BYTES_LIMIT = 64 << 30
 
 

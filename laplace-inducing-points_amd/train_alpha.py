@@ -151,6 +151,27 @@ def fit_alpha_last_layer_kron(X, state, model_type, full_set_size=None, alpha0: 
     return _fit_from_spectrum(lam, DL, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
+def log_marginal_likelihood_subnetwork(alpha, X, state, model_type: str, indices, full_set_size: Optional[int] = None) -> float:
+    """:func:`log_marginal_likelihood` of the subnetwork model (every parameter outside ``indices`` frozen): the spectrum
+    is that of the dense subnetwork GGN (``subnetwork.compute_ggn_subnetwork`` at N/M = 1), D = |S| and
+    ||theta||^2 = ||theta_S||^2.  No null-space projection is applied (an arbitrary index set has no known one), so on a
+    classifier whose set holds the whole final layer the float32 softmax leak that
+    ``last_layer._spectrum_last_layer`` removes stays in.  Scalar alpha.  Not a reference function."""
+    from .subnetwork import _spectrum_subnetwork
+    N = full_set_size or X.shape[0]
+    lam, DS, theta2 = _spectrum_subnetwork(X, state, model_type, indices)
+    return _lml_from_spectrum(float(alpha), lam, DS, theta2, N / X.shape[0])[0]
+
+
+def fit_alpha_subnetwork(X, state, model_type, indices, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2,
+                         steps: int = 200):
+    """:func:`fit_alpha` on the subnetwork evidence: ``(alpha, history)``; the spectrum is computed once."""
+    from .subnetwork import _spectrum_subnetwork
+    N = full_set_size or X.shape[0]
+    lam, DS, theta2 = _spectrum_subnetwork(X, state, model_type, indices)
+    return _fit_from_spectrum(lam, DS, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
+
+
 # ---- layer-wise precisions ------------------------------------------------------------------------------------------
 def grouped_spectrum(X, state, model_type, prior: GroupedPrior):
     """``(grams (G, d, d) float64, sizes (G,), theta_sqnorms (G,) float64)`` of the factor built at N/M = 1 like
