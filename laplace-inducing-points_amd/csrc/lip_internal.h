@@ -333,6 +333,13 @@ struct Switches {
   bool dot_nt_noquad;  // LIP_DOT_NT_NOQUAD: lip_dot_nt_f64 with one tile per block, the waves splitting K
 };
 const Switches& switches();
+// LIP_WGW_NOSTAGE: wgrad_wino/rowq fetches the cotangent per wave, without the block's LDS stage.  It picks an
+// instantiation, not a route (the name stays wgrad_wino/rowq), so it is read here, as lip_bindcache.h reads its policy;
+// its A/B test is tests/test_wgrad_wino_stage.py, which starts one child process per setting.
+inline bool wgw_nostage() {
+  static const bool off = getenv("LIP_WGW_NOSTAGE") != nullptr;
+  return off;
+}
 
 // ---- one record per (device, stream) ---------------------------------------------------------------
 // with(st, f) finds or creates the record of (current device, st) and returns f(record), run under the table's lock.

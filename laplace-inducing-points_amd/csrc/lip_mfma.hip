@@ -2380,7 +2380,8 @@ static hipError_t run_wgrad_first(const WgradP& p0, int P, hipStream_t st) {
 //     launch as Vt[xi][t/4][c][4], so lane (c, half h) reads four consecutive tiles of its channel as ONE dwordx4 (512
 //     contiguous bytes per half-wave) — the A registers of 4 k-steps (k-step j multiplies tile 8m + 4h + j);
 //   * Gh = A g A^T of the probe's cotangent is formed on the fly: lane (n, h) loads the 2 x 2 pixels of its tile (dwords,
-//     128 contiguous bytes per half-wave), 2 + 3 VALU operations -> the B registers of its wave's four positions;
+//     128 contiguous bytes per half-wave; on maps with TW % 4 == 0 from the block's LDS stage instead, see STAGE below),
+//     2 + 3 VALU operations -> the B registers of its wave's four positions;
 //   * wave a owns row a of the 4x4 position grid (64 accumulator registers); dW = G^T dU G in-wave over b, across the
 //     waves over a through LDS; the fused output y = s acc + alpha v when one block reduces all tiles, float atomics
 //     into the initialised block when the tiles are split over blocks (few (c, n) tiles per probe: the 32-channel stage).
@@ -2430,9 +2431,17 @@ __global__ __launch_bounds__(256) void wino_input_transform_kernel(const float* 
     *reinterpret_cast<f32x4v*>(&vt[(((long long)xi * TQ + tq) * C + c) * 4]) = f32x4v{v[xi][0], v[xi][1], v[xi][2], v[xi][3]};
 }
 
-template <bool ROWQ>
+// STAGE (ROWQ launches only; LIP_WGW_NOSTAGE picks the instantiation without it): the cotangent goes global -> registers
+// -> LDS -> B registers, fetched ONCE per block instead of once per wave.  A stage is two groups = 8 units (group, half h,
+// pixel row r) of 8 pixels x 32 channels, one run of 1 KB in g (the four tiles of a half share a tile row); wave a takes
+// the units of (group a >> 1, half a & 1): lane (pixel, channel quad) one dwordx4 per r, one ds_write_b128 into
+// [group][h][r][pixel][32]; lane (n, h) reads its 16 values back as dwords (32 consecutive floats per half-wave).  Two
+// buffers at the start of the exchange area, one barrier per stage: a buffer is rewritten after the barrier that
+// follows its last reader.  Operands and MFMA order are those of the loop without staging: bitwise the same sums.
+template <bool ROWQ, bool STAGE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_wino_kernel(const WgWinoP prm) {
-  extern __shared__ __attribute__((aligned(16))) float wgw_lds[];          // [4 a][3 kw][16 reg][64 lane]
+  static_assert(ROWQ || !STAGE, "a staged unit is one run of pixels: the four tiles of a half must share a tile row");
+  extern __shared__ __attribute__((aligned(16))) float wgw_lds[];          // [4 a][3 kw][16 reg][64 lane]; STAGE: first [2][2 group][2 h][2 r][8 pixel][32]
   const int tid = threadIdx.x, lane = tid & 63;
   const int a = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, h = lane >> 5;
@@ -2460,10 +2469,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
   const int m0 = z * prm.gps, m1 = m0 + prm.gps;
   f32x4v areg[2][4];
   float graw[2][4][4];                 // [buffer][tile j][r * 2 + q]
-  auto load_group = [&](int m, f32x4v (&ar)[4], float (&gr)[4][4]) __attribute__((always_inline)) {
+  auto load_vt = [&](int m, f32x4v (&ar)[4]) __attribute__((always_inline)) {
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       ar[q] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(vrs, avoff, (4 * a + q) * a_xi + (unsigned)(2 * m) * C * 16, 0));
+  };
+  auto load_group = [&](int m, f32x4v (&ar)[4], float (&gr)[4][4]) __attribute__((always_inline)) {
+    load_vt(m, ar);
     const int t = 8 * m + 4 * h;
     if (ROWQ) {                                       // TW % 4 == 0: the lane's four tiles share a tile row
       const int img = prm.dTPI.div(t), rem = t - img * prm.tpi, ty = prm.dTW.div(rem), tx = rem - ty * prm.TW;
@@ -2499,15 +2511,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void w
     }
   };
   // (gps is even: two groups per iteration, the last iteration re-requests the final group instead of branching)
-  load_group(m0, areg[0], graw[0]);
-  for (int m = m0; m < m1; m += 2) {
-    load_group(m + 1, areg[1], graw[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(areg[0], graw[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    load_group(m + 2 < m1 ? m + 2 : m1 - 1, areg[0], graw[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(areg[1], graw[1]);
+  if constexpr (STAGE) {
+    const int px = lane >> 3, cq = lane & 7;
+    const int sg = a >> 1, sh = a & 1;                                   // this wave's units: (group sg, half sh, r = 0, 1)
+    const unsigned swr = (unsigned)((4 * sg + 2 * sh) * 256 + px * 32 + cq * 4);      // floats into a buffer, r = 0
+    const unsigned srd = (unsigned)(h * 512 + l31);
+    f32x4v gst[2];
+    auto stage_load = [&](int m) __attribute__((always_inline)) {        // the stage of groups m, m + 1 -> registers
+      const int t = 8 * (m + sg) + 4 * sh;
+      const int img = prm.dTPI.div(t), rem = t - img * prm.tpi, ty = prm.dTW.div(rem), tx = rem - ty * prm.TW;
+      const unsigned gv = t < prm.T ? (unsigned)((((img * H + 2 * ty) * W + 2 * tx + px) * N + nt * 32 + cq * 4) * 4) : 0x80000000u;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) gst[r] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(grs, gv, r * row_bytes, 0));
+    };
+    auto stage_write = [&](int b) __attribute__((always_inline)) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) *reinterpret_cast<f32x4v*>(&wgw_lds[b * 2048 + swr + r * 256]) = gst[r];
+    };
+    auto stage_read = [&](int b, int g, float (&gr)[4][4]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+          for (int q = 0; q < 2; ++q) gr[j][2 * r + q] = wgw_lds[b * 2048 + g * 1024 + srd + r * 256 + (2 * j + q) * 32];
+    };
+    // stage s is read from buffer s & 1 while stage s + 1 is written to the other and stage s + 2 is in flight; the last
+    // iterations re-request the final stage (never consumed) instead of branching
+    stage_load(m0);
+    stage_write(0);
+    stage_load(m0 + 2 < m1 ? m0 + 2 : m1 - 2);       // (then Vt, as in the loop: one count of loads in flight at its stage_write)
+    load_vt(m0, areg[0]);
+    __syncthreads();
+    stage_read(0, 0, graw[0]);
+    int b = 0;
+    for (int m = m0; m < m1; m += 2, b ^= 1) {
+      load_vt(m + 1, areg[1]);
+      stage_read(b, 1, graw[1]);
+      stage_write(b ^ 1);              // last read before the previous iteration's barrier
+      stage_load(m + 4 < m1 ? m + 4 : m1 - 2);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(areg[0], graw[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      load_vt(m + 2 < m1 ? m + 2 : m1 - 1, areg[0]);
+      __syncthreads();
+      stage_read(b ^ 1, 0, graw[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(areg[1], graw[1]);
+    }
+    __syncthreads();                   // the exchange area below overlays the buffers
+  } else {
+    load_group(m0, areg[0], graw[0]);
+    for (int m = m0; m < m1; m += 2) {
+      load_group(m + 1, areg[1], graw[1]);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(areg[0], graw[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      load_group(m + 2 < m1 ? m + 2 : m1 - 1, areg[0], graw[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(areg[1], graw[1]);
+    }
   }
 
   // dW = G^T dU G: over b in the wave (X[kw]), over a across the waves
@@ -2615,15 +2678,19 @@ static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st, BindCac
   const size_t shmem = 12 * 1024 * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad_wino_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wgrad_wino_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    hipError_t e = hipFuncSetAttribute((const void*)wgrad_wino_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wgrad_wino_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wgrad_wino_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
   const dim3 grid((unsigned)((p.C / 32) * (p.N / 32) * S), (unsigned)P);
-  with_flag((TW & 3) == 0, [&](auto rowq) {
-    LIP_ROUTE("wgrad_wino%s", rowq ? "/rowq" : ""); hipLaunchKernelGGL(wgrad_wino_kernel<rowq>, grid, dim3(256), shmem, st, q);
-  });
+  with_flag((TW & 3) == 0, [&](auto rq) { with_flag(decltype(rq)::value && !wgw_nostage(), [&](auto stage) {
+    constexpr bool rowq = decltype(rq)::value;
+    if constexpr (rowq || !stage) {
+      LIP_ROUTE("wgrad_wino%s", rowq ? "/rowq" : ""); hipLaunchKernelGGL((wgrad_wino_kernel<rowq, stage>), grid, dim3(256), shmem, st, q);
+    }
+  }); });
   return hipGetLastError();
 }
 
