@@ -348,6 +348,54 @@ int lip_sub_gram(const float* W, int64_t ldw, int64_t D, int32_t R, const int64_
 int lip_sub_predict_scratch(int32_t B, int32_t K, int32_t S, int64_t* doubles);
 int lip_sub_predict(const float* Jr, int64_t ldj, int64_t D, int32_t B, int32_t K, const int64_t* idx, int32_t S,
                     const double* Sigma, double* out, int32_t diag, double* scratch, int64_t scratch_doubles, void* stream);
+
+/* ---- Kronecker-factored curvature of every layer (KFAC / KFC; not reference functions) ------------------------
+ * A layer block is the flat slice [bias (N)] + kernel (M x N row-major), M = KH KW C in (kh, kw, ci) order, read as an
+ * (Mt, N) matrix with the bias as row 0 when there is one (Mt = M + 1).  Its curvature is approximated by
+ * (recal / (n T)) A (x) S with the two float64 Grams below, T = OH OW.
+ *
+ * Input factor of one layer, ADDED into A (Mt, Mt) float64 row-major:
+ *   A += sum_{i < n} sum_{t < OH OW} at_{i,t} at_{i,t}^T
+ * X is the layer's float32 NHWC input (n, IH, IW, C); at_{i,t} the im2col patch of image i at output position t, zero
+ * outside the image (the high-side padding of SAME included), with a leading 1 when bias != 0.  Lower-triangle 32 x 32
+ * tiles x row ranges write partial tiles to scratch (>= lip_kfac_input_gram_scratch doubles), added in index order: no
+ * atomics, bitwise reproducible, exactly symmetric; chunks of images add up.  The gather clamps its address and selects
+ * zero: nothing outside X is read.  A null pointer, a non-positive extent, too small a scratch, or 2^31 or more input
+ * elements or Gram rows returns LIP_ERR_ARG and leaves A untouched. */
+int lip_kfac_input_gram_scratch(int32_t n, int32_t IH, int32_t IW, int32_t C, int32_t KH, int32_t KW, int32_t stride,
+                                int32_t pad_h, int32_t pad_w, int32_t OH, int32_t OW, int32_t bias, int64_t* doubles);
+int lip_kfac_input_gram(const float* X, int32_t n, int32_t IH, int32_t IW, int32_t C, int32_t KH, int32_t KW, int32_t stride,
+                        int32_t pad_h, int32_t pad_w, int32_t OH, int32_t OW, int32_t bias, double* A, double* scratch,
+                        int64_t scratch_doubles, void* stream);
+/* Output factors of every layer from one backward sweep, ADDED into S: the sweep of lip_vjp_sqsum (same U, head modes
+ * and c) in which every WGRAD op, instead of a weight gradient, Gram-multiplies the (P n OH OW, N) float32 rows g of its
+ * cotangent operand, S_l += sum g g^T, and no bias / BN reduction is launched.  S holds the (N_l, N_l) float64 blocks of
+ * the WGRAD ops in tape order; lip_vjp_kron_layout gives, per op, the flat offset of its kernel in theta, the offset of
+ * its block in S and N_l (up to `cap` entries; *count the number of ops, *total the doubles of S).  The cotangent is
+ * that of the layer's output after BN: the caller applies the frozen BN scale s s^T o S_l.  Probe passes add in order:
+ * bitwise reproducible for a given chunking.  scratch holds >= lip_vjp_kron_scratch(e, P) doubles for the P of the call
+ * (the largest need over every pass size the call can run; it is not monotone in P).  Every Gram of every pass is
+ * checked before the first launch.  Status codes as
+ * lip_vjp_sqsum; S is untouched on LIP_ERR_ARG / LIP_ERR_STATE. */
+int lip_vjp_kron_scratch(lip_engine_t* e, int32_t P, int64_t* doubles);
+int lip_vjp_kron_layout(lip_engine_t* e, int32_t cap, int64_t* kernel_off, int64_t* out_off, int32_t* N, int32_t* count,
+                        int64_t* total);
+int lip_vjp_kron(lip_engine_t* e, const float* U, double* S, int32_t P, int32_t head_mode, float c, double* scratch,
+                 int64_t scratch_doubles, void* stream);
+/* Closed-form predictive of one layer block under the factored posterior, float64, ADDED into out.  Jr (Kc B, ldj)
+ * float32, row k B + b the Jacobian row of output k at test point b (lip_vjp_rows, LIP_HEAD_IN); the block is the
+ * (Mt, N) matrix at flat offset off of a row, ldj >= off + Mt N; V (Mt, Mt), Ub (N, N), R (Mt, N) the fitted factors
+ * (covariance sum_{j,l} V[f][j] V[g][j] Ub[k][l] Ub[m][l] R[j][l]).  With T_r = V^T J_r Ub,
+ *   diag == 0: out (B, Kc, Kc), out[b][k][m] += sum_{j,l} R[j][l] T_{(k,b)}[j][l] T_{(m,b)}[j][l], computed for k <= m
+ *              and mirrored (a symmetric out stays exactly symmetric);
+ *   diag != 0: out (B, Kc), the k == m entries only, bitwise those of the full form.
+ * J Ub and T live in scratch; lip_kfac_predict_scratch gives the doubles for all B points at once, a smaller scratch
+ * (at least 2 Kc Mt N doubles, one point) makes the call run in chunks of points.  A null pointer, a non-positive
+ * extent, ldj < off + Mt N, Mt N >= 2^31 or a scratch below one point returns LIP_ERR_ARG and leaves out untouched. */
+int lip_kfac_predict_scratch(int32_t B, int32_t Kc, int32_t Mt, int32_t N, int64_t* doubles);
+int lip_kfac_predict(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_t off, int32_t Mt, int32_t N, const double* V,
+                     const double* Ub, const double* R, double* out, int32_t diag, double* scratch, int64_t scratch_doubles,
+                     void* stream);
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);

@@ -111,6 +111,15 @@ SIGNATURES = {
     "lip_sub_predict_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "lip_sub_predict": (C.c_int, [_V, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _V, C.c_int32, _V, _V, C.c_int32, _V,
                                   C.c_int64, _V]),
+    "lip_kfac_input_gram_scratch": (C.c_int, [C.c_int32] * 12 + [C.POINTER(C.c_int64)]),
+    "lip_kfac_input_gram": (C.c_int, [_V] + [C.c_int32] * 12 + [_V, _V, C.c_int64, _V]),
+    "lip_vjp_kron_scratch": (C.c_int, [_V, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_vjp_kron_layout": (C.c_int, [_V, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "lip_vjp_kron": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_float, _V, C.c_int64, _V]),
+    "lip_kfac_predict_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_kfac_predict": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V,
+                                   C.c_int32, _V, C.c_int64, _V]),
     "lip_fill_rademacher": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_fill_normal": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
 }

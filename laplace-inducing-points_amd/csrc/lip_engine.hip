@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <vector>
 #include "lip_internal.h"
+#include "lip_gramtile.h"
 
 namespace lip {
 
@@ -46,6 +47,10 @@ struct lip_engine {
   // Winograd transforms of the binding's shared kernels and primal activations (lip_bindcache.h): filled lazily by the
   // sweeps' launches, stale after a primal pass, freed on re-binding and destruction; null with LIP_NOBINDCACHE
   BindCache* cache = new_bind_cache();
+  // lip_vjp_kron: doubles before the (N, N) block of backward op i in its output (WGRAD ops, in tape order), and the
+  // total; filled when the backward tape is set
+  std::vector<int64_t> kron_off;
+  int64_t kron_total = 0;
   ~lip_engine() { delete cache; }
 };
 
@@ -58,6 +63,8 @@ enum class Sweep {
   SQSUM,    // lip_vjp_sqsum: formed per (probe, example) as in ROWS, squared and summed into ONE (D,) vector Y
   WNORM,    // lip_vjp_wnorm: formed per (probe, example); Y is the (D,) WEIGHT vector, read only, and the weighted square
             // norm of every cotangent is added to wout[p * n + i]
+  KRON,     // lip_vjp_kron: no parameter cotangent is formed; every WGRAD op Gram-multiplies the rows of its cotangent
+            // operand into its (N, N) float64 block of kron (the output factors of a Kronecker-factored curvature)
 };
 
 struct RunCtx {
@@ -74,6 +81,9 @@ struct RunCtx {
   long long scratch_floats = 0;
   bool wones = false;             // WNORM: every weight is 1 and Y is a placeholder of the right extent that is never read
   float* wout = nullptr;
+  double* kron = nullptr;         // KRON: the (N, N) block of the op being run (run_tape shifts the output buffer per op)
+  double* kron_scratch = nullptr; // ... and the partial tiles of one Gram
+  long long kron_doubles = 0;
   // summed products (lip_ggn_vp / lip_vjp): a weight gradient that reduces all rows in one block may WRITE
   // y = s acc + alpha v instead of adding to an initialised block (the initialisation then skips its parameters)
   bool fuse = false;
@@ -92,6 +102,11 @@ inline RunCtx square_sum(RunCtx c, float* scratch, long long floats) {
 }
 inline RunCtx weighted_norm(RunCtx c, float* scratch, long long floats, bool wones, float* wout) {
   c.mode = Sweep::WNORM; c.scratch = scratch; c.scratch_floats = floats; c.wones = wones; c.wout = wout;
+  return c;
+}
+
+inline RunCtx kron_factors(RunCtx c, double* out, double* scratch, long long doubles) {
+  c.mode = Sweep::KRON; c.kron = out; c.kron_scratch = scratch; c.kron_doubles = doubles;
   return c;
 }
 
@@ -157,6 +172,7 @@ int reduce_params(const RunCtx& c, const ReduceP& r, int n_img, const char* who)
 // without them and takes them by a segmented reduce over the op's freshly written output [P][n][rows][N] instead.
 template <class Prm, class Launch>
 int launch_with_reductions(const RunCtx& c, Prm& p, Launch launch, const char* who, int n_img, int rows, int N, const float* xhat) {
+  if (c.mode == Sweep::KRON) { p.red0 = nullptr; p.red1 = nullptr; }      // no parameter cotangent is formed
   if (!c.per_example() || (!p.red0 && !p.red1)) { RUN_CHECK(launch(p), who); return LIP_OK; }
   ReduceP r;
   memset(&r, 0, sizeof(r));
@@ -204,6 +220,40 @@ int make_wgrad(const RunCtx& c, const lip_op_t& op, WgradP& p) {
     p.overwrite = 1;
     p.v = c.V ? c.V + op.out.off : nullptr; p.v_ps = op.out.pstride; p.alpha = c.alpha;
   }
+  return LIP_OK;
+}
+
+// Gram rows of a WGRAD op's cotangent operand on a pass of pc probes, and the launches they take: one over all probes
+// when the probes are adjacent (the per-probe stride is the row block), else one per probe
+long long kron_rows(const lip_op_t& op, int pc, int* launches) {
+  const long long Rp = (long long)op.n_img * op.OH * op.OW;
+  const bool packed = pc == 1 || op.seg[0].b.pstride == Rp * op.N;
+  if (launches) *launches = packed ? 1 : pc;
+  return packed ? Rp * pc : Rp;
+}
+
+// can the Gram of a WGRAD op's cotangent rows run on a pass of pc probes?
+bool kron_op_fits(const lip_op_t& op, int pc) {
+  const long long R = kron_rows(op, pc, nullptr);
+  return R > 0 && R < (1ll << 31) && op.N > 0 && panel_gram_fits((int)R, op.N);
+}
+
+// KRON: S_l += sum over the (probe, example, position) rows g of the op's cotangent operand of g g^T (the panel Gram of
+// lip_subnetwork.hip on the (rows, N) float32 block in place)
+int kron_wgrad(const RunCtx& c, const lip_op_t& op) {
+  const lip_ref_t& b = op.seg[0].b;
+  const float* rows = resolve(c, b);
+  int launches = 1;
+  const long long R = kron_rows(op, c.P, &launches);
+  if (!rows || !c.kron || !c.kron_scratch || R <= 0 || op.N <= 0) { set_error("WGRAD (kron): bad operands"); return LIP_ERR_ARG; }
+  if (!kron_op_fits(op, c.P)) {       // lip_vjp_kron has checked every op before its first launch
+    set_error("WGRAD (kron): 2^31 or more cotangent rows on a pass; bind fewer examples per engine");
+    return LIP_ERR_ARG;
+  }
+  if (panel_gram_scratch((int)R, op.N) > c.kron_doubles) { set_error("WGRAD (kron): scratch too small"); return LIP_ERR_ARG; }
+  double* S = c.kron;
+  for (int l = 0; l < launches; ++l)
+    RUN_CHECK(launch_panel_gram(rows + (int64_t)l * b.pstride, (int)R, op.N, S, c.kron_scratch, c.st), "kron gram launch");
   return LIP_OK;
 }
 
@@ -259,6 +309,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
                                     op.n_img, p.OHW, p.N, p.xhat2);
     }
     case LIP_OP_WGRAD: {
+      if (c.mode == Sweep::KRON) return kron_wgrad(c, op);
       WgradP p;
       const int rc = make_wgrad(c, op, p);
       if (rc) return rc;
@@ -273,6 +324,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       return LIP_OK;
     }
     case LIP_OP_REDUCE: {
+      if (c.mode == Sweep::KRON) return LIP_OK;
       ReduceP p;
       memset(&p, 0, sizeof(p));
       p.g = resolve(c, op.seg[0].a); p.g_ps = op.seg[0].a.pstride;
@@ -383,7 +435,14 @@ int run_tape(const RunCtx& c, int which, bool skip_head) {
       e0 = next_event(c.e); e1 = next_event(c.e);
       if (e0 && e1) { c.e->ev_kind.push_back(t[i].kind); (void)hipEventRecord(e0, c.st); }
     }
-    const int rc = run_op(c, t[i]);
+    int rc;
+    if (c.mode == Sweep::KRON && t[i].kind == LIP_OP_WGRAD) {
+      RunCtx ck = c;                                   // this op's block of the output buffer
+      ck.kron = c.kron + c.e->kron_off[i];
+      rc = run_op(ck, t[i]);
+    } else {
+      rc = run_op(c, t[i]);
+    }
     if (c.e->prof && e0 && e1) (void)hipEventRecord(e1, c.st);
     if (rc != LIP_OK) {
       char buf[400];
@@ -472,15 +531,22 @@ int ggn_sweep(const lip_engine* e, const float* V, float* Y, int P, float scale,
   });
 }
 
-// Scratch floats of a lip_vjp_sqsum / lip_vjp_wnorm call of P probes: the largest need of one backward op on one pass
-// (ops run in stream order and reuse it).  Depends on the tape geometry and the probes per pass only.
+// Scratch floats of a lip_vjp_sqsum / lip_vjp_wnorm call of P probes (doubles of a lip_vjp_kron call): the largest need
+// of one backward op on one pass (ops run in stream order and reuse it).  Depends on the tape geometry and the probes
+// per pass only.
 int64_t sweep_scratch(const lip_engine* e, Sweep mode, int P) {
   const int pc = e->max_chunk > 0 ? balanced_chunk(P, e->max_chunk) : P;
   int64_t need = 0;
   for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
     const long long pairs = (long long)pc * op.n_img;
     int64_t k = 0;
-    if (op.kind == LIP_OP_WGRAD)
+    if (mode == Sweep::KRON) {
+      // The last pass may be shorter, and the partial tiles of a Gram are not monotone in its rows (ll_split trades
+      // ranges for rows per range): the largest need over every pass size up to pc
+      if (op.kind == LIP_OP_WGRAD)
+        for (int q = 1; q <= pc; ++q)
+          if (kron_op_fits(op, q)) k = std::max<int64_t>(k, panel_gram_scratch((int)kron_rows(op, q, nullptr), op.N));
+    } else if (op.kind == LIP_OP_WGRAD)
       k = wgrad_scratch(mode, op.seg[0].KH * op.seg[0].KW * op.seg[0].C, op.N, op.OH * op.OW, pairs);
     else if ((op.kind == LIP_OP_IGEMM || op.kind == LIP_OP_REDUCE || op.kind == LIP_OP_POOL_BWD || op.kind == LIP_OP_MAXPOOL_BWD) &&
              (op.red0.space != LIP_SP_NONE || op.red1.space != LIP_SP_NONE))
@@ -499,10 +565,11 @@ int scratch_query(const lip_engine* e, const char* who, Sweep mode, int P, int64
 }
 
 // ... and the refusal of a call whose scratch is smaller than the query says
-int scratch_fits(const lip_engine* e, const char* who, Sweep mode, int P, const float* scratch, int64_t scratch_floats) {
+int scratch_fits(const lip_engine* e, const char* who, Sweep mode, int P, const void* scratch, int64_t scratch_floats) {
   const int64_t need = sweep_scratch(e, mode, P);
   if (scratch_floats >= need && (need == 0 || scratch)) return LIP_OK;
-  set_error("%s: scratch of %lld floats, %lld needed (%s_scratch)", who, (long long)scratch_floats, (long long)need, who);
+  set_error("%s: scratch of %lld %s, %lld needed (%s_scratch)", who, (long long)scratch_floats,
+            mode == Sweep::KRON ? "doubles" : "floats", (long long)need, who);
   return LIP_ERR_ARG;
 }
 
@@ -536,6 +603,14 @@ int lip_engine_destroy(lip_engine_t* e) {
 int lip_engine_set_tape(lip_engine_t* e, int32_t which, const lip_op_t* ops, int32_t nops) {
   if (!e || which < 0 || which > 2 || !ops || nops <= 0) { set_error("lip_engine_set_tape: bad argument"); return LIP_ERR_ARG; }
   e->tape[which].assign(ops, ops + nops);
+  if (which == LIP_TAPE_BACKWARD) {
+    e->kron_off.assign(nops, 0);
+    e->kron_total = 0;
+    for (int i = 0; i < nops; ++i) {
+      e->kron_off[i] = e->kron_total;
+      if (ops[i].kind == LIP_OP_WGRAD) e->kron_total += (int64_t)ops[i].N * ops[i].N;
+    }
+  }
   if (which == LIP_TAPE_PRIMAL) e->primal_done = false;
   return LIP_OK;
 }
@@ -687,6 +762,43 @@ int lip_vjp_wnorm(lip_engine_t* e, const float* U, const float* w, float* out, i
     // (w == NULL: theta stands in for the weight vector — a (D,) device block whose slices are addressed, never read)
     const RunCtx c{e, nullptr, const_cast<float*>(w ? w : e->theta), head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
     return run_tape(weighted_norm(c, scratch, scratch_floats, w == nullptr, out + (int64_t)c0 * e->n_img), LIP_TAPE_BACKWARD, false);
+  });
+}
+
+int lip_vjp_kron_scratch(lip_engine_t* e, int32_t P, int64_t* doubles) {
+  return scratch_query(e, "lip_vjp_kron_scratch", Sweep::KRON, P, doubles);
+}
+
+int lip_vjp_kron_layout(lip_engine_t* e, int32_t cap, int64_t* kernel_off, int64_t* out_off, int32_t* N, int32_t* count,
+                        int64_t* total) {
+  if (!e || cap < 0 || !count || !total || (cap > 0 && (!kernel_off || !out_off || !N))) { set_error("lip_vjp_kron_layout: bad argument"); return LIP_ERR_ARG; }
+  if (e->tape[LIP_TAPE_BACKWARD].empty()) { set_error("lip_vjp_kron_layout: backward tape missing"); return LIP_ERR_STATE; }
+  int32_t k = 0;
+  const std::vector<lip_op_t>& t = e->tape[LIP_TAPE_BACKWARD];
+  for (size_t i = 0; i < t.size(); ++i) {
+    if (t[i].kind != LIP_OP_WGRAD) continue;
+    if (k < cap) { kernel_off[k] = t[i].out.off; out_off[k] = e->kron_off[i]; N[k] = t[i].N; }
+    ++k;
+  }
+  *count = k;
+  *total = e->kron_total;
+  return LIP_OK;
+}
+
+int lip_vjp_kron(lip_engine_t* e, const float* U, double* S, int32_t P, int32_t head_mode, float cc, double* scratch,
+                 int64_t scratch_doubles, void* stream) {
+  int rc = ready_vjp(e, "lip_vjp_kron", U, S, P, head_mode, scratch_doubles >= 0);
+  if (rc || (rc = scratch_fits(e, "lip_vjp_kron", Sweep::KRON, P, scratch, scratch_doubles))) return rc;
+  // every Gram of every pass is checked before the first launch, so that a refusal leaves S untouched
+  const int step = balanced_chunk(P, e->max_chunk), last = P - (P - 1) / step * step;
+  for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD])
+    if (op.kind == LIP_OP_WGRAD && !(kron_op_fits(op, step) && kron_op_fits(op, last))) {
+      set_error("lip_vjp_kron: 2^31 or more cotangent rows on a pass; bind fewer examples per engine");
+      return LIP_ERR_ARG;
+    }
+  return for_each_pass(e, P, [&](int c0, int pc) {
+    const RunCtx c{e, nullptr, nullptr, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    return run_tape(kron_factors(c, S, scratch, scratch_doubles), LIP_TAPE_BACKWARD, false);
   });
 }
 

@@ -90,6 +90,15 @@ __device__ __forceinline__ void ll_tri_tile(int tile, int& tr, int& tc) {
   tc = tile - tr * (tr + 1) / 2;
 }
 
+// The Gram of a compact float32 (R, S) panel's columns (lip_subnetwork.hip: sub_gram_kernel, then sub_assemble_kernel),
+// for the translation units that Gram-multiply panels of their own: G (S, S) += panel^T panel through `part`
+// (>= panel_gram_scratch(R, S) doubles), and the assemble step alone for partial tiles a caller's own kernel wrote with
+// ll_gram_tile (ys ranges of `tiles` lower-triangle tiles each, added in index order, both triangles from the same sums).
+bool panel_gram_fits(int R, int S);
+long long panel_gram_scratch(int R, int S);
+hipError_t launch_panel_gram(const float* panel, int R, int S, double* G, double* part, hipStream_t st);
+hipError_t launch_gram_assemble(const double* part, long long tiles, int ys, int S, double* G, hipStream_t st);
+
 }  // namespace lip
 
 #endif  // LIP_GRAMTILE_H

@@ -1,0 +1,360 @@
+// Kronecker-factored Laplace over every layer (KFAC; KFC for convolutions): the input factor of one layer
+// (lip_kfac_input_gram) and the closed-form predictive of one layer block (lip_kfac_predict).  The output factors come
+// from the KRON sweep of lip_engine.hip (lip_vjp_kron).  Everything after the float32 loads in float64.
+//
+//   A[e][f]       += sum_{i < n} sum_{t < OH OW} at_{i,t}[e] at_{i,t}[f]
+//   out[b][k][m]  += sum_{j,l} R[j][l] T_{(k,b)}[j][l] T_{(m,b)}[j][l],   T_r = V^T J_r Ub
+//
+// at_{i,t} is the im2col patch of image i at output position t in (kh, kw, ci) order, zero outside the image, with a
+// leading 1 when the layer has a bias; J_r is the (Mt, N) block at flat offset `off` of Jacobian row r.
+//
+// Input Gram: ll_gram_tile (lip_gramtile.h) with an operand functor that gathers patch elements, over the lower triangle
+// of 32 x 32 tiles x ranges of Gram rows (image, oh, ow); partial tiles go to scratch and the assemble step of
+// lip_subnetwork.hip adds the ranges in index order, both triangles from the same sums: no atomics, bitwise
+// reproducible, exactly symmetric.  The gather clamps the address and selects zero: it never reads outside the tensor.
+//
+// Predict: W = J Ub and T = V^T W on v_mfma_f64_16x16x4_f64 (the tile code of sub_tsigma_kernel), both in the caller's
+// scratch, for chunks of test points that fit it; then one block per output entry walks R o T_k o T_m.  The diag form
+// runs the k == m entries through the same function, so it equals the diagonal of the full form bitwise.
+#include <algorithm>
+#include "lip_internal.h"
+#include "lip_gramtile.h"
+
+namespace lip {
+
+struct KfacGeom {
+  int IH, IW, C, KH, KW, stride, pad_h, pad_w, OH, OW, bias, Mt;
+};
+
+// The operand pair of one lane of the patch Gram: Gram row i = (image, oh, ow), column = patch element
+struct KfacPatchOperands {
+  const float* __restrict__ X;
+  int IH, IW, C, stride, pad_h, pad_w, OHW, OW;
+  unsigned mOHW, sOHW, mOW, sOW;                     // FastDiv magic numbers of OH OW and OW
+  int rh[2], rw[2], rc[2], ch[2], cw[2], cc[2];      // (kh, kw, ci) of the lane's row / column elements; kh < 0: the constant 1
+  __device__ __forceinline__ void element(int e, int bias, int KW, int& kh, int& kw, int& ci) const {
+    e -= bias;
+    if (e < 0) { kh = -1; kw = 0; ci = 0; return; }
+    ci = e % C;
+    const int k = e / C;
+    kw = k % KW;
+    kh = k / KW;
+  }
+  __device__ __forceinline__ double at(int i, int kh, int kw, int ci) const {
+    const int img = (int)((__umulhi((unsigned)i, mOHW) + (unsigned)i) >> sOHW), t = i - img * OHW;
+    const int oh = (int)((__umulhi((unsigned)t, mOW) + (unsigned)t) >> sOW), ow = t - oh * OW;
+    const int ih = oh * stride - pad_h + kh, iw = ow * stride - pad_w + kw;
+    const bool in = kh >= 0 && ih >= 0 && ih < IH && iw >= 0 && iw < IW;
+    const int ihc = min(max(ih, 0), IH - 1), iwc = min(max(iw, 0), IW - 1);                   // clamped: the load stays inside
+    const float v = X[(((long long)img * IH + ihc) * IW + iwc) * C + ci];
+    return kh < 0 ? 1.0 : (in ? (double)v : 0.0);
+  }
+  __device__ __forceinline__ double row(int i, int t) const { return at(i, rh[t], rw[t], rc[t]); }
+  __device__ __forceinline__ double col(int i, int t) const { return at(i, ch[t], cw[t], cc[t]); }
+};
+
+struct KfacPlan {
+  int T;                 // tiles per edge
+  long long tiles;       // lower-triangle tiles
+  int ys, nper;          // row ranges and rows per range (a multiple of LL_SPAN)
+};
+
+static KfacPlan kfac_plan(int R, int Mt) {
+  KfacPlan p;
+  p.T = (Mt + LL_B - 1) / LL_B;
+  p.tiles = (long long)p.T * (p.T + 1) / 2;
+  ll_split(R, p.tiles, p.ys, p.nper);
+  return p;
+}
+
+__global__ __launch_bounds__(256) void kfac_input_gram_kernel(const float* __restrict__ X, KfacGeom g, int R, KfacPlan pl,
+                                                              FastDiv dOHW, FastDiv dOW, double* __restrict__ part) {
+  __shared__ double red[3 * LL_TILE];
+  const int i16 = threadIdx.x & 15;
+  const int tile = blockIdx.x;
+  int tr, tc;
+  ll_tri_tile(tile, tr, tc);
+  KfacPatchOperands op;
+  op.X = X, op.IH = g.IH, op.IW = g.IW, op.C = g.C, op.stride = g.stride, op.pad_h = g.pad_h, op.pad_w = g.pad_w;
+  op.OHW = g.OH * g.OW, op.OW = g.OW, op.mOHW = dOHW.m, op.sOHW = dOHW.s, op.mOW = dOW.m, op.sOW = dOW.s;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    op.element(min(tr * LL_B + 16 * t + i16, g.Mt - 1), g.bias, g.KW, op.rh[t], op.rw[t], op.rc[t]);   // clamped: never read back
+    op.element(min(tc * LL_B + 16 * t + i16, g.Mt - 1), g.bias, g.KW, op.ch[t], op.cw[t], op.cc[t]);
+  }
+  const int ib = blockIdx.y * pl.nper;
+  ll_gram_tile(op, ib, min(ib + pl.nper, R), red, part + ((long long)blockIdx.y * pl.tiles + tile) * LL_TILE);
+}
+
+// W (rows Mt, N) = J Ub: local row rho = (lr, j), lr = bl Kc + k the row of point b0 + bl and class k (source row
+// k B + b0 + bl of Jr), j the row of its (Mt, N) block.  A wave per 32 x 32 tile of W, a block per four column tiles; the
+// lane map is that of sub_tsigma_kernel and the sum stays in l order.
+__global__ __launch_bounds__(256) void kfac_jub_kernel(const float* __restrict__ Jr, long long ldj, long long off, int B,
+                                                       int Kc, int b0, long long rows, int Mt, int N,
+                                                       const double* __restrict__ Ub, double* __restrict__ W) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const int ct = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long r0 = (long long)blockIdx.x * 32;
+  if (ct * 32 >= N) return;
+  const float* pa[2];
+  const double* pb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    long long r = r0 + 16 * t + i16;
+    r = r < rows ? r : rows - 1;                                                             // clamped: never written back
+    const long long lr = r / Mt;
+    const int j = (int)(r - lr * Mt), bl = (int)(lr / Kc), k = (int)(lr - (long long)bl * Kc);
+    pa[t] = Jr + ((long long)k * B + b0 + bl) * ldj + off + (long long)j * N;
+    pb[t] = Ub + min(ct * 32 + 16 * t + i16, N - 1);
+  }
+  ll_f64x4 acc[2][2];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  for (int l0 = 0; l0 < N; l0 += 4) {
+    const int l = l0 + q;
+    const bool ok = l < N;
+    const int lc = ok ? l : N - 1;
+    double a[2], b[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const double av = (double)pa[t][lc], bv = pb[t][(long long)lc * N];
+      a[t] = ok ? av : 0.0;
+      b[t] = ok ? bv : 0.0;
+    }
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+  }
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long long row = r0 + 16 * tm + q + 4 * r;
+        const int col = ct * 32 + 16 * tn + i16;
+        if (row < rows && col < N) W[row * N + col] = acc[tm][tn][r];
+      }
+}
+
+// T_lr (Mt, N) = V^T W_lr for every local row lr: T[j][l] = sum_f V[f][j] W[f][l].  blockIdx.x = (lr, row tile), a wave
+// per 32 x 32 tile, a block per four column tiles; the sum stays in f order.
+__global__ __launch_bounds__(256) void kfac_vt_kernel(const double* __restrict__ V, const double* __restrict__ W, int Mt, int N,
+                                                      int MT32, double* __restrict__ T) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const int ct = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (ct * 32 >= N) return;
+  const long long lr = blockIdx.x / MT32;
+  const int rt = (int)(blockIdx.x - lr * MT32);
+  const double* Wr = W + lr * Mt * N;
+  const double* pa[2];
+  const double* pb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    pa[t] = V + min(rt * 32 + 16 * t + i16, Mt - 1);                                         // clamped: never written back
+    pb[t] = Wr + min(ct * 32 + 16 * t + i16, N - 1);
+  }
+  ll_f64x4 acc[2][2];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  int f0 = 0;
+  // four k-steps per round, every load issued before the first product
+  for (; f0 + 16 <= Mt; f0 += 16) {
+    double a[4][2], b[4][2];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int f = f0 + 4 * s + q;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        a[s][t] = pa[t][(long long)f * Mt];
+        b[s][t] = pb[t][(long long)f * N];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+          acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][tm], b[s][tn], acc[tm][tn], 0, 0, 0);
+  }
+  for (; f0 < Mt; f0 += 4) {
+    const int f = f0 + q;
+    const bool ok = f < Mt;
+    const int fc = ok ? f : Mt - 1;
+    double a[2], b[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const double av = pa[t][(long long)fc * Mt], bv = pb[t][(long long)fc * N];
+      a[t] = ok ? av : 0.0;
+      b[t] = ok ? bv : 0.0;
+    }
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+  }
+  double* Tr = T + lr * Mt * N;
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rt * 32 + 16 * tm + q + 4 * r, col = ct * 32 + 16 * tn + i16;
+        if (row < Mt && col < N) Tr[(long long)row * N + col] = acc[tm][tn][r];
+      }
+}
+
+// One entry sum_e R[e] tk[e] tm[e] by one block: a thread per e (every 256th), the threads' sums met by a fixed tree in
+// LDS.  Both forms go through it, so the diag form equals the diagonal of the full form bitwise.
+__device__ __forceinline__ double kfac_quad_entry(const double* __restrict__ R, const double* __restrict__ tk,
+                                                  const double* __restrict__ tm, int E, double* red) {
+  double t = 0.0;
+  for (int e = threadIdx.x; e < E; e += 256) t = fma(R[e] * tk[e], tm[e], t);
+  red[threadIdx.x] = t;
+  __syncthreads();
+  for (int w = 128; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// block = (local point bl, pair): the full form takes the pairs k <= m and mirrors, the diag form the pairs k == m
+__global__ __launch_bounds__(256) void kfac_quad_kernel(const double* __restrict__ R, const double* __restrict__ T, int Kc,
+                                                        int E, int b0, int pairs, double* __restrict__ out, int diag) {
+  __shared__ double red[256];
+  const int bl = blockIdx.x / pairs, pair = blockIdx.x - bl * pairs;
+  int k, m;
+  if (diag) k = m = pair;
+  else ll_tri_tile(pair, m, k);                                                              // m >= k
+  const double* base = T + (long long)bl * Kc * E;
+  const double t = kfac_quad_entry(R, base + (long long)k * E, base + (long long)m * E, E, red);
+  if (threadIdx.x != 0) return;
+  const long long b = b0 + bl;
+  if (diag) {
+    out[b * Kc + k] += t;
+  } else {
+    out[(b * Kc + k) * Kc + m] += t;
+    if (m != k) out[(b * Kc + m) * Kc + k] += t;
+  }
+}
+
+}  // namespace lip
+
+using namespace lip;
+
+static bool kfac_geom_ok(int32_t n, const KfacGeom& g) {
+  if (n <= 0 || g.IH <= 0 || g.IW <= 0 || g.C <= 0 || g.KH <= 0 || g.KW <= 0 || g.stride <= 0 || g.pad_h < 0 || g.pad_w < 0 ||
+      g.OH <= 0 || g.OW <= 0)
+    return false;
+  // every output position's window starts at or before the last input row / column (its rest may hang over: zeros)
+  return (long long)(g.OH - 1) * g.stride - g.pad_h < g.IH && (long long)(g.OW - 1) * g.stride - g.pad_w < g.IW &&
+         (long long)g.KH * g.KW * g.C + 1 <= 0x7fffffffll;
+}
+
+static KfacGeom kfac_geom(int32_t IH, int32_t IW, int32_t C, int32_t KH, int32_t KW, int32_t stride, int32_t pad_h,
+                          int32_t pad_w, int32_t OH, int32_t OW, int32_t bias) {
+  KfacGeom g;
+  g.IH = IH, g.IW = IW, g.C = C, g.KH = KH, g.KW = KW, g.stride = stride, g.pad_h = pad_h, g.pad_w = pad_w, g.OH = OH, g.OW = OW;
+  g.bias = bias ? 1 : 0;
+  g.Mt = (int)((long long)KH * KW * C) + g.bias;
+  return g;
+}
+
+// the tensors the 32-bit row arithmetic of the Gram can take: fewer than 2^31 input elements and Gram rows
+static bool kfac_fits(int32_t n, const KfacGeom& g) {
+  return (long long)n * g.IH * g.IW * g.C < (1ll << 31) && (long long)n * g.OH * g.OW < (1ll << 31);
+}
+
+static bool kfac_block_ok(int32_t B, int32_t Kc, int64_t off, int32_t Mt, int32_t N) {
+  return B > 0 && Kc > 0 && Mt > 0 && N > 0 && off >= 0 && (long long)Mt * N < (1ll << 31) && (long long)B * Kc < (1ll << 31);
+}
+
+extern "C" {
+
+int lip_kfac_input_gram_scratch(int32_t n, int32_t IH, int32_t IW, int32_t C, int32_t KH, int32_t KW, int32_t stride,
+                                int32_t pad_h, int32_t pad_w, int32_t OH, int32_t OW, int32_t bias, int64_t* doubles) {
+  const KfacGeom g = kfac_geom(IH, IW, C, KH, KW, stride, pad_h, pad_w, OH, OW, bias);
+  if (!doubles || !kfac_geom_ok(n, g)) { set_error("lip_kfac_input_gram_scratch: bad argument"); return LIP_ERR_ARG; }
+  if (!kfac_fits(n, g)) { set_error("lip_kfac_input_gram_scratch: a tensor of 2^31 or more elements; pass fewer images per call"); return LIP_ERR_ARG; }
+  const KfacPlan pl = kfac_plan(n * OH * OW, g.Mt);
+  *doubles = pl.tiles * pl.ys * LL_TILE;
+  return LIP_OK;
+}
+
+int lip_kfac_input_gram(const float* X, int32_t n, int32_t IH, int32_t IW, int32_t C, int32_t KH, int32_t KW, int32_t stride,
+                        int32_t pad_h, int32_t pad_w, int32_t OH, int32_t OW, int32_t bias, double* A, double* scratch,
+                        int64_t scratch_doubles, void* stream) {
+  const KfacGeom g = kfac_geom(IH, IW, C, KH, KW, stride, pad_h, pad_w, OH, OW, bias);
+  if (!X || !A || !scratch || !kfac_geom_ok(n, g)) { set_error("lip_kfac_input_gram: bad argument"); return LIP_ERR_ARG; }
+  if (!kfac_fits(n, g)) { set_error("lip_kfac_input_gram: a tensor of 2^31 or more elements; pass fewer images per call"); return LIP_ERR_ARG; }
+  const int R = n * OH * OW;
+  const KfacPlan pl = kfac_plan(R, g.Mt);
+  const long long need = pl.tiles * pl.ys * LL_TILE;
+  if (scratch_doubles < need) {
+    set_error("lip_kfac_input_gram: scratch of %lld doubles, %lld needed (lip_kfac_input_gram_scratch)", (long long)scratch_doubles, need);
+    return LIP_ERR_ARG;
+  }
+  if (pl.tiles > 0x7fffffffll || (g.Mt + 15) / 16 > 65535) { set_error("lip_kfac_input_gram: Mt = %d is too large", g.Mt); return LIP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(kfac_input_gram_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.ys), dim3(256), 0, st, X, g, R, pl,
+                     FastDiv((unsigned)(OH * OW)), FastDiv((unsigned)OW), scratch);
+  LIP_CHECK_HIP(hipGetLastError());
+  LIP_CHECK_HIP(launch_gram_assemble(scratch, pl.tiles, pl.ys, g.Mt, A, st));
+  return LIP_OK;
+}
+
+int lip_kfac_predict_scratch(int32_t B, int32_t Kc, int32_t Mt, int32_t N, int64_t* doubles) {
+  if (!doubles || !kfac_block_ok(B, Kc, 0, Mt, N)) { set_error("lip_kfac_predict_scratch: bad argument"); return LIP_ERR_ARG; }
+  *doubles = 2ll * B * Kc * Mt * N;                                  // W and T of every row; a (Kc, Mt, N) pair per point at least
+  return LIP_OK;
+}
+
+int lip_kfac_predict(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_t off, int32_t Mt, int32_t N, const double* V,
+                     const double* Ub, const double* R, double* out, int32_t diag, double* scratch, int64_t scratch_doubles,
+                     void* stream) {
+  if (!Jr || !V || !Ub || !R || !out || !scratch || !kfac_block_ok(B, Kc, off, Mt, N) || ldj < off + (long long)Mt * N) {
+    set_error("lip_kfac_predict: bad argument");
+    return LIP_ERR_ARG;
+  }
+  const int E = Mt * N, MT32 = (Mt + 31) / 32;
+  const long long per_point = 2ll * Kc * E;
+  if (scratch_doubles < per_point) {
+    set_error("lip_kfac_predict: scratch of %lld doubles, at least %lld needed for one point (lip_kfac_predict_scratch: all points)",
+              (long long)scratch_doubles, per_point);
+    return LIP_ERR_ARG;
+  }
+  const long long pairs = diag ? (long long)Kc : (long long)Kc * (Kc + 1) / 2;
+  // points per chunk: what the scratch holds, within the grids' 2^31 - 1 blocks
+  long long Bc = scratch_doubles / per_point;
+  Bc = std::min<long long>(Bc, B);
+  Bc = std::min<long long>(Bc, 0x7fffffffll / ((long long)Kc * std::max(Mt, 32)));
+  Bc = std::min<long long>(Bc, 0x7fffffffll / pairs);
+  if (Bc < 1 || (N + 127) / 128 > 65535) { set_error("lip_kfac_predict: Kc = %d, Mt = %d, N = %d is too large", (int)Kc, (int)Mt, (int)N); return LIP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned gy = (unsigned)((N + 127) / 128);
+  for (long long b0 = 0; b0 < B; b0 += Bc) {
+    const long long nb = std::min<long long>(Bc, B - b0), lrows = nb * Kc, rows = lrows * Mt;
+    double* W = scratch;
+    double* T = scratch + lrows * E;
+    hipLaunchKernelGGL(kfac_jub_kernel, dim3((unsigned)((rows + 31) / 32), gy), dim3(256), 0, st, Jr, (long long)ldj,
+                       (long long)off, (int)B, (int)Kc, (int)b0, rows, (int)Mt, (int)N, Ub, W);
+    LIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kfac_vt_kernel, dim3((unsigned)(lrows * MT32), gy), dim3(256), 0, st, V, (const double*)W, (int)Mt, (int)N,
+                       MT32, T);
+    LIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kfac_quad_kernel, dim3((unsigned)(nb * pairs)), dim3(256), 0, st, R, (const double*)T, (int)Kc, E, (int)b0,
+                       (int)pairs, out, (int)diag);
+    LIP_CHECK_HIP(hipGetLastError());
+  }
+  return LIP_OK;
+}
+
+}  // extern "C"

@@ -215,6 +215,30 @@ __global__ __launch_bounds__(256) void sub_quad_kernel(const double* __restrict_
 
 static long long sub_panel_doubles(long long rows, int S) { return (rows * S + 1) / 2; }
 
+// The Gram stages on their own (declared in lip_gramtile.h): lip_kfac.hip and the KRON sweep of lip_engine.hip run them too
+hipError_t launch_gram_assemble(const double* part, long long tiles, int ys, int S, double* G, hipStream_t st) {
+  const unsigned gb = (unsigned)((S + 15) / 16);
+  hipLaunchKernelGGL(sub_assemble_kernel, dim3(gb, gb), dim3(256), 0, st, part, tiles, ys, S, G);
+  return hipGetLastError();
+}
+
+bool panel_gram_fits(int R, int S) {
+  if (R <= 0 || S <= 0) return false;
+  return sub_plan(R, S).tiles <= 0x7fffffffll && (S + 15) / 16 <= 65535;
+}
+
+long long panel_gram_scratch(int R, int S) {
+  const SubPlan pl = sub_plan(R, S);
+  return pl.tiles * pl.ys * LL_TILE;
+}
+
+hipError_t launch_panel_gram(const float* panel, int R, int S, double* G, double* part, hipStream_t st) {
+  const SubPlan pl = sub_plan(R, S);
+  hipLaunchKernelGGL(sub_gram_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.ys), dim3(256), 0, st, panel, R, S, pl, part);
+  const hipError_t err = hipGetLastError();
+  return err != hipSuccess ? err : launch_gram_assemble(part, pl.tiles, pl.ys, S, G, st);
+}
+
 static void sub_gather(const float* W, long long ldw, long long D, long long R, const int64_t* idx, int S, int K, int B,
                        float* panel, hipStream_t st) {
   const unsigned gy = (unsigned)(R < 65535 ? R : 65535);
@@ -265,12 +289,7 @@ int lip_sub_gram(const float* W, int64_t ldw, int64_t D, int32_t R, const int64_
   double* part = scratch + pd;
   sub_gather(W, (long long)ldw, (long long)D, R, idx, S, 0, 0, panel, st);
   LIP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(sub_gram_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.ys), dim3(256), 0, st, (const float*)panel, (int)R,
-                     (int)S, pl, part);
-  LIP_CHECK_HIP(hipGetLastError());
-  const unsigned gb = (unsigned)((S + 15) / 16);
-  hipLaunchKernelGGL(sub_assemble_kernel, dim3(gb, gb), dim3(256), 0, st, (const double*)part, pl.tiles, pl.ys, (int)S, G);
-  LIP_CHECK_HIP(hipGetLastError());
+  LIP_CHECK_HIP(launch_panel_gram(panel, (int)R, (int)S, G, part, st));
   return LIP_OK;
 }
 

@@ -10,6 +10,9 @@ Supports a batch of distributions: loc (..., k), covariance (..., k, k).
 the sizes a diagonal posterior is used for.
 
 ``KroneckerNormal`` (not in the reference) is the factored Gaussian that ``posterior_lla_last_layer_kron`` returns.
+
+``KFACNormal`` (not in the reference) is the Gaussian over the whole flat vector that ``posterior_lla_kfac`` returns: one
+``KroneckerNormal`` per layer block and independent variances for the parameters outside every block.
 """
 from __future__ import annotations
 
@@ -125,3 +128,73 @@ class KroneckerNormal:
         E = torch.randn(tuple(sample_shape) + (Ft, K), dtype=self.loc.dtype, device=self.loc.device, generator=g)
         dW = self.V @ (E * torch.sqrt(self.R)) @ self.Ub.T
         return self.loc + dW.reshape(tuple(sample_shape) + (Ft * K,))
+
+
+class KFACNormal:
+    """N(loc, S) over the whole flat parameter vector (D,), S block-diagonal: ``blocks`` is a list of
+    ``(offset, KroneckerNormal)`` whose (Mt, N) blocks are the contiguous slices loc[offset : offset + Mt N], and
+    ``remainder`` = ``(indices, variance)`` gives every other parameter an independent variance.  Blocks and remainder
+    must cover [0, D) exactly once.  ``remainder_prior`` (the prior precisions of the remainder, or one number), when
+    given, lets :meth:`log_det_precision_ratio` include the remainder's term."""
+
+    def __init__(self, loc: torch.Tensor, blocks, remainder, remainder_prior=None):
+        idx, var = remainder
+        idx = torch.as_tensor(idx, dtype=torch.int64, device=loc.device).reshape(-1)
+        var = torch.as_tensor(var, device=loc.device).reshape(-1)
+        if idx.numel() != var.numel():
+            raise ValueError(f"the remainder has {idx.numel()} indices and {var.numel()} variances")
+        seen = torch.zeros(loc.shape[-1], dtype=torch.int64)
+        for off, kn in blocks:
+            Mt, N = kn.R.shape
+            if off < 0 or off + Mt * N > loc.shape[-1]:
+                raise ValueError(f"the ({Mt}, {N}) block at offset {off} does not lie in [0, {loc.shape[-1]})")
+            seen[off:off + Mt * N] += 1
+        seen.index_add_(0, idx.cpu(), torch.ones(idx.numel(), dtype=torch.int64))       # counts a repeated index twice
+        if not bool((seen == 1).all()):
+            raise ValueError("the blocks and the remainder must cover every parameter exactly once")
+        self.loc, self.blocks, self.remainder, self.remainder_prior = loc, list(blocks), (idx, var), remainder_prior
+
+    def mean(self) -> torch.Tensor:
+        return self.loc
+
+    def variance(self) -> torch.Tensor:
+        idx, var = self.remainder
+        out = torch.empty_like(self.loc)
+        for off, kn in self.blocks:
+            v = kn.variance()
+            out[off:off + v.numel()] = v.to(out.dtype)
+        out[idx] = var.to(out.dtype)
+        return out
+
+    def stddev(self) -> torch.Tensor:
+        return torch.sqrt(self.variance())
+
+    def log_det_precision_ratio(self) -> torch.Tensor:
+        """log det(prior^-1 posterior precision): the blocks' sums and -sum log(a_d var_d) over the remainder"""
+        idx, var = self.remainder
+        total = sum((kn.log_det_precision_ratio() for _, kn in self.blocks), torch.zeros((), dtype=torch.float64, device=self.loc.device))
+        if idx.numel():
+            if self.remainder_prior is None:
+                raise ValueError("the remainder's prior precisions are not known (remainder_prior)")
+            a = torch.as_tensor(self.remainder_prior, dtype=torch.float64, device=var.device)
+            total = total - torch.log(a * var.double()).sum()
+        return total
+
+    def sample(self, sample_shape=(), seed=None, dtype=torch.float32) -> torch.Tensor:
+        """draws (sample_shape + (D,)) of ``dtype``: every block through :meth:`KroneckerNormal.sample` (block l seeded
+        ``seed + l``), the remainder loc + sqrt(var) E (seeded ``seed + number of blocks``)"""
+        if isinstance(sample_shape, int):
+            sample_shape = (sample_shape,)
+        shape = tuple(sample_shape)
+        out = torch.empty(shape + (self.loc.shape[-1],), dtype=dtype, device=self.loc.device)
+        for l, (off, kn) in enumerate(self.blocks):
+            x = kn.sample(shape, seed=None if seed is None else int(seed) + l)
+            out[..., off:off + x.shape[-1]] = x.to(dtype)
+        idx, var = self.remainder
+        if idx.numel():
+            g = None
+            if seed is not None:
+                g = torch.Generator(device=self.loc.device).manual_seed(int(seed) + len(self.blocks))
+            E = torch.randn(shape + (idx.numel(),), dtype=var.dtype, device=var.device, generator=g)
+            out[..., idx] = (self.loc[idx].to(var.dtype) + torch.sqrt(var) * E).to(dtype)
+        return out

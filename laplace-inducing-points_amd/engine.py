@@ -114,6 +114,50 @@ def last_layer_of(net: NetSpec, layout: Dict[Tuple, Tuple[int, Tuple[int, ...]]]
     return boff, F, K
 
 
+@dataclasses.dataclass
+class KfacBlock:
+    """One layer block of the Kronecker-factored posterior: the flat slice theta[off : off + Mt N] = [bias (N)] + kernel
+    (M x N row-major) of a conv unit read as an (Mt, N) matrix, the bias row 0 when the unit has one; T = OH OW output
+    positions; ``bn`` the (offset, N) slice of the frozen BN scale s in the constants buffer, or None; ``src`` the
+    offset of the unit's input tensor in ``prim``; ``final``: the plain final Dense, whose classifier factor is centred."""
+    unit: Unit
+    off: int
+    Mt: int
+    N: int
+    T: int
+    bias: bool
+    kernel_off: int
+    final: bool = False
+    bn: Optional[Tuple[int, int]] = None
+    src: Optional[int] = None
+
+
+def kfac_block_table(net: NetSpec, layout: Dict[Tuple, Tuple[int, Tuple[int, ...]]]) -> List[KfacBlock]:
+    """The layer blocks of ``net``, one per conv unit in unit order, from the layer program and the flat layout
+    (``param_layout``) alone: pure Python.  Raises ``ValueError`` when a unit's bias is not directly before its kernel
+    in the flat parameter order."""
+    try:
+        last = last_dense_unit(net)
+    except ValueError:
+        last = None
+    blocks = []
+    for u in net.units:
+        if u.kind != "conv":
+            continue
+        M, N = u.kh * u.kw * u.cin, u.cout
+        oh, ow, _ = net.tensors[u.dst]
+        koff = layout[u.kernel][0]
+        off = koff
+        if u.bias is not None:
+            off = layout[u.bias][0]
+            if koff != off + N:
+                raise ValueError(f"the Kronecker-factored posterior needs the bias of {'/'.join(map(str, u.kernel[:-1]))} "
+                                 f"(offset {off}, {N} entries) directly before its kernel (offset {koff}) in the flat "
+                                 f"parameter order")
+        blocks.append(KfacBlock(u, off, M + (u.bias is not None), N, oh * ow, u.bias is not None, koff, final=u is last))
+    return blocks
+
+
 def _seg(a, b, IH, IW, Cc, KH, KW, stride, pad_h, pad_w, mode):
     return dict(a=a, b=b, IH=IH, IW=IW, C=Cc, KH=KH, KW=KW, stride=stride, pad_h=pad_h, pad_w=pad_w, mode=mode)
 
@@ -838,6 +882,156 @@ class LinearizedNet:
                                               nv.stream_ptr()), "lip_sub_predict")
             if part is not out:
                 out[:, k0:k1] = part
+        return out
+
+    # ------------------------------------------------------------------------------ Kronecker factors of every layer
+    KFAC_SCRATCH_BYTES = 1 << 30       # cap of the float64 scratch of one lip_kfac_predict call (it chunks the points)
+
+    def kfac_blocks(self) -> List[KfacBlock]:
+        """The layer blocks of this binding (:func:`kfac_block_table`) with the BN scale slice in ``consts`` and the
+        offset of every block's input tensor in ``prim`` filled in."""
+        blocks = getattr(self, "_kfac_blocks", None)
+        if blocks is None:
+            cn = self.cn
+            blocks = kfac_block_table(cn.net, cn.offsets)
+            for b in blocks:
+                b.src = cn.a_off[b.unit.src]
+                if b.unit.bn_scale is not None:
+                    b.bn = (cn.meta["s_off"][b.unit.dst], b.N)
+            self._kfac_blocks = blocks
+        return blocks
+
+    def _f64_scratch(self, name: str, doubles: int) -> torch.Tensor:
+        scratch = self._scratches.get(name)
+        if scratch is None or scratch.numel() < doubles:
+            scratch = self._scratches[name] = torch.empty(max(1, int(doubles)), device=self.device, dtype=torch.float64)
+        return scratch
+
+    def kfac_input_grams(self, As: List[torch.Tensor]) -> List[torch.Tensor]:
+        """ADD A_l += sum_i sum_t at_{i,t} at_{i,t}^T of this binding's examples into every (Mt, Mt) float64 matrix of
+        ``As``: one ``lip_kfac_input_gram`` per block on the cached primal activations."""
+        tens = self.cn.net.tensors
+        for b, A in zip(self.kfac_blocks(), As):
+            u = b.unit
+            ih, iw, _ = tens[u.src]
+            oh, ow, _ = tens[u.dst]
+            geom = (self.n, ih, iw, u.cin, u.kh, u.kw, u.stride, u.pad_h, u.pad_w, oh, ow, int(b.bias))
+            doubles = C.c_int64(0)
+            nv.check(self.lib.lip_kfac_input_gram_scratch(*geom, C.byref(doubles)), "lip_kfac_input_gram_scratch")
+            scratch = self._f64_scratch("lip_kfac_input_gram", doubles.value)
+            nv.check(self.lib.lip_kfac_input_gram(self.prim[b.src:].data_ptr(), *geom, A.data_ptr(), scratch.data_ptr(),
+                                                  scratch.numel(), nv.stream_ptr()), "lip_kfac_input_gram")
+        return As
+
+    def kfac_output_grams(self, Ss: List[torch.Tensor], class_chunk: Optional[int] = None) -> List[torch.Tensor]:
+        """ADD S_l += sum_i sum_t sum_k g_{i,t,k} g_{i,t,k}^T into every (N, N) float64 matrix of ``Ss``: one
+        ``lip_vjp_kron`` sweep ('l') over the one-hot probes, in the class blocks of :meth:`_class_blocks`; the frozen BN
+        scale s s^T o S_l is applied here, in float64, to this binding's sums before they are added."""
+        blocks = self.kfac_blocks()
+        cap = len(blocks)
+        koff, ooff, Ns = (C.c_int64 * cap)(), (C.c_int64 * cap)(), (C.c_int32 * cap)()
+        count, total = C.c_int32(0), C.c_int64(0)
+        nv.check(self.lib.lip_vjp_kron_layout(self.h, cap, koff, ooff, Ns, C.byref(count), C.byref(total)), "lip_vjp_kron_layout")
+        where = {int(koff[i]): (int(ooff[i]), int(Ns[i])) for i in range(min(cap, count.value))}
+        if count.value != cap or any(b.kernel_off not in where or where[b.kernel_off][1] != b.N for b in blocks):
+            raise nv.NativeError("lip_vjp_kron_layout: the backward tape's weight gradients do not match the layer blocks")
+        buf = torch.zeros(total.value, device=self.device, dtype=torch.float64)
+        eye = torch.eye(self.K, device=self.device, dtype=torch.float32)
+        for k0, k1 in self._class_blocks(class_chunk):
+            doubles = C.c_int64(0)                     # for the probes this call passes: the need is not monotone in them
+            nv.check(self.lib.lip_vjp_kron_scratch(self.h, k1 - k0, C.byref(doubles)), "lip_vjp_kron_scratch")
+            scratch = self._f64_scratch("lip_vjp_kron", doubles.value)
+            E = eye[k0:k1, None, :].expand(k1 - k0, self.n, self.K).contiguous()
+            nv.check(self.lib.lip_vjp_kron(self.h, nv.ptr(E), buf.data_ptr(), k1 - k0, nv.HEAD_L, 1.0, scratch.data_ptr(),
+                                           scratch.numel(), nv.stream_ptr()), "lip_vjp_kron")
+        for b, S in zip(blocks, Ss):
+            o, N = where[b.kernel_off]
+            part = buf[o:o + N * N].reshape(N, N)
+            if b.bn is not None:
+                s = self.consts[b.bn[0]:b.bn[0] + N].double()
+                part = part * (s[:, None] * s[None, :])            # the outer product first: exactly symmetric
+            S += part
+        return Ss
+
+    def kfac_factors(self, As: List[torch.Tensor], Ss: List[torch.Tensor], class_chunk: Optional[int] = None):
+        """ADD this binding's examples into the Kronecker factors of every layer block (:meth:`kfac_blocks` order):
+        ``As[l]`` (Mt, Mt) and ``Ss[l]`` (N, N), contiguous float64 device matrices; unscaled."""
+        blocks = self.kfac_blocks()
+        if len(As) != len(blocks) or len(Ss) != len(blocks):
+            raise ValueError(f"{len(blocks)} layer blocks need {len(blocks)} matrices in As and in Ss")
+        for b, A, S in zip(blocks, As, Ss):
+            for name, t, d in (("A", A, b.Mt), ("S", S, b.N)):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (d, d)):
+                    raise ValueError(f"{name} of the block at offset {b.off} must be a contiguous float64 device matrix of "
+                                     f"{d} x {d}")
+        self.kfac_input_grams(As)
+        self.kfac_output_grams(Ss, class_chunk=class_chunk)
+        return As, Ss
+
+    def _kfac_predict_rows(self, rows: torch.Tensor, B: int, Kc: int, fits, rem, out: torch.Tensor, diag: bool) -> None:
+        """add every block's and the remainder's term of the (Kc, B, D) float32 rows into ``out``"""
+        for b, (V, R, Ub) in zip(self.kfac_blocks(), fits):
+            doubles = C.c_int64(0)
+            nv.check(self.lib.lip_kfac_predict_scratch(B, Kc, b.Mt, b.N, C.byref(doubles)), "lip_kfac_predict_scratch")
+            one = 2 * Kc * b.Mt * b.N
+            scratch = self._f64_scratch("lip_kfac_predict", min(doubles.value, max(one, self.KFAC_SCRATCH_BYTES // 8)))
+            nv.check(self.lib.lip_kfac_predict(rows.data_ptr(), self.D, B, Kc, b.off, b.Mt, b.N, V.data_ptr(), Ub.data_ptr(),
+                                               R.data_ptr(), out.data_ptr(), int(diag), scratch.data_ptr(), scratch.numel(),
+                                               nv.stream_ptr()), "lip_kfac_predict")
+        idx, var = rem
+        if idx.numel():
+            Jd = rows[:, :, idx].double()                                                  # (Kc, B, r)
+            dg = (Jd * Jd * var).sum(-1).T                                                  # (B, Kc)
+            if diag:
+                out += dg
+            else:
+                # symmetrised, and its diagonal the expression of the diag form: the two forms agree bitwise there
+                full = torch.einsum("kbd,d,mbd->bkm", Jd, var, Jd)
+                full = 0.5 * (full + full.transpose(1, 2))
+                k = torch.arange(Kc, device=full.device)
+                full[:, k, k] = dg
+                out += full
+
+    def kfac_predict(self, fits, rem, diag: bool = False, class_chunk: Optional[int] = None) -> torch.Tensor:
+        """J(x) Sigma J(x)^T for every point of this binding under the Kronecker-factored posterior: (n, K, K) float64,
+        or (n, K) for ``diag``.  ``fits`` holds (V, R, Ub) of every layer block in :meth:`kfac_blocks` order (contiguous
+        float64 device matrices), ``rem`` = (indices, variances) of the parameters outside every block, whose term
+        sum_d J_d^2 var_d is formed in float64 torch.  The blocks go through ``lip_kfac_predict`` on the 'raw' rows of
+        :meth:`vjp_rows`, with the row-block cap and the refusals of :meth:`subnetwork_predict`."""
+        blocks = self.kfac_blocks()
+        if len(fits) != len(blocks):
+            raise ValueError(f"{len(blocks)} layer blocks need {len(blocks)} fitted factor triples")
+        for b, (V, R, Ub) in zip(blocks, fits):
+            for name, t, shape in (("V", V, (b.Mt, b.Mt)), ("R", R, (b.Mt, b.N)), ("Ub", Ub, (b.N, b.N))):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"{name} of the block at offset {b.off} must be a contiguous float64 device matrix of "
+                                     f"{shape[0]} x {shape[1]}")
+        rem = (rem[0].to(self.device), rem[1].to(device=self.device, dtype=torch.float64))
+        K, n = self.K, self.n
+        if diag:
+            out = torch.zeros(n, K, device=self.device, dtype=torch.float64)
+            for k0, k1 in self._class_blocks(class_chunk):
+                Kc = k1 - k0
+                part = out if Kc == K else torch.zeros(n, Kc, device=self.device, dtype=torch.float64)
+                self._kfac_predict_rows(self._one_hot_rows(k0, k1, "raw"), n, Kc, fits, rem, part, True)
+                if part is not out:
+                    out[:, k0:k1] = part
+            return out
+        fit = (self.ROW_BLOCK_BYTES // (4 * self.D)) // K
+        if fit < 1:
+            raise ValueError(f"the full predictive needs the K = {K} Jacobian rows of a point at once: {K} x {self.D} "
+                             f"floats exceed the row-block cap (use diag)")
+        out = torch.zeros(n, K, K, device=self.device, dtype=torch.float64)
+        if fit >= n:
+            self._kfac_predict_rows(self._one_hot_rows(0, K, "raw"), n, K, fits, rem, out, False)
+            return out
+        # the rows of all n points do not fit: chunks of `fit` points, as in subnetwork_predict
+        for b0 in range(0, n, fit):
+            b1 = min(n, b0 + fit)
+            Jr = torch.empty(K, b1 - b0, self.D, device=self.device, dtype=torch.float32)
+            for k0, k1 in self._class_blocks(class_chunk):
+                Jr[k0:k1] = self._one_hot_rows(k0, k1, "raw")[:, b0:b1]
+            self._kfac_predict_rows(Jr, b1 - b0, K, fits, rem, out[b0:b1], False)
         return out
 
     # ------------------------------------------------------------------------------ measurement

@@ -270,6 +270,13 @@ def compute_kron_factors_last_layer(state, Z, model_type, example_chunk: Optiona
     return last_layer_kron.compute_kron_factors_last_layer(state, Z, model_type, example_chunk=example_chunk)
 
 
+def compute_kfac_factors(state, Z, model_type, example_chunk: Optional[int] = None):
+    """``(blocks, As, Ss, M)``: the layer blocks of the Kronecker-factored posterior over all layers and their two
+    factors per block, float64, unscaled (:func:`kfac.compute_kfac_factors`)."""
+    from . import kfac
+    return kfac.compute_kfac_factors(state, Z, model_type, example_chunk=example_chunk)
+
+
 def compute_ggn_subnetwork(state, Z, model_type, indices, full_set_size=None, example_chunk: Optional[int] = None) -> torch.Tensor:
     """The dense GGN block over the flat-parameter indices ``indices``, (S, S) float64, scaled like
     :func:`compute_ggn_vp` and chunked like :func:`compute_ggn_diag` (:func:`subnetwork.compute_ggn_subnetwork`)."""

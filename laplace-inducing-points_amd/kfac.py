@@ -1,0 +1,241 @@
+"""Kronecker-factored Laplace over every layer (KFAC; KFC for convolutions): a Gaussian over the whole flat parameter
+vector whose covariance is block-diagonal with one Kronecker-factored block per weight tensor.  Not a reference function.
+
+A layer l is every unit of kind ``"conv"`` of the ``NetSpec`` (a Dense is a 1x1 convolution on a 1x1 map, a Dense on a
+feature map an h x w VALID convolution with one output position).  Its block is the contiguous flat slice
+[bias (N)] + kernel (M x N row-major), M = KH KW Cin in HWIO order, read as an (Mt, N) matrix with the bias as row 0
+when the unit has one (``engine.kfac_block_table``).  With at_{i,t} the im2col patch of the layer's input at output
+position t of example i (zero outside the image, a leading 1 for the bias) and g_{i,t,k} the cotangent of the raw
+convolution output for column k of the square-root Hessian factor,
+
+    A_l = sum_i sum_t at_{i,t} at_{i,t}^T  (Mt, Mt),    S_l = sum_i sum_t sum_k g_{i,t,k} g_{i,t,k}^T  (N, N),
+    G_l = (recal / (M T_l)) A_l (x) S_l,
+
+M the number of bound examples, T_l = OH OW and recal the N/M (x exp(-logvar)) factor of ``compute_ggn_vp``.  At
+T_l = 1 this is c A (x) Bf of ``last_layer_kron.py``, and the final Dense block reproduces that module (its classifier
+factor is centred as there).  A_l comes from the cached primal activations (``lip_kfac_input_gram``), every S_l from one
+backward sweep of K one-hot probes (``lip_vjp_kron``); both are float64 Grams, bitwise reproducible.
+
+Every parameter outside a layer block (BN scale and bias) gets the exact GGN diagonal of ``compute_ggn_diag`` and is
+independent of everything else; a net without BN has no such parameter and runs no square-sum sweep.
+
+The prior is a scalar alpha or a :class:`prior.GroupedPrior` that is constant along the N outputs of each row of each
+block (the rule of ``last_layer_kron.prior_rows``).  The host algebra of a block is that module's
+(``factor_posterior``, ``distributions.KroneckerNormal``).
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Tuple
+
+import torch
+
+from . import ggn as _ggn
+from .distributions import KFACNormal, KroneckerNormal
+from .engine import KfacBlock, LinearizedNet, kfac_block_table
+from .last_layer import _engines, _recal
+from .last_layer_kron import factor_posterior, prior_rows
+from .prior import check_dim, is_grouped
+from .utils import flatten_nn_params, param_layout
+
+
+def block_table(state) -> List[KfacBlock]:
+    """the layer blocks of ``state.net`` from the layer program and ``param_layout`` alone (pure Python, no GPU)"""
+    net = getattr(state, "net", None)
+    if net is None:
+        raise TypeError("the Kronecker-factored posterior needs state.net (a NetSpec layer program)")
+    return kfac_block_table(net, {path: (o, shape) for path, o, shape in param_layout(state.params)})
+
+
+def prior_rows_no_bias(alpha, off: int, M: int, N: int, D: int) -> torch.Tensor:
+    """(M,) float64 CPU: :func:`last_layer_kron.prior_rows` for an (M, N) block without a bias row, row j kernel row j;
+    raises ``ValueError`` when a :class:`prior.GroupedPrior` varies along the N outputs within a row"""
+    if not is_grouped(alpha):
+        return torch.full((M,), float(alpha), dtype=torch.float64)
+    check_dim(alpha, D)
+    rows = torch.full((M,), float("nan"), dtype=torch.float64)
+    for g, (name, segs) in enumerate(alpha.table):
+        for o, n in segs:
+            s, e = max(o, off) - off, min(o + n, off + M * N) - off
+            if s >= e:
+                continue
+            seen = rows[s // N:(e + N - 1) // N]
+            clash = ~torch.isnan(seen) & (seen != alpha.values[g])
+            if bool(clash.any()):
+                raise ValueError(f"prior group {name!r} gives row {s // N + int(clash.nonzero()[0])} of the ({M}, {N}) "
+                                 f"kernel block at flat offset {off} a second precision: the Kronecker-factored posterior "
+                                 f"needs a prior that is constant along the N outputs of each row of each block")
+            seen.fill_(float(alpha.values[g]))
+    return rows
+
+
+def block_prior_rows(alpha, b: KfacBlock, D: int) -> torch.Tensor:
+    """(Mt,) row precisions of one block"""
+    if b.bias:
+        return prior_rows(alpha, b.off, b.Mt - 1, b.N, D)
+    return prior_rows_no_bias(alpha, b.off, b.Mt, b.N, D)
+
+
+def remainder_indices(blocks: List[KfacBlock], D: int) -> torch.Tensor:
+    """sorted int64 CPU indices of the parameters outside every block"""
+    keep = torch.ones(D, dtype=torch.bool)
+    for b in blocks:
+        keep[b.off:b.off + b.Mt * b.N] = False
+    return keep.nonzero().reshape(-1)
+
+
+def _remainder_prior(alpha, idx: torch.Tensor, D: int) -> torch.Tensor:
+    if is_grouped(alpha):
+        return check_dim(alpha, D).vector("cpu", torch.float64)[idx]
+    return torch.full((idx.numel(),), float(alpha), dtype=torch.float64)
+
+
+def compute_kfac_factors(state, Z, model_type, example_chunk: Optional[int] = None, class_chunk: Optional[int] = None):
+    """``(blocks, As, Ss, M)``: the layer blocks and their two unscaled factors summed over the M = len(Z) examples,
+    float64 on the device (:meth:`LinearizedNet.kfac_factors`), chunked like
+    :func:`last_layer_kron.compute_kron_factors_last_layer`; all chunks add into one pair per block."""
+    blocks = block_table(state)
+    engines = _engines(state, Z, model_type, None, example_chunk)
+    dev = engines[0].device
+    As = [torch.zeros(b.Mt, b.Mt, device=dev, dtype=torch.float64) for b in blocks]
+    Ss = [torch.zeros(b.N, b.N, device=dev, dtype=torch.float64) for b in blocks]
+    for eng in engines:
+        eng.kfac_factors(As, Ss, class_chunk=class_chunk)
+    return engines[0].kfac_blocks(), As, Ss, Z.shape[0]
+
+
+def fit_blocks(blocks, As, Ss, rows, recal: float, M: int, classifier: bool):
+    """[(V, R, Ub, lam, mu, c)] per block from the factors and the row precisions: ``factor_posterior`` with
+    c_l = recal / (M T_l); the final Dense block of a classifier is centred.  Float64 on the device of the factors
+    (CPU included)."""
+    return [factor_posterior(A, S, a, recal / (M * b.T), classifier and b.final) + (recal / (M * b.T),)
+            for b, A, S, a in zip(blocks, As, Ss, rows)]
+
+
+def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk):
+    """(blocks, fits, rem_idx, rem_var, rem_prior); the prior is checked before anything is allocated"""
+    blocks = block_table(map_state)
+    D = flatten_nn_params(map_state.params)[0].numel()
+    rows = [block_prior_rows(alpha, b, D) for b in blocks]
+    rem = remainder_indices(blocks, D)
+    a_rem = _remainder_prior(alpha, rem, D)
+    blocks, As, Ss, M = compute_kfac_factors(map_state, Z, model_type, example_chunk=example_chunk)
+    fits = fit_blocks(blocks, As, Ss, rows, _recal(map_state, M, model_type, full_set_size), M, model_type != "regressor")
+    dev = As[0].device
+    rem_var = torch.zeros(0, device=dev, dtype=torch.float64)
+    if rem.numel():
+        diag = _ggn.compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk)
+        rem_var = 1.0 / (a_rem.to(dev) + diag.double()[rem.to(dev)])
+    return blocks, fits, rem.to(dev), rem_var, a_rem.to(dev)
+
+
+def _prior_key(alpha):
+    return alpha.key() if is_grouped(alpha) else float(alpha)
+
+
+_FIT_CACHE = {}          # one entry, as last_layer_kron._FIT_CACHE
+
+
+def _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk):
+    """the fit, computed once per (binding, prior, N, chunking); ``clear_engine_cache`` drops the entry"""
+    if _FIT_CACHE.clear not in _ggn._CLEAR_HOOKS:
+        _ggn._CLEAR_HOOKS.append(_FIT_CACHE.clear)
+    key = (_ggn.engine_key(map_state, Z, model_type), _prior_key(alpha), full_set_size, example_chunk)
+    hit = _FIT_CACHE.get(key)
+    if hit is None:
+        fit = _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+        _FIT_CACHE.clear()
+        hit = _FIT_CACHE[key] = (fit, (map_state.params, map_state.batch_stats, Z))
+    return hit[0]
+
+
+def posterior_from_fit(flat: torch.Tensor, blocks, fits, rem_idx, rem_var, rem_prior=None) -> KFACNormal:
+    """the :class:`KFACNormal` of a fit, on the device of its factors (CPU included)"""
+    dev = fits[0][0].device
+    loc = flat.detach().to(device=dev, dtype=torch.float64)
+    parts = [(b.off, KroneckerNormal(loc[b.off:b.off + b.Mt * b.N], V, R, Ub, spectrum=(lam, mu, c)))
+             for b, (V, R, Ub, lam, mu, c) in zip(blocks, fits)]
+    return KFACNormal(loc, parts, (rem_idx, rem_var), remainder_prior=rem_prior)
+
+
+def posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=None, example_chunk: Optional[int] = None) -> KFACNormal:
+    """N(theta_MAP, blockdiag((G_l + diag(a))^-1, remainder)) over the whole flat vector in factored form, float64 on
+    the device; nothing of size D x D, and no Mt N x Mt N matrix, is built.  The fit is cached per
+    (state, Z, prior, N, chunking) (a one-entry cache)."""
+    blocks, fits, rem_idx, rem_var, rem_prior = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+    flat, _ = flatten_nn_params(map_state.params)
+    return posterior_from_fit(flat, blocks, fits, rem_idx, rem_var, rem_prior)
+
+
+def predict_lla_kfac(map_state, Xnew, Z, model_type, alpha, full_set_size=None, cov: str = "full", batch: int = 256,
+                     example_chunk: Optional[int] = None):
+    """Closed-form linearised predictive of :func:`posterior_lla_kfac`: mean f(x; theta_MAP) and
+    sum_l J_l(x) Sigma_l J_l(x)^T + sum_d J_d(x)^2 var_d per test point (``lip_kfac_predict`` per layer block on the
+    Jacobian rows of ``lip_vjp_rows``), in the return shapes and types of
+    :func:`last_layer_kron.predict_lla_last_layer_kron`.  ``batch`` test points are bound at a time, fewer for
+    ``cov="full"`` when their (K, batch, D) float32 rows would exceed 2 GiB."""
+    from .distributions import MultivariateNormalFullCovariance
+    if cov not in ("diag", "full"):
+        raise ValueError("cov must be 'diag' or 'full'")
+    _, fits, rem_idx, rem_var, _ = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+    triples = [(V, R, Ub) for V, R, Ub, _, _, _ in fits]
+    if cov == "full":
+        D = flatten_nn_params(map_state.params)[0].numel()
+        fit = (LinearizedNet.ROW_BLOCK_BYTES // (4 * D)) // int(map_state.net.num_outputs)
+        if fit < 1:
+            raise ValueError("the K Jacobian rows of one test point exceed the row-block cap: use cov='diag'")
+        batch = min(int(batch), fit)
+    means, outs = [], []
+    for s0 in range(0, Xnew.shape[0], batch):
+        eng = _ggn.get_engine(map_state, Xnew[s0:s0 + batch], model_type)
+        outs.append(eng.kfac_predict(triples, (rem_idx, rem_var), diag=cov == "diag"))
+        means.append(eng.outputs().double())
+    f_mean, f_out = torch.cat(means), torch.cat(outs)
+    if cov == "diag":
+        return (f_mean.squeeze(-1), f_out.squeeze(-1)) if model_type == "regressor" else (f_mean, f_out)
+    if model_type == "regressor":
+        return MultivariateNormalFullCovariance(loc=f_mean.squeeze(), covariance_matrix=torch.diag(f_out.reshape(-1)))
+    return MultivariateNormalFullCovariance(loc=f_mean.squeeze(), covariance_matrix=f_out)
+
+
+def predict_lla_kfac_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1,
+                              example_chunk: Optional[int] = None) -> torch.Tensor:
+    """Draws of the outputs under :func:`posterior_lla_kfac`: f(x; theta_MAP) + J(x) d_theta_s -> (S, B, K) float32,
+    d_theta_s the zero-mean part of ``num_samples`` draws of :meth:`KFACNormal.sample` pushed through the engine's JVP
+    ('raw'), as :func:`lla.predict_lla_diag_scalable` does.  This is the route for heads like ResNet-50's: K = 1000
+    Jacobian rows per test point make the closed form of :func:`predict_lla_kfac` impractical there, while a draw costs
+    one tangent-forward pass whatever K is."""
+    post = posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=full_set_size, example_chunk=example_chunk)
+    key = key if key is not None else 123
+    d_theta = post.sample((num_samples,), seed=key, dtype=torch.float64) - post.mean()
+    eng = _ggn.get_engine(map_state, Xnew, model_type, workspace_bytes=4 << 30)
+    return eng.outputs()[None] + eng.jvp(d_theta.float(), "raw")
+
+
+def kfac_spectrum(blocks, As, Ss, M: int, classifier: bool) -> torch.Tensor:
+    """the concatenation of outer(lam_l, mu_l) / (M T_l) over the blocks: the spectrum of blockdiag(A_l (x) S_l / (M T_l)),
+    what ``_lml_from_spectrum`` takes at N/M = 1; the final classifier block centred.  Float64 on the factors' device."""
+    from .last_layer_kron import centre
+    parts = []
+    for b, A, S in zip(blocks, As, Ss):
+        S = centre(S) if (classifier and b.final) else S
+        lam = torch.linalg.eigvalsh(0.5 * (A + A.T)).clamp_min(0.0)
+        mu = torch.linalg.eigvalsh(0.5 * (S + S.T)).clamp_min(0.0)
+        parts.append((lam[:, None] * mu[None, :] / (M * b.T)).reshape(-1))
+    return torch.cat(parts)
+
+
+def _spectrum_kfac(X, state, model_type) -> Tuple[torch.Tensor, int, float]:
+    """eigenvalues (float64, clamped at 0) of the Kronecker-factored curvature built at N/M = 1 (x exp(-logvar) for the
+    regressor) with the remainder's GGN diagonal appended, D, ||theta||^2"""
+    blocks, As, Ss, M = compute_kfac_factors(state, X, model_type)
+    spec = kfac_spectrum(blocks, As, Ss, M, model_type != "regressor")
+    if model_type == "regressor":
+        spec = spec * math.exp(-_ggn._logvar(state))
+    flat, _ = flatten_nn_params(state.params)
+    D = flat.numel()
+    rem = remainder_indices(blocks, D)
+    if rem.numel():
+        diag = _ggn.compute_ggn_diag(state, X, model_type)
+        spec = torch.cat([spec, diag.double()[rem.to(diag.device)].clamp_min(0.0)])
+    return spec, D, float((flat.detach().double() ** 2).sum())
