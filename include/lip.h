@@ -396,6 +396,20 @@ int lip_kfac_predict_scratch(int32_t B, int32_t Kc, int32_t Mt, int32_t N, int64
 int lip_kfac_predict(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_t off, int32_t Mt, int32_t N, const double* V,
                      const double* Ub, const double* R, double* out, int32_t diag, double* scratch, int64_t scratch_doubles,
                      void* stream);
+/* Second moments of the factor rows in a block's Kronecker eigenbasis (EKFAC), float64, ADDED into Lam (Mt, N):
+ *   Lam[j][l] += sum_{r < R} ( sum_{f,k} V[f][j] W_r[f][k] Ub[k][l] )^2
+ * W (R, ldw) float32, the rows lip_vjp_rows writes for one-hot probes in LIP_HEAD_L mode; W_r the (Mt, N) row-major
+ * block at flat offset off of row r, ldw >= off + Mt N; V (Mt, Mt) and Ub (N, N) float64 row-major.  Chunks of examples
+ * and of classes add into one Lam.  W_r Ub lives in scratch (stage one of lip_kfac_predict); V^T (W_r Ub) is formed tile
+ * by tile on the float64 matrix pipe, squared in registers and summed over groups of rows, whose partial sums (also in
+ * scratch) are folded in group order: V^T W_r Ub is never written, no atomics, and two calls with identical arguments
+ * give bitwise identical results.  lip_kfac_eigen_sqsum_scratch gives the doubles for all R rows at once; a smaller
+ * scratch (at least 2 Mt N doubles, one row) makes the call run in chunks of rows.  A null pointer, a non-positive
+ * extent, off < 0, ldw < off + Mt N, Mt N >= 2^31 or a scratch below one row returns LIP_ERR_ARG and leaves Lam
+ * untouched. */
+int lip_kfac_eigen_sqsum_scratch(int32_t R, int32_t Mt, int32_t N, int64_t* doubles);
+int lip_kfac_eigen_sqsum(const float* W, int64_t ldw, int32_t R, int64_t off, int32_t Mt, int32_t N, const double* V,
+                         const double* Ub, double* Lam, double* scratch, int64_t scratch_doubles, void* stream);
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);

@@ -16,6 +16,11 @@
 // Predict: W = J Ub and T = V^T W on v_mfma_f64_16x16x4_f64 (the tile code of sub_tsigma_kernel), both in the caller's
 // scratch, for chunks of test points that fit it; then one block per output entry walks R o T_k o T_m.  The diag form
 // runs the k == m entries through the same function, so it equals the diagonal of the full form bitwise.
+//
+// Eigenbasis square sums (lip_kfac_eigen_sqsum, the fit-time twin of the predictive, for EKFAC):
+//   Lam[j][l]     += sum_{r < R} T_r[j][l]^2
+// Stage one is the predictive's (kfac_jub_kernel with Kc = 1); stage two forms V^T W_r tile by tile, squares it in
+// registers and sums over groups of rows, so T is never written; the groups' partial sums are folded in group order.
 #include <algorithm>
 #include "lip_internal.h"
 #include "lip_gramtile.h"
@@ -246,6 +251,121 @@ __global__ __launch_bounds__(256) void kfac_quad_kernel(const double* __restrict
   }
 }
 
+// The row groups of the eigenbasis square sums: each block of kfac_sqsum_kernel owns a row tile and four column tiles of
+// Lam, so a small block has few of them; the local rows are split over ~1024 / blocks groups of nper consecutive rows.
+struct KfacSqPlan {
+  int groups, nper;
+};
+
+static long long kfac_sq_max_groups(int Mt, int N) {
+  const long long blocks = (long long)((Mt + 31) / 32) * ((N + 127) / 128);
+  return std::min<long long>((1024 + blocks - 1) / blocks, 1024);
+}
+
+static KfacSqPlan kfac_sq_plan(long long lrows, int Mt, int N) {
+  const long long gz = std::max<long long>(1, std::min(kfac_sq_max_groups(Mt, N), lrows));
+  KfacSqPlan p;
+  p.nper = (int)((lrows + gz - 1) / gz);
+  p.groups = (int)((lrows + p.nper - 1) / p.nper);
+  return p;
+}
+
+// part_g (Mt, N) = sum_{lr in group g} T_lr o T_lr, T_lr = V^T W_lr: the product of kfac_vt_kernel (same lane map, the
+// sum in f order) per local row, squared in registers and accumulated over the group's rows in row order; T is never
+// written.  blockIdx = (row tile, four column tiles, group), a wave per 32 x 32 tile of Lam.
+__global__ __launch_bounds__(256) void kfac_sqsum_kernel(const double* __restrict__ V, const double* __restrict__ W, int Mt,
+                                                         int N, long long lrows, int nper, double* __restrict__ part) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const int ct = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (ct * 32 >= N) return;
+  const int rt = blockIdx.x;
+  const long long E = (long long)Mt * N;
+  const long long lr0 = (long long)blockIdx.z * nper, lr1 = min(lr0 + nper, lrows);
+  const double* pa[2];
+  int cb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    pa[t] = V + min(rt * 32 + 16 * t + i16, Mt - 1);                                         // clamped: never written back
+    cb[t] = min(ct * 32 + 16 * t + i16, N - 1);
+  }
+  ll_f64x4 sq[2][2];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) sq[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  for (long long lr = lr0; lr < lr1; ++lr) {
+    const double* pb[2] = {W + lr * E + cb[0], W + lr * E + cb[1]};
+    ll_f64x4 acc[2][2];
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+    int f0 = 0;
+    // four k-steps per round, every load issued before the first product
+    for (; f0 + 16 <= Mt; f0 += 16) {
+      double a[4][2], b[4][2];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int f = f0 + 4 * s + q;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          a[s][t] = pa[t][(long long)f * Mt];
+          b[s][t] = pb[t][(long long)f * N];
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+          for (int tn = 0; tn < 2; ++tn)
+            acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][tm], b[s][tn], acc[tm][tn], 0, 0, 0);
+    }
+    for (; f0 < Mt; f0 += 4) {
+      const int f = f0 + q;
+      const bool ok = f < Mt;
+      const int fc = ok ? f : Mt - 1;
+      double a[2], b[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const double av = pa[t][(long long)fc * Mt], bv = pb[t][(long long)fc * N];
+        a[t] = ok ? av : 0.0;
+        b[t] = ok ? bv : 0.0;
+      }
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+    }
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sq[tm][tn][r] = fma(acc[tm][tn][r], acc[tm][tn][r], sq[tm][tn][r]);
+  }
+  double* mine = part + (long long)blockIdx.z * E;
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rt * 32 + 16 * tm + q + 4 * r, col = ct * 32 + 16 * tn + i16;
+        if (row < Mt && col < N) mine[(long long)row * N + col] = sq[tm][tn][r];
+      }
+}
+
+// Lam[e] += part_0[e] + part_1[e] + ... in group order: a thread per entry
+__global__ __launch_bounds__(256) void kfac_sqsum_fold_kernel(const double* __restrict__ part, int groups, long long E,
+                                                              double* __restrict__ Lam) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  double t = part[e];
+  for (int g = 1; g < groups; ++g) t += part[(long long)g * E + e];
+  Lam[e] += t;
+}
+
 }  // namespace lip
 
 using namespace lip;
@@ -352,6 +472,53 @@ int lip_kfac_predict(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_
     LIP_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(kfac_quad_kernel, dim3((unsigned)(nb * pairs)), dim3(256), 0, st, R, (const double*)T, (int)Kc, E, (int)b0,
                        (int)pairs, out, (int)diag);
+    LIP_CHECK_HIP(hipGetLastError());
+  }
+  return LIP_OK;
+}
+
+int lip_kfac_eigen_sqsum_scratch(int32_t R, int32_t Mt, int32_t N, int64_t* doubles) {
+  if (!doubles || !kfac_block_ok(R, 1, 0, Mt, N)) { set_error("lip_kfac_eigen_sqsum_scratch: bad argument"); return LIP_ERR_ARG; }
+  *doubles = ((long long)R + kfac_sq_plan(R, Mt, N).groups) * Mt * N;         // J Ub of every row and the groups' partial sums
+  return LIP_OK;
+}
+
+int lip_kfac_eigen_sqsum(const float* W, int64_t ldw, int32_t R, int64_t off, int32_t Mt, int32_t N, const double* V,
+                         const double* Ub, double* Lam, double* scratch, int64_t scratch_doubles, void* stream) {
+  if (!W || !V || !Ub || !Lam || !scratch || !kfac_block_ok(R, 1, off, Mt, N) || ldw < off + (long long)Mt * N) {
+    set_error("lip_kfac_eigen_sqsum: bad argument");
+    return LIP_ERR_ARG;
+  }
+  const long long E = (long long)Mt * N;
+  if (scratch_doubles < 2 * E) {
+    set_error("lip_kfac_eigen_sqsum: scratch of %lld doubles, at least %lld needed for one row (lip_kfac_eigen_sqsum_scratch: all rows)",
+              (long long)scratch_doubles, 2 * E);
+    return LIP_ERR_ARG;
+  }
+  const int MT32 = (Mt + 31) / 32;
+  if ((N + 127) / 128 > 65535) { set_error("lip_kfac_eigen_sqsum: N = %d is too large", (int)N); return LIP_ERR_ARG; }
+  // rows per chunk: all R in one chunk when the scratch holds them with their groups and stage one's grid does; else a
+  // chunk size under which every chunk, the shorter last one included, fits with its partial sums whatever its group
+  // count (never more groups than gmax, or than rows), within the 2^31 - 1 blocks of stage one
+  const long long avail = scratch_doubles / E, gmax = kfac_sq_max_groups(Mt, N), cap = 0x7fffffffll / std::max(Mt, 32);
+  long long Rc = R;
+  if (R > cap || avail < R + kfac_sq_plan(R, Mt, N).groups)
+    Rc = std::min(std::min<long long>(R, cap), avail > 2 * gmax ? avail - gmax : avail / 2);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned gy = (unsigned)((N + 127) / 128);
+  for (long long r0 = 0; r0 < R; r0 += Rc) {
+    const long long nb = std::min<long long>(Rc, R - r0), rows = nb * Mt;
+    const KfacSqPlan pl = kfac_sq_plan(nb, Mt, N);
+    double* JU = scratch;
+    double* part = scratch + nb * E;
+    hipLaunchKernelGGL(kfac_jub_kernel, dim3((unsigned)((rows + 31) / 32), gy), dim3(256), 0, st, W, (long long)ldw,
+                       (long long)off, (int)R, 1, (int)r0, rows, (int)Mt, (int)N, Ub, JU);
+    LIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kfac_sqsum_kernel, dim3((unsigned)MT32, gy, (unsigned)pl.groups), dim3(256), 0, st, V, (const double*)JU,
+                       (int)Mt, (int)N, nb, pl.nper, part);
+    LIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kfac_sqsum_fold_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, (const double*)part, pl.groups, E,
+                       Lam);
     LIP_CHECK_HIP(hipGetLastError());
   }
   return LIP_OK;

@@ -1034,6 +1034,36 @@ class LinearizedNet:
             self._kfac_predict_rows(Jr, b1 - b0, K, fits, rem, out[b0:b1], False)
         return out
 
+    def kfac_eigen_sqsums(self, bases, Lams: List[torch.Tensor], class_chunk: Optional[int] = None) -> List[torch.Tensor]:
+        """ADD Lam_l[j][m] += sum_i sum_k ((V_l^T mat_l(J_i^T L_i e_k) Ub_l)[j][m])^2 of this binding's examples into every
+        (Mt, N) float64 matrix of ``Lams``: the second moments of the per-example factor rows in the eigenbasis
+        ``bases[l] = (V, Ub)`` of every layer block (:meth:`kfac_blocks` order; contiguous float64 device matrices), what
+        EKFAC puts in place of KFAC's eigenvalue products.  One-hot probes on every example go through :meth:`vjp_rows`
+        ('l') in the class blocks of :meth:`_class_blocks`, each block's rows once for all layer blocks
+        (``lip_kfac_eigen_sqsum``; its scratch is capped by ``KFAC_SCRATCH_BYTES``, under which it chunks the rows)."""
+        blocks = self.kfac_blocks()
+        if len(bases) != len(blocks) or len(Lams) != len(blocks):
+            raise ValueError(f"{len(blocks)} layer blocks need {len(blocks)} (V, Ub) pairs in bases and {len(blocks)} matrices in Lams")
+        for b, (V, Ub), Lam in zip(blocks, bases, Lams):
+            for name, t, shape in (("V", V, (b.Mt, b.Mt)), ("Ub", Ub, (b.N, b.N)), ("Lam", Lam, (b.Mt, b.N))):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"{name} of the block at offset {b.off} must be a contiguous float64 device matrix of "
+                                     f"{shape[0]} x {shape[1]}")
+        for k0, k1 in self._class_blocks(class_chunk):
+            rows = self._one_hot_rows(k0, k1, "l")
+            R = (k1 - k0) * self.n
+            for b, (V, Ub), Lam in zip(blocks, bases, Lams):
+                doubles = C.c_int64(0)
+                nv.check(self.lib.lip_kfac_eigen_sqsum_scratch(R, b.Mt, b.N, C.byref(doubles)), "lip_kfac_eigen_sqsum_scratch")
+                # the doubles asked for, not the buffer's (it may have grown): the row chunks, and with them the order of
+                # the sums, depend on the binding alone
+                need = min(doubles.value, max(2 * b.Mt * b.N, self.KFAC_SCRATCH_BYTES // 8))
+                scratch = self._f64_scratch("lip_kfac_eigen_sqsum", need)
+                nv.check(self.lib.lip_kfac_eigen_sqsum(rows.data_ptr(), self.D, R, b.off, b.Mt, b.N, V.data_ptr(), Ub.data_ptr(),
+                                                       Lam.data_ptr(), scratch.data_ptr(), need, nv.stream_ptr()),
+                         "lip_kfac_eigen_sqsum")
+        return Lams
+
     # ------------------------------------------------------------------------------ measurement
     def profile(self, enable: bool):
         nv.check(self.lib.lip_engine_profile(self.h, int(enable)), "lip_engine_profile")

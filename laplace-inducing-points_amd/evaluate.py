@@ -147,16 +147,18 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
     ``"last_layer_kron"``: its Kronecker-factored twin without the size cap (``lla.predict_lla_last_layer_kron``),
     ``"subnetwork"``: the dense posterior over the flat-parameter indices ``indices`` (``lla.predict_lla_subnetwork``,
     fitted once for all batches; ``indices`` is read by this value alone), ``"kfac"``: the Kronecker-factored posterior
-    over all layers (``lla.predict_lla_kfac``, fitted once for all batches).
+    over all layers (``lla.predict_lla_kfac``, fitted once for all batches), ``"ekfac"``: its eigenvalue-corrected twin
+    (``lla.predict_lla_ekfac``, fitted once for all batches).
     -> (NLL, accuracy, Brier, ECE, probs, labels)"""
-    from .lla import (predict_lla_diag, predict_lla_kfac, predict_lla_last_layer, predict_lla_last_layer_kron, predict_lla_subnetwork,
-                      predict_lla_variances, probit_predictive)
+    from .lla import (predict_lla_diag, predict_lla_ekfac, predict_lla_kfac, predict_lla_last_layer, predict_lla_last_layer_kron,
+                      predict_lla_subnetwork, predict_lla_variances, probit_predictive)
     if posterior == "subnetwork" and indices is None:
         raise ValueError("posterior='subnetwork' needs indices")
     predict = {"diag": predict_lla_diag, "inducing": predict_lla_variances,
                "last_layer": lambda *a, **kw: predict_lla_last_layer(*a, cov="diag", **kw),
                "last_layer_kron": lambda *a, **kw: predict_lla_last_layer_kron(*a, cov="diag", **kw),
                "kfac": lambda *a, **kw: predict_lla_kfac(*a, cov="diag", **kw),
+               "ekfac": lambda *a, **kw: predict_lla_ekfac(*a, cov="diag", **kw),
                "subnetwork": lambda *a, **kw: predict_lla_subnetwork(*a, indices, cov="diag", **kw)}[posterior]
     all_probs, all_labels = [], []
     for x_b, y_b in dataloader:

@@ -277,6 +277,14 @@ def compute_kfac_factors(state, Z, model_type, example_chunk: Optional[int] = No
     return kfac.compute_kfac_factors(state, Z, model_type, example_chunk=example_chunk)
 
 
+def compute_ekfac_scales(state, Z, model_type, bases, example_chunk: Optional[int] = None,
+                         class_chunk: Optional[int] = None):
+    """``[Lam_l (Mt, N)]``: the second moments of the per-example factor rows in the Kronecker eigenbasis
+    ``bases[l] = (V_l, Ub_l)`` of every layer block, float64, unscaled (:func:`ekfac.compute_ekfac_scales`)."""
+    from . import ekfac
+    return ekfac.compute_ekfac_scales(state, Z, model_type, bases, example_chunk=example_chunk, class_chunk=class_chunk)
+
+
 def compute_ggn_subnetwork(state, Z, model_type, indices, full_set_size=None, example_chunk: Optional[int] = None) -> torch.Tensor:
     """The dense GGN block over the flat-parameter indices ``indices``, (S, S) float64, scaled like
     :func:`compute_ggn_vp` and chunked like :func:`compute_ggn_diag` (:func:`subnetwork.compute_ggn_subnetwork`)."""

@@ -174,11 +174,18 @@ def predict_lla_kfac(map_state, Xnew, Z, model_type, alpha, full_set_size=None, 
     Jacobian rows of ``lip_vjp_rows``), in the return shapes and types of
     :func:`last_layer_kron.predict_lla_last_layer_kron`.  ``batch`` test points are bound at a time, fewer for
     ``cov="full"`` when their (K, batch, D) float32 rows would exceed 2 GiB."""
-    from .distributions import MultivariateNormalFullCovariance
     if cov not in ("diag", "full"):
         raise ValueError("cov must be 'diag' or 'full'")
     _, fits, rem_idx, rem_var, _ = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
-    triples = [(V, R, Ub) for V, R, Ub, _, _, _ in fits]
+    return predictive_from_fit(map_state, Xnew, model_type, [(V, R, Ub) for V, R, Ub, _, _, _ in fits], (rem_idx, rem_var),
+                               cov, batch)
+
+
+def predictive_from_fit(map_state, Xnew, model_type, triples, rem, cov: str, batch: int):
+    """the predictive of :func:`predict_lla_kfac` from the (V, R, Ub) of every block and the remainder's
+    (indices, variances): :meth:`LinearizedNet.kfac_predict` on ``batch`` test points at a time"""
+    from .distributions import MultivariateNormalFullCovariance
+    rem_idx, rem_var = rem
     if cov == "full":
         D = flatten_nn_params(map_state.params)[0].numel()
         fit = (LinearizedNet.ROW_BLOCK_BYTES // (4 * D)) // int(map_state.net.num_outputs)
@@ -206,6 +213,11 @@ def predict_lla_kfac_scalable(map_state, Xnew, Z, model_type, alpha, key=None, f
     Jacobian rows per test point make the closed form of :func:`predict_lla_kfac` impractical there, while a draw costs
     one tangent-forward pass whatever K is."""
     post = posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=full_set_size, example_chunk=example_chunk)
+    return draws_from_posterior(post, map_state, Xnew, model_type, key, num_samples)
+
+
+def draws_from_posterior(post: KFACNormal, map_state, Xnew, model_type, key, num_samples) -> torch.Tensor:
+    """f(x; theta_MAP) + J(x) d_theta_s for ``num_samples`` seeded draws of ``post`` through the engine's JVP"""
     key = key if key is not None else 123
     d_theta = post.sample((num_samples,), seed=key, dtype=torch.float64) - post.mean()
     eng = _ggn.get_engine(map_state, Xnew, model_type, workspace_bytes=4 << 30)

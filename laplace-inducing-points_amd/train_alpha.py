@@ -170,6 +170,25 @@ def fit_alpha_kfac(X, state, model_type, full_set_size=None, alpha0: float = 1.0
     return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
+def log_marginal_likelihood_ekfac(alpha, X, state, model_type: str, full_set_size: Optional[int] = None) -> float:
+    """:func:`log_marginal_likelihood_kfac` under the eigenvalue-corrected curvature (``ekfac.py``): in the spectrum every
+    block's outer(lam_l, mu_l) / (M T_l) is replaced by the second moments of the factor rows in the block's orthonormal
+    Kronecker eigenbasis, which a scalar alpha does not move.  Scalar alpha.  Not a reference function."""
+    from .ekfac import _spectrum_ekfac
+    N = full_set_size or X.shape[0]
+    lam, D, theta2 = _spectrum_ekfac(X, state, model_type)
+    return _lml_from_spectrum(float(alpha), lam, D, theta2, N / X.shape[0])[0]
+
+
+def fit_alpha_ekfac(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200):
+    """:func:`fit_alpha` on the eigenvalue-corrected evidence: ``(alpha, history)``; the factors, their
+    eigendecompositions and the pass over the factor rows are computed once."""
+    from .ekfac import _spectrum_ekfac
+    N = full_set_size or X.shape[0]
+    lam, D, theta2 = _spectrum_ekfac(X, state, model_type)
+    return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
+
+
 def log_marginal_likelihood_subnetwork(alpha, X, state, model_type: str, indices, full_set_size: Optional[int] = None) -> float:
     """:func:`log_marginal_likelihood` of the subnetwork model (every parameter outside ``indices`` frozen): the spectrum
     is that of the dense subnetwork GGN (``subnetwork.compute_ggn_subnetwork`` at N/M = 1), D = |S| and
