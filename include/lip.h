@@ -270,6 +270,15 @@ int lip_gemm_nn_axpy(const float* T, int64_t ldt, int32_t m, int32_t k, const fl
  * G - (G Q) Q^T of :131.  Out must not alias Y or Z.                                                      */
 int lip_rows_combine(const double* Cm, const float* Y, int64_t ldy, int32_t s, const float* Z, int64_t ldz, float zscale,
                      float* Out, int64_t ldo, int32_t r, int64_t N, void* stream);
+/* out[d] += sum_{j<k} w[j] U[j][d]^2,  d < N: the weighted column square sums of the float32 rows U (k, N), row stride
+ * ldu >= N, in float64; w (k) float64 on the device or NULL (all ones); out (N) float64 is ADDED into.  The marginal
+ * variance of a low-rank posterior, diag(U^T diag(s) U), in one read of U and without a (k, N) temporary.  Every column
+ * is owned by one thread that takes the rows in ascending order (no atomics, no scratch): out0 + sum, the sum started at
+ * zero, each term one fused multiply-add of the exact square, so the result is bitwise reproducible and independent of
+ * the grid.  16-byte loads when ldu % 4 == 0 and U is 16-byte aligned, dword loads otherwise.  A null U / out,
+ * k or N <= 0 or ldu < N returns LIP_ERR_ARG and leaves out untouched.                                         */
+int lip_cols_wsqsum(const float* U, int64_t ldu, int32_t k, int64_t N, const double* w /*[k], NULL = ones*/,
+                    double* out /*[N], added into*/, void* stream);
 /* Last-layer Laplace: the dense GGN block over theta_L = [bias (K), kernel (F, K) row-major] of a final Dense layer,
  * from the penultimate features and the softmax probabilities alone (no backward sweep).  G (DL, DL) float64
  * row-major, DL = (F + 1) K, ADDED into (example chunks sum into one G):

@@ -97,6 +97,7 @@ SIGNATURES = {
                                    C.c_int64, _V]),
     "lip_rows_combine": (C.c_int, [_V, _V, C.c_int64, C.c_int32, _V, C.c_int64, C.c_float, _V, C.c_int64, C.c_int32,
                                    C.c_int64, _V]),
+    "lip_cols_wsqsum": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int64, _V, _V, _V]),
     "lip_ll_ggn": (C.c_int, [_V, C.c_int64, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int64, _V]),
     "lip_ll_ggn_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "lip_ll_predict": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int32, _V]),

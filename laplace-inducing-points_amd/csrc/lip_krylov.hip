@@ -570,6 +570,59 @@ __global__ __launch_bounds__(256) void rows_combine_kernel(const double* __restr
   }
 }
 
+// ---- out[d] += sum_j w[j] U[j][d]^2: the weighted column square sums of a (k, N) block of float32 rows, float64 — the
+// marginal variance of a low-rank posterior, diag(U^T diag(s) U), without the two (k, N) temporaries of (U * U) * s.
+// A thread owns VW adjacent columns and walks the rows in ascending order: the square of a float32 is exact in float64
+// and each term enters through one fused multiply-add, so the result does not depend on the grid and is bitwise
+// reproducible; out is read once, after the sum, and out0 + sum is rounded once.  CW_ROWS rows of loads are issued
+// before the first is used (k x 1 KiB per wave and row: the kernel is a pure HBM stream, 4 k N bytes read once).
+// VW = 4 takes 16-byte loads (base and row stride 16-byte aligned); VW = 1 is the dword path for any other layout.
+constexpr int CW_ROWS = 8;
+
+template <int VW>
+__global__ __launch_bounds__(KT) void cols_wsqsum_kernel(const float* __restrict__ U, long long ldu, int k, long long N,
+                                                         const double* __restrict__ w, double* __restrict__ out) {
+  const long long col = (long long)VW * ((long long)blockIdx.x * KT + threadIdx.x);
+  if (col >= N) return;
+  const int cnt = (N - col < VW) ? (int)(N - col) : VW;     // columns of this thread inside the block (a ragged last quad)
+  double acc[VW];
+#pragma unroll
+  for (int c = 0; c < VW; ++c) acc[c] = 0.0;
+  const float* src = U + col;
+  int j = 0;
+  if (cnt == VW) {
+    for (; j + CW_ROWS <= k; j += CW_ROWS) {
+      float v[CW_ROWS][VW];
+#pragma unroll
+      for (int t = 0; t < CW_ROWS; ++t) {
+        const float* p = src + (long long)(j + t) * ldu;
+        if constexpr (VW == 4) {
+          const float4 q = LD4(p, 0);
+          v[t][0] = q.x; v[t][1] = q.y; v[t][2] = q.z; v[t][3] = q.w;
+        } else {
+          v[t][0] = p[0];
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < CW_ROWS; ++t) {
+        const double wj = w ? w[j + t] : 1.0;
+#pragma unroll
+        for (int c = 0; c < VW; ++c) { const double x = (double)v[t][c]; acc[c] = fma(wj, x * x, acc[c]); }
+      }
+    }
+  }
+  for (; j < k; ++j) {                                      // the last k % CW_ROWS rows, and every row of a ragged quad
+    const float* p = src + (long long)j * ldu;
+    const double wj = w ? w[j] : 1.0;
+#pragma unroll
+    for (int c = 0; c < VW; ++c)
+      if (c < cnt) { const double x = (double)p[c]; acc[c] = fma(wj, x * x, acc[c]); }
+  }
+#pragma unroll
+  for (int c = 0; c < VW; ++c)
+    if (c < cnt) out[col + c] += acc[c];
+}
+
 // ---- counter-based RNG: Philox4x32-10, counter = flat element index / 4, key = seed ---------------------------
 __device__ __forceinline__ void philox4x32(unsigned long long ctr, unsigned long long key, unsigned int (&out)[4]) {
   unsigned int c0 = (unsigned int)ctr, c1 = (unsigned int)(ctr >> 32), c2 = 0x9E3779B9u, c3 = 0xBB67AE85u;
@@ -850,6 +903,24 @@ int lip_rows_combine(const double* Cm, const float* Y, int64_t ldy, int32_t s, c
     LIP_ROUTE("rows_combine<12>");
     hipLaunchKernelGGL((rows_combine_kernel<12>), dim3((unsigned)((r + 11) / 12), ny), dim3(256), sizeof(float) * 12 * s, st, Cm, Y,
                        (long long)ldy, s, Z, (long long)ldz, zscale, Out, (long long)ldo, r, (long long)N);
+  }
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_cols_wsqsum(const float* U, int64_t ldu, int32_t k, int64_t N, const double* w, double* out, void* stream) {
+  if (!U || !out || k <= 0 || N <= 0 || ldu < N) { set_error("lip_cols_wsqsum: bad argument"); return LIP_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const bool quads = (ldu % 4 == 0) && ((((unsigned long long)U) & 15ull) == 0);
+  const long long per_block = (long long)KT * (quads ? 4 : 1);
+  const long long blocks = (N + per_block - 1) / per_block;
+  if (blocks > 0x7fffffffll) { set_error("lip_cols_wsqsum: N = %lld is too large", (long long)N); return LIP_ERR_ARG; }
+  if (quads) {
+    LIP_ROUTE("cols_wsqsum<4>");
+    hipLaunchKernelGGL((cols_wsqsum_kernel<4>), dim3((unsigned)blocks), dim3(KT), 0, st, U, (long long)ldu, k, (long long)N, w, out);
+  } else {
+    LIP_ROUTE("cols_wsqsum<1>");
+    hipLaunchKernelGGL((cols_wsqsum_kernel<1>), dim3((unsigned)blocks), dim3(KT), 0, st, U, (long long)ldu, k, (long long)N, w, out);
   }
   LIP_CHECK_HIP(hipGetLastError());
   return LIP_OK;

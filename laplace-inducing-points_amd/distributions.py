@@ -13,6 +13,10 @@ the sizes a diagonal posterior is used for.
 
 ``KFACNormal`` (not in the reference) is the Gaussian over the whole flat vector that ``posterior_lla_kfac`` returns: one
 ``KroneckerNormal`` per layer block and independent variances for the parameters outside every block.
+
+``LowRankNormal`` (not in the reference) is the Gaussian over the whole flat vector that ``posterior_lla_lowrank``
+returns: the prior plus the leading eigenpairs of the whitened GGN in the precision, every other direction at the prior
+variance.
 """
 from __future__ import annotations
 
@@ -198,3 +202,126 @@ class KFACNormal:
             E = torch.randn(shape + (idx.numel(),), dtype=var.dtype, device=var.device, generator=g)
             out[..., idx] = (self.loc[idx].to(var.dtype) + torch.sqrt(var) * E).to(dtype)
         return out
+
+
+class LowRankNormal:
+    """N(loc, S) over the whole flat parameter vector (D,) with a diagonal-plus-low-rank precision: with the prior
+    A0 = alpha I or diag(a), orthonormal rows ``Ut`` (r, D) and whitened eigenvalues ``lam_t`` (r,) >= 0 (the leading
+    eigenpairs of A0^(-1/2) G A0^(-1/2); for a scalar prior recal lam / alpha with the eigenvectors of G itself),
+
+        S^-1 = A0^(1/2) (I + Ut^T diag(lam_t) Ut) A0^(1/2),
+        S    = A0^(-1/2) (I - Ut^T diag(s) Ut) A0^(-1/2),    s_j = lam_t_j / (1 + lam_t_j).
+
+    Every direction outside span(Ut) keeps the prior variance, so truncating the spectrum over-states the variance: it
+    never under-states it relative to the posterior that more of the same Ritz pairs would give, because every further
+    pair only subtracts a positive semi-definite term.
+
+    ``prior`` is a number (alpha) or a (D,) vector of precisions.  On CUDA ``Ut`` is float32 and the (r, D) passes are the
+    HIP primitives of ``krylov.py``: ``cols_wsqsum`` for the marginal variance, ``dot_nt`` / ``gemm_nt`` and
+    ``gemm_nn_axpy`` / ``rows_combine`` for the draws and the covariance products.  CPU tensors (float64 in the tests)
+    run the same algebra in plain torch."""
+
+    STIFF = 250.0          # sqrt(1 + lam_t) above which a draw's coefficient is accumulated in float64 (``sample.py``)
+
+    def __init__(self, loc: torch.Tensor, Ut: torch.Tensor, lam_t: torch.Tensor, prior):
+        D = loc.shape[-1]
+        if Ut.dim() != 2 or Ut.shape[1] != D or lam_t.shape != (Ut.shape[0],):
+            raise ValueError(f"Ut {tuple(Ut.shape)}, lam_t {tuple(lam_t.shape)} and loc {tuple(loc.shape)} do not describe "
+                             f"r eigenpairs over {D} parameters")
+        self.loc, self.Ut = loc, Ut
+        self.lam_t = lam_t.to(device=loc.device, dtype=torch.float64).clamp_min(0.0)
+        if torch.is_tensor(prior) and prior.dim() > 0:
+            if prior.numel() != D:
+                raise ValueError(f"the prior holds {prior.numel()} precisions for {D} parameters")
+            self.a = prior.to(device=loc.device, dtype=torch.float64).reshape(-1)
+            if not bool((self.a > 0).all()):
+                raise ValueError("the prior precisions must be positive")
+            self.isq = self.a.rsqrt().to(Ut.dtype)
+        else:
+            self.a = float(prior)
+            if not self.a > 0:
+                raise ValueError("the prior precision must be positive")
+            self.isq = self.a ** -0.5
+        self.s = self.lam_t / (1.0 + self.lam_t)
+        root = torch.sqrt(1.0 + self.lam_t)
+        self.g = -self.lam_t / (root * (1.0 + root))        # (1 + lam_t)^(-1/2) - 1 without the cancellation
+        self.n_stiff = int(min(96, int((root > self.STIFF).sum())))      # lam_t descends: the stiff rows come first
+
+    def _hip(self) -> bool:
+        return self.Ut.is_cuda and self.Ut.dtype == torch.float32
+
+    def mean(self) -> torch.Tensor:
+        return self.loc
+
+    def spectrum(self) -> torch.Tensor:
+        """the whitened eigenvalues lam_t (r,), float64: the posterior precision is A0^(1/2) (I + Ut^T diag(lam_t) Ut) A0^(1/2)"""
+        return self.lam_t
+
+    def log_det_precision_ratio(self) -> torch.Tensor:
+        """log det(prior^-1 posterior precision) = sum_j log1p(lam_t_j)"""
+        return torch.log1p(self.lam_t).sum()
+
+    def variance(self) -> torch.Tensor:
+        """diag(S)_d = (1 - sum_j s_j Ut[j, d]^2) / a_d, (D,) float64 (``lip_cols_wsqsum`` on float32 device rows: one read
+        of Ut, no (r, D) temporary)"""
+        if self.Ut.shape[0] == 0:
+            q = torch.zeros_like(self.loc, dtype=torch.float64)
+        elif self._hip():
+            from . import krylov
+            q = krylov.cols_wsqsum(self.Ut, self.s)
+        else:
+            q = (self.s[:, None] * self.Ut.double() ** 2).sum(0)
+        return (1.0 - q) / self.a
+
+    def stddev(self) -> torch.Tensor:
+        return torch.sqrt(self.variance())
+
+    def _combine(self, X: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+        """X + (C o coef) Ut with C = X Ut^T, for rows X (P, D) of Ut's dtype; X is overwritten where the kernels allow"""
+        if self.Ut.shape[0] == 0:
+            return X
+        if not self._hip():
+            return X + ((X @ self.Ut.T) * coef.to(X.dtype)) @ self.Ut
+        from . import krylov
+        X = X.contiguous()
+        if X.shape[0] < 32:
+            C = krylov.dot_nt(X, self.Ut)
+        else:
+            C = krylov.gemm_nt(X, self.Ut).double()
+            if self.n_stiff:
+                C[:, :self.n_stiff] = krylov.dot_nt(X, self.Ut[:self.n_stiff])
+        return krylov.gemm_nn_axpy((C * coef).float().contiguous(), self.Ut, X, 1.0, out=X)
+
+    def cov_vp(self, V: torch.Tensor) -> torch.Tensor:
+        """S V for a vector (D,) or the rows of a block (P, D), in Ut's dtype"""
+        single = V.dim() == 1
+        X = (V[None] if single else V).to(device=self.Ut.device, dtype=self.Ut.dtype) * self.isq
+        out = self._combine(X, -self.s) * self.isq
+        return out[0] if single else out
+
+    def sample_map(self, eps: torch.Tensor) -> torch.Tensor:
+        """the exact linear map of the draws, rows eps (S, D) -> A0^(-1/2) (eps + Ut^T (g o (Ut eps))), whose covariance
+        under standard-normal eps is S: (I + Ut^T diag(g) Ut)^2 = I - Ut^T diag(s) Ut.  ``eps`` may be overwritten."""
+        return self._combine(eps, self.g) * self.isq
+
+    def sample(self, sample_shape=(), seed=None, dtype=None) -> torch.Tensor:
+        """draws (sample_shape + (D,)): loc + A0^(-1/2) (eps + Ut^T (g o (Ut eps))), g_j = -lam_t_j / (sqrt(1 + lam_t_j)
+        (1 + sqrt(1 + lam_t_j))); two passes over Ut per block of draws.  On the device eps is ``fill_normal(seed)`` and
+        the draws are float32 unless ``dtype`` says otherwise; on the CPU a seeded torch generator in Ut's dtype."""
+        if isinstance(sample_shape, int):
+            sample_shape = (sample_shape,)
+        shape = tuple(sample_shape)
+        S = 1
+        for n in shape:
+            S *= int(n)
+        D = self.loc.shape[-1]
+        if self._hip():
+            from . import krylov
+            eps = krylov.fill_normal(S, D, 0 if seed is None else int(seed), device=self.Ut.device)
+        else:
+            g = None
+            if seed is not None:
+                g = torch.Generator(device=self.Ut.device).manual_seed(int(seed))
+            eps = torch.randn(S, D, dtype=self.Ut.dtype, device=self.Ut.device, generator=g)
+        dtype = dtype or eps.dtype
+        return (self.loc.to(dtype) + self.sample_map(eps).to(dtype)).reshape(shape + (D,))

@@ -139,7 +139,7 @@ def auroc_ood(state, id_probs: torch.Tensor, ood_loader: Iterable, Z, alpha, ful
 
 
 def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, model_type="classifier",
-                        posterior: str = "diag", indices=None):
+                        posterior: str = "diag", indices=None, rank=None):
     """:func:`eval_dataset_extended` without draws: the class probabilities are the probit predictive
     (``lla.probit_predictive``) of the closed-form output variances — ``posterior="diag"``: the diagonal Laplace
     posterior (``lla.predict_lla_diag``), ``"inducing"``: the inducing-point posterior (``lla.predict_lla_variances``),
@@ -148,10 +148,13 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
     ``"subnetwork"``: the dense posterior over the flat-parameter indices ``indices`` (``lla.predict_lla_subnetwork``,
     fitted once for all batches; ``indices`` is read by this value alone), ``"kfac"``: the Kronecker-factored posterior
     over all layers (``lla.predict_lla_kfac``, fitted once for all batches), ``"ekfac"``: its eigenvalue-corrected twin
-    (``lla.predict_lla_ekfac``, fitted once for all batches).
+    (``lla.predict_lla_ekfac``, fitted once for all batches), ``"lowrank"``: the low-rank posterior from the ``rank``
+    leading eigenpairs of the GGN of Z (``lla.predict_lla_lowrank``, fitted once for all batches; ``rank`` is read by this
+    value alone, ``None``: ``lowrank.DEFAULT_RANK``).
     -> (NLL, accuracy, Brier, ECE, probs, labels)"""
     from .lla import (predict_lla_diag, predict_lla_ekfac, predict_lla_kfac, predict_lla_last_layer, predict_lla_last_layer_kron,
-                      predict_lla_subnetwork, predict_lla_variances, probit_predictive)
+                      predict_lla_lowrank, predict_lla_subnetwork, predict_lla_variances, probit_predictive)
+    rank_kw = {} if rank is None else {"rank": rank}
     if posterior == "subnetwork" and indices is None:
         raise ValueError("posterior='subnetwork' needs indices")
     predict = {"diag": predict_lla_diag, "inducing": predict_lla_variances,
@@ -159,6 +162,7 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
                "last_layer_kron": lambda *a, **kw: predict_lla_last_layer_kron(*a, cov="diag", **kw),
                "kfac": lambda *a, **kw: predict_lla_kfac(*a, cov="diag", **kw),
                "ekfac": lambda *a, **kw: predict_lla_ekfac(*a, cov="diag", **kw),
+               "lowrank": lambda *a, **kw: predict_lla_lowrank(*a, cov="diag", **rank_kw, **kw),
                "subnetwork": lambda *a, **kw: predict_lla_subnetwork(*a, indices, cov="diag", **kw)}[posterior]
     all_probs, all_labels = [], []
     for x_b, y_b in dataloader:

@@ -285,6 +285,13 @@ def compute_ekfac_scales(state, Z, model_type, bases, example_chunk: Optional[in
     return ekfac.compute_ekfac_scales(state, Z, model_type, bases, example_chunk=example_chunk, class_chunk=class_chunk)
 
 
+def compute_ggn_lowrank(state, Z, model_type, rank, prior=None, example_chunk: Optional[int] = None, **solver):
+    """``(lam (r,), U (r, D), info)``: the ``rank`` leading eigenpairs of the (prior-whitened) GGN summed over the examples
+    of Z at N/M = 1, by randomized block subspace iteration on the GGN-vector product (:func:`lowrank.compute_ggn_lowrank`)."""
+    from . import lowrank
+    return lowrank.compute_ggn_lowrank(state, Z, model_type, rank, prior=prior, example_chunk=example_chunk, **solver)
+
+
 def compute_ggn_subnetwork(state, Z, model_type, indices, full_set_size=None, example_chunk: Optional[int] = None) -> torch.Tensor:
     """The dense GGN block over the flat-parameter indices ``indices``, (S, S) float64, scaled like
     :func:`compute_ggn_vp` and chunked like :func:`compute_ggn_diag` (:func:`subnetwork.compute_ggn_subnetwork`)."""

@@ -586,3 +586,8 @@ def cg_deflated(A: Callable, B: torch.Tensor, defl: RangeDeflation, **cg_kw):
     Xp = defl.project_out(Xp)                       # what the recurrence let leak back into range(Q)
     X = axpby(defl.range_part(C, lambda lam: 1.0 / lam), Xp, None, 1.0, None, 1.0)
     return X, info
+
+
+# the eigen-solver and its streaming primitive live in ``subspace.py`` (drivers of this module's drivers); they are part
+# of this module's surface: ``krylov.top_eigenpairs``, ``krylov.cols_wsqsum``
+from .subspace import cols_wsqsum, top_eigenpairs  # noqa: E402,F401

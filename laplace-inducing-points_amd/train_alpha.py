@@ -189,6 +189,27 @@ def fit_alpha_ekfac(X, state, model_type, full_set_size=None, alpha0: float = 1.
     return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
+def log_marginal_likelihood_lowrank(alpha, X, state, model_type: str, full_set_size: Optional[int] = None, rank: Optional[int] = None,
+                                    example_chunk: Optional[int] = None, **solver) -> float:
+    """:func:`log_marginal_likelihood` under the low-rank curvature (``lowrank.py``): the spectrum is the ``rank`` leading
+    eigenvalues of the GGN of X from the matrix-free fit (``lowrank.DEFAULT_RANK`` when not given), every other direction
+    flat; D and ||theta||^2 are those of the whole vector.  A scalar alpha does not move the eigenpairs, so one cached fit
+    serves every alpha.  Scalar alpha.  Not a reference function."""
+    from .lowrank import DEFAULT_RANK, _spectrum_lowrank
+    N = full_set_size or X.shape[0]
+    lam, D, theta2 = _spectrum_lowrank(X, state, model_type, rank or DEFAULT_RANK, example_chunk, **solver)
+    return _lml_from_spectrum(float(alpha), lam, D, theta2, N / X.shape[0])[0]
+
+
+def fit_alpha_lowrank(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200,
+                      rank: Optional[int] = None, example_chunk: Optional[int] = None, **solver):
+    """:func:`fit_alpha` on the low-rank evidence: ``(alpha, history)``; the eigenpairs are computed once."""
+    from .lowrank import DEFAULT_RANK, _spectrum_lowrank
+    N = full_set_size or X.shape[0]
+    lam, D, theta2 = _spectrum_lowrank(X, state, model_type, rank or DEFAULT_RANK, example_chunk, **solver)
+    return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
+
+
 def log_marginal_likelihood_subnetwork(alpha, X, state, model_type: str, indices, full_set_size: Optional[int] = None) -> float:
     """:func:`log_marginal_likelihood` of the subnetwork model (every parameter outside ``indices`` frozen): the spectrum
     is that of the dense subnetwork GGN (``subnetwork.compute_ggn_subnetwork`` at N/M = 1), D = |S| and
