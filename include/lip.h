@@ -422,6 +422,18 @@ int lip_kfac_eigen_sqsum(const float* W, int64_t ldw, int32_t R, int64_t off, in
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
+/* Monte-Carlo Fisher head cotangents: for sample s < S and example i < n of the softmax rows probs (n, K), draw a class
+ * yhat ~ p_i and write U[s][i][k] = (k == yhat ? 1 : 0) - p_i[k] (one float32 subtraction), labels[s][i] = yhat when
+ * labels is not null.  U is (S, n, K) row-major and is overwritten.  The draw is defined in integers, so it does not
+ * depend on the launch geometry and a host can replay it: q_k = floor((double)p_i[k] * 2^40) as a 64-bit unsigned
+ * integer, pre_k = q_0 + ... + q_k, Q = pre_{K-1} (Q = 0 for a row with an entry outside [0, 1], NaN included); Philox4x32-10
+ * with the counter words (g, s, 0x9E3779B9, 0xBB67AE85), g = example_offset + i, keyed by the two words of seed (the
+ * generator of lip_fill_normal) gives w0..w3; t = mulhi64((w1 << 32) | w0, Q); yhat = min{k : pre_k > t}, so a class
+ * with q_k = 0 is never drawn.  A row with Q = 0 gets label -1 and the row -p_i.  Sampling the rows [a, b) of a block
+ * with example_offset = a gives the rows [a, b) of the draw of the whole block.  A null probs / U, n < 1, S < 1, K < 1,
+ * K > 8192, example_offset < 0 or example_offset + n > 2^32 returns LIP_ERR_ARG and writes nothing. */
+int lip_head_sample(const float* probs, int32_t n, int32_t K, int32_t S, uint64_t seed, int64_t example_offset, float* U,
+                    int32_t* labels, void* stream);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,7 @@ SIGNATURES = {
                                        _V]),
     "lip_fill_rademacher": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_fill_normal": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
+    "lip_head_sample": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _V, _V, _V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -704,6 +704,103 @@ __global__ __launch_bounds__(KT) void fill_rademacher_kernel(float* X, long long
   }
 }
 
+// ---- Monte-Carlo Fisher head cotangents: U[s][i] = e_yhat - p_i, yhat ~ p_i drawn in integers -------------------
+// One block per example.  The row p_i sits in LDS ([K] floats); thread t owns the classes [t L, (t + 1) L), L =
+// ceil(K / NT), and the block scans the 64-bit sums of q_k = floor(p_k 2^40) over those segments.  A draw is one Philox
+// call at counter (s << 32) | g, t = mulhi64(w1:w0, Q), a binary search for the segment whose inclusive prefix exceeds t
+// and a walk of at most L classes inside it: min{k : pre_k > t} whatever NT is.  Each round of NT draws is then streamed
+// out as NT rows of U, coalesced along k (16-byte stores when VEC).  A row with an entry outside [0, 1] (non-finite
+// included) is no distribution and counts as Q = 0; a row with Q = 0 gets label -1 and the row -p.
+__device__ __forceinline__ unsigned long long head_q(float p) {
+  return (p > 0.f && p <= 1.f) ? (unsigned long long)((double)p * 1099511627776.0) : 0ull;   // exact: a power-of-two scaling
+}
+
+template <int NT, bool VEC>
+__global__ __launch_bounds__(NT) void head_sample_kernel(const float* __restrict__ probs, int n, int K, int S,
+                                                         unsigned long long seed, unsigned long long g0,
+                                                         float* __restrict__ U, int* __restrict__ labels) {
+  extern __shared__ __attribute__((aligned(16))) float hs_p[];   // [K] (rounded up to a quad)
+  __shared__ unsigned long long seg[2][NT];
+  __shared__ int lab[NT];
+  const int i = blockIdx.x, t = threadIdx.x;
+  const float* prow = probs + (long long)i * K;
+  for (int k = t; k < K; k += NT) hs_p[k] = prow[k];
+  __syncthreads();
+  const int L = (K + NT - 1) / NT;
+  const int k_lo = min(t * L, K), k_hi = min(k_lo + L, K);
+  unsigned long long mine = 0;
+  int bad = 0;
+  for (int k = k_lo; k < k_hi; ++k) {
+    const float p = hs_p[k];
+    bad |= !(p >= 0.f && p <= 1.f);
+    mine += head_q(p);
+  }
+  seg[0][t] = mine;
+  bad = __syncthreads_or(bad);
+  int cur = 0;
+#pragma unroll
+  for (int off = 1; off < NT; off <<= 1) {                       // inclusive scan of the segment sums
+    const unsigned long long v = seg[cur][t] + (t >= off ? seg[cur][t - off] : 0ull);
+    seg[cur ^ 1][t] = v;
+    __syncthreads();
+    cur ^= 1;
+  }
+  const unsigned long long* inc = seg[cur];
+  const unsigned long long Q = bad ? 0ull : inc[NT - 1];
+  const unsigned long long g = g0 + (unsigned long long)i;
+  const long long sstride = (long long)n * K;                    // floats between two samples of one example
+  for (int s0 = 0; s0 < S; s0 += NT) {
+    const int s = s0 + t;
+    if (s < S) {
+      int y = -1;
+      if (Q != 0ull) {
+        unsigned int w[4];
+        philox4x32(((unsigned long long)s << 32) | g, seed, w);
+        const unsigned long long r = ((unsigned long long)w[1] << 32) | w[0];
+        const unsigned long long tv = __umul64hi(r, Q);          // < Q
+        int lo = 0, hi = NT - 1;                                 // min{j : inc[j] > tv}; inc[NT - 1] = Q > tv
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (inc[mid] > tv) hi = mid; else lo = mid + 1;
+        }
+        unsigned long long acc = lo ? inc[lo - 1] : 0ull;
+        const int a = min(lo * L, K), b = min(a + L, K);
+        y = b - 1;                                               // reached only if the walk below does not stop (it does)
+        for (int k = a; k < b; ++k) {
+          acc += head_q(hs_p[k]);
+          if (acc > tv) { y = k; break; }
+        }
+      }
+      lab[t] = y;
+      if (labels) labels[(long long)s * n + i] = y;
+    }
+    __syncthreads();
+    const int R = min(NT, S - s0);
+    float* base = U + ((long long)s0 * n + i) * K;
+    if (VEC) {
+      const unsigned KQ = (unsigned)K >> 2, total = (unsigned)R * KQ;
+      for (unsigned e = t; e < total; e += NT) {
+        const unsigned rr = e / KQ, k = (e - rr * KQ) << 2;
+        const int y = lab[rr];
+        const float4 p4 = *reinterpret_cast<const float4*>(hs_p + k);
+        float4 o;
+        o.x = ((int)k == y ? 1.f : 0.f) - p4.x;
+        o.y = ((int)k + 1 == y ? 1.f : 0.f) - p4.y;
+        o.z = ((int)k + 2 == y ? 1.f : 0.f) - p4.z;
+        o.w = ((int)k + 3 == y ? 1.f : 0.f) - p4.w;
+        ST4(base + (long long)rr * sstride, k, o);
+      }
+    } else {
+      const unsigned total = (unsigned)R * (unsigned)K;
+      for (unsigned e = t; e < total; e += NT) {
+        const unsigned rr = e / (unsigned)K, k = e - rr * (unsigned)K;
+        base[(long long)rr * sstride + k] = ((int)k == lab[rr] ? 1.f : 0.f) - hs_p[k];
+      }
+    }
+    __syncthreads();                                             // lab is rewritten by the next round
+  }
+}
+
 static inline unsigned nblk_for(long long N, long long per_block, unsigned cap) {
   long long b = (N + per_block - 1) / per_block;
   if (b < 1) b = 1;
@@ -942,6 +1039,33 @@ int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream)
   LIP_ROUTE("fill_normal");
   hipLaunchKernelGGL((fill_kernel<true>), dim3(nblk_for(total, KT * 16, 8192)), dim3(KT), 0, (hipStream_t)stream, X, total,
                      (unsigned long long)seed);
+  LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_head_sample(const float* probs, int32_t n, int32_t K, int32_t S, uint64_t seed, int64_t example_offset, float* U,
+                    int32_t* labels, void* stream) {
+  if (!probs || !U || n < 1 || S < 1 || K < 1 || K > 8192) {
+    set_error("lip_head_sample: bad argument (null probs / U, n < 1, S < 1 or K outside 1..8192)");
+    return LIP_ERR_ARG;
+  }
+  if (example_offset < 0 || example_offset + (int64_t)n > (1ll << 32)) {
+    set_error("lip_head_sample: bad argument (example_offset %lld with n = %d leaves 0 .. 2^32)", (long long)example_offset, n);
+    return LIP_ERR_ARG;
+  }
+  const bool vec = (K & 3) == 0 && (((unsigned long long)U) & 15ull) == 0;   // then every row of U is 16-byte aligned
+  const size_t shmem = (size_t)((K + 3) & ~3) * sizeof(float);
+  const hipStream_t st = (hipStream_t)stream;
+  const unsigned long long g0 = (unsigned long long)example_offset;
+  with_flag(vec, [&](auto v) {
+    constexpr bool VEC = decltype(v)::value;
+    if (K <= 256)
+      hipLaunchKernelGGL((head_sample_kernel<64, VEC>), dim3((unsigned)n), dim3(64), shmem, st, probs, n, K, S,
+                         (unsigned long long)seed, g0, U, labels);
+    else
+      hipLaunchKernelGGL((head_sample_kernel<KT, VEC>), dim3((unsigned)n), dim3(KT), shmem, st, probs, n, K, S,
+                         (unsigned long long)seed, g0, U, labels);
+  });
   LIP_CHECK_HIP(hipGetLastError());
   return LIP_OK;
 }

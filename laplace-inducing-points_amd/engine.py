@@ -923,10 +923,13 @@ class LinearizedNet:
                                                   scratch.numel(), nv.stream_ptr()), "lip_kfac_input_gram")
         return As
 
-    def kfac_output_grams(self, Ss: List[torch.Tensor], class_chunk: Optional[int] = None) -> List[torch.Tensor]:
+    def kfac_output_grams(self, Ss: List[torch.Tensor], class_chunk: Optional[int] = None,
+                          probes: Optional[torch.Tensor] = None, divisor: float = 1.0) -> List[torch.Tensor]:
         """ADD S_l += sum_i sum_t sum_k g_{i,t,k} g_{i,t,k}^T into every (N, N) float64 matrix of ``Ss``: one
         ``lip_vjp_kron`` sweep ('l') over the one-hot probes, in the class blocks of :meth:`_class_blocks`; the frozen BN
-        scale s s^T o S_l is applied here, in float64, to this binding's sums before they are added."""
+        scale s s^T o S_l is applied here, in float64, to this binding's sums before they are added.  ``probes``: a raw
+        (P, n, K) block of head cotangents swept instead ('raw'), in probe chunks under the same byte cap, its sums divided by
+        ``divisor`` before they are added (``fisher.py``)."""
         blocks = self.kfac_blocks()
         cap = len(blocks)
         koff, ooff, Ns = (C.c_int64 * cap)(), (C.c_int64 * cap)(), (C.c_int32 * cap)()
@@ -936,13 +939,20 @@ class LinearizedNet:
         if count.value != cap or any(b.kernel_off not in where or where[b.kernel_off][1] != b.N for b in blocks):
             raise nv.NativeError("lip_vjp_kron_layout: the backward tape's weight gradients do not match the layer blocks")
         buf = torch.zeros(total.value, device=self.device, dtype=torch.float64)
-        eye = torch.eye(self.K, device=self.device, dtype=torch.float32)
-        for k0, k1 in self._class_blocks(class_chunk):
+        if probes is None:
+            eye = torch.eye(self.K, device=self.device, dtype=torch.float32)
+            sweeps = ((eye[k0:k1, None, :].expand(k1 - k0, self.n, self.K).contiguous(), nv.HEAD_L)
+                      for k0, k1 in self._class_blocks(class_chunk))
+        else:
+            Ub, head = self._cotangents(probes, "raw")
+            pc = max(1, (self.ROW_BLOCK_BYTES // (4 * self.D)) // self.n)        # the cap of _class_blocks, not cut at K
+            pc = pc if class_chunk is None else max(1, min(pc, int(class_chunk)))
+            sweeps = ((Ub[p0:p0 + pc], head) for p0 in range(0, Ub.shape[0], pc))
+        for E, head in sweeps:
             doubles = C.c_int64(0)                     # for the probes this call passes: the need is not monotone in them
-            nv.check(self.lib.lip_vjp_kron_scratch(self.h, k1 - k0, C.byref(doubles)), "lip_vjp_kron_scratch")
+            nv.check(self.lib.lip_vjp_kron_scratch(self.h, E.shape[0], C.byref(doubles)), "lip_vjp_kron_scratch")
             scratch = self._f64_scratch("lip_vjp_kron", doubles.value)
-            E = eye[k0:k1, None, :].expand(k1 - k0, self.n, self.K).contiguous()
-            nv.check(self.lib.lip_vjp_kron(self.h, nv.ptr(E), buf.data_ptr(), k1 - k0, nv.HEAD_L, 1.0, scratch.data_ptr(),
+            nv.check(self.lib.lip_vjp_kron(self.h, nv.ptr(E), buf.data_ptr(), E.shape[0], head, 1.0, scratch.data_ptr(),
                                            scratch.numel(), nv.stream_ptr()), "lip_vjp_kron")
         for b, S in zip(blocks, Ss):
             o, N = where[b.kernel_off]
@@ -950,12 +960,16 @@ class LinearizedNet:
             if b.bn is not None:
                 s = self.consts[b.bn[0]:b.bn[0] + N].double()
                 part = part * (s[:, None] * s[None, :])            # the outer product first: exactly symmetric
+            if probes is not None and divisor != 1.0:
+                part = part / float(divisor)
             S += part
         return Ss
 
-    def kfac_factors(self, As: List[torch.Tensor], Ss: List[torch.Tensor], class_chunk: Optional[int] = None):
+    def kfac_factors(self, As: List[torch.Tensor], Ss: List[torch.Tensor], class_chunk: Optional[int] = None,
+                     probes: Optional[torch.Tensor] = None, divisor: float = 1.0):
         """ADD this binding's examples into the Kronecker factors of every layer block (:meth:`kfac_blocks` order):
-        ``As[l]`` (Mt, Mt) and ``Ss[l]`` (N, N), contiguous float64 device matrices; unscaled."""
+        ``As[l]`` (Mt, Mt) and ``Ss[l]`` (N, N), contiguous float64 device matrices; unscaled.  ``probes`` / ``divisor``
+        go to :meth:`kfac_output_grams`; the input factors do not depend on them."""
         blocks = self.kfac_blocks()
         if len(As) != len(blocks) or len(Ss) != len(blocks):
             raise ValueError(f"{len(blocks)} layer blocks need {len(blocks)} matrices in As and in Ss")
@@ -965,7 +979,7 @@ class LinearizedNet:
                     raise ValueError(f"{name} of the block at offset {b.off} must be a contiguous float64 device matrix of "
                                      f"{d} x {d}")
         self.kfac_input_grams(As)
-        self.kfac_output_grams(Ss, class_chunk=class_chunk)
+        self.kfac_output_grams(Ss, class_chunk=class_chunk, probes=probes, divisor=divisor)
         return As, Ss
 
     def _kfac_predict_rows(self, rows: torch.Tensor, B: int, Kc: int, fits, rem, out: torch.Tensor, diag: bool) -> None:

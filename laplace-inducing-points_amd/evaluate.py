@@ -139,7 +139,7 @@ def auroc_ood(state, id_probs: torch.Tensor, ood_loader: Iterable, Z, alpha, ful
 
 
 def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, model_type="classifier",
-                        posterior: str = "diag", indices=None, rank=None):
+                        posterior: str = "diag", indices=None, rank=None, *, curvature=None):
     """:func:`eval_dataset_extended` without draws: the class probabilities are the probit predictive
     (``lla.probit_predictive``) of the closed-form output variances — ``posterior="diag"``: the diagonal Laplace
     posterior (``lla.predict_lla_diag``), ``"inducing"``: the inducing-point posterior (``lla.predict_lla_variances``),
@@ -150,11 +150,17 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
     over all layers (``lla.predict_lla_kfac``, fitted once for all batches), ``"ekfac"``: its eigenvalue-corrected twin
     (``lla.predict_lla_ekfac``, fitted once for all batches), ``"lowrank"``: the low-rank posterior from the ``rank``
     leading eigenpairs of the GGN of Z (``lla.predict_lla_lowrank``, fitted once for all batches; ``rank`` is read by this
-    value alone, ``None``: ``lowrank.DEFAULT_RANK``).
+    value alone, ``None``: ``lowrank.DEFAULT_RANK``).  ``curvature``: a spec of ``fisher.py`` for the fit of
+    ``posterior="diag"`` and ``"kfac"``; the other posteriors refuse one.
     -> (NLL, accuracy, Brier, ECE, probs, labels)"""
     from .lla import (predict_lla_diag, predict_lla_ekfac, predict_lla_kfac, predict_lla_last_layer, predict_lla_last_layer_kron,
                       predict_lla_lowrank, predict_lla_subnetwork, predict_lla_variances, probit_predictive)
     rank_kw = {} if rank is None else {"rank": rank}
+    curv_kw = {}
+    if curvature is not None:
+        if posterior not in ("diag", "kfac"):
+            raise ValueError(f"curvature is taken by posterior='diag' and 'kfac' only, not {posterior!r}")
+        curv_kw = {"curvature": curvature}
     if posterior == "subnetwork" and indices is None:
         raise ValueError("posterior='subnetwork' needs indices")
     predict = {"diag": predict_lla_diag, "inducing": predict_lla_variances,
@@ -166,7 +172,7 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
                "subnetwork": lambda *a, **kw: predict_lla_subnetwork(*a, indices, cov="diag", **kw)}[posterior]
     all_probs, all_labels = [], []
     for x_b, y_b in dataloader:
-        probs = probit_predictive(*predict(state, x_b, Z, model_type, alpha, full_set_size=full_set_size))
+        probs = probit_predictive(*predict(state, x_b, Z, model_type, alpha, full_set_size=full_set_size, **curv_kw))
         all_probs.append(probs)
         all_labels.append(y_b.reshape(-1).long().to(probs.device))
     probs, labels = torch.cat(all_probs), torch.cat(all_labels)

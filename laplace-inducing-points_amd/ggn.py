@@ -231,7 +231,8 @@ def materialize_factor(eng: LinearizedNet, c: float = 1.0, block: Optional[int] 
     return Wm
 
 
-def compute_ggn_diag(state, Z, model_type, full_set_size=None, example_chunk: Optional[int] = None) -> torch.Tensor:
+def compute_ggn_diag(state, Z, model_type, full_set_size=None, example_chunk: Optional[int] = None, *,
+                     curvature=None) -> torch.Tensor:
     """diag((N/M) sum_i J_i^T H_i J_i) (x exp(-logvar) for the regressor) -> (D,) float32 on the device.
 
     Not a reference function (the reference has no diagonal): the exact GGN diagonal, the curvature of a diagonal
@@ -239,7 +240,14 @@ def compute_ggn_diag(state, Z, model_type, full_set_size=None, example_chunk: Op
     go through ONE square-accumulating backward sweep (:meth:`LinearizedNet.vjp_sqsum`): diag = recal * sum_k sum_i
     (J_i^T L_i e_k)^2 with the same N/M (x exp(-logvar)) factor as :func:`compute_ggn_vp`, and without the (M K, D)
     factor rows ``(materialize_factor(eng) ** 2).sum(0)`` would write.  ``example_chunk`` binds the examples in chunks
-    as :class:`ExampleChunkedGGN` does; the chunks' sums add up in one output vector."""
+    as :class:`ExampleChunkedGGN` does; the chunks' sums add up in one output vector.  ``curvature`` (a spec of
+    ``fisher.py``: ``MCFisher``, ``EmpiricalFisher``, ``Cotangents``) replaces the K one-hot probes by that spec's raw
+    cotangents (:func:`fisher.compute_ggn_diag`); ``None`` / ``"ggn"`` is the exact diagonal."""
+    if curvature is not None:
+        from . import fisher
+        spec = fisher.checked(curvature, state, Z, model_type)
+        if spec is not None:
+            return fisher.compute_ggn_diag(state, Z, model_type, spec, full_set_size=full_set_size, example_chunk=example_chunk)
     M = Z.shape[0]
     N = full_set_size or M
     recal = N / M
@@ -270,11 +278,11 @@ def compute_kron_factors_last_layer(state, Z, model_type, example_chunk: Optiona
     return last_layer_kron.compute_kron_factors_last_layer(state, Z, model_type, example_chunk=example_chunk)
 
 
-def compute_kfac_factors(state, Z, model_type, example_chunk: Optional[int] = None):
+def compute_kfac_factors(state, Z, model_type, example_chunk: Optional[int] = None, *, curvature=None):
     """``(blocks, As, Ss, M)``: the layer blocks of the Kronecker-factored posterior over all layers and their two
     factors per block, float64, unscaled (:func:`kfac.compute_kfac_factors`)."""
     from . import kfac
-    return kfac.compute_kfac_factors(state, Z, model_type, example_chunk=example_chunk)
+    return kfac.compute_kfac_factors(state, Z, model_type, example_chunk=example_chunk, curvature=curvature)
 
 
 def compute_ekfac_scales(state, Z, model_type, bases, example_chunk: Optional[int] = None,

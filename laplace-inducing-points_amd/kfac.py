@@ -90,17 +90,28 @@ def _remainder_prior(alpha, idx: torch.Tensor, D: int) -> torch.Tensor:
     return torch.full((idx.numel(),), float(alpha), dtype=torch.float64)
 
 
-def compute_kfac_factors(state, Z, model_type, example_chunk: Optional[int] = None, class_chunk: Optional[int] = None):
+def compute_kfac_factors(state, Z, model_type, example_chunk: Optional[int] = None, class_chunk: Optional[int] = None, *,
+                         curvature=None):
     """``(blocks, As, Ss, M)``: the layer blocks and their two unscaled factors summed over the M = len(Z) examples,
     float64 on the device (:meth:`LinearizedNet.kfac_factors`), chunked like
-    :func:`last_layer_kron.compute_kron_factors_last_layer`; all chunks add into one pair per block."""
+    :func:`last_layer_kron.compute_kron_factors_last_layer`; all chunks add into one pair per block.  ``curvature``
+    (a spec of ``fisher.py``) builds the output factors S_l from that spec's raw cotangents, divided by its divisor,
+    instead of the K one-hot probes; the input factors A_l are the same either way."""
+    from . import fisher
+    spec = fisher.checked(curvature, state, Z, model_type)
     blocks = block_table(state)
     engines = _engines(state, Z, model_type, None, example_chunk)
     dev = engines[0].device
     As = [torch.zeros(b.Mt, b.Mt, device=dev, dtype=torch.float64) for b in blocks]
     Ss = [torch.zeros(b.N, b.N, device=dev, dtype=torch.float64) for b in blocks]
-    for eng in engines:
-        eng.kfac_factors(As, Ss, class_chunk=class_chunk)
+    if spec is None:
+        for eng in engines:
+            eng.kfac_factors(As, Ss, class_chunk=class_chunk)
+    else:
+        source = fisher.source_for(spec, state, Z, model_type)
+        for j, eng in enumerate(engines):
+            U, divisor = source(eng, j * example_chunk if len(engines) > 1 else 0)
+            eng.kfac_factors(As, Ss, class_chunk=class_chunk, probes=U, divisor=divisor)
     return engines[0].kfac_blocks(), As, Ss, Z.shape[0]
 
 
@@ -112,19 +123,20 @@ def fit_blocks(blocks, As, Ss, rows, recal: float, M: int, classifier: bool):
             for b, A, S, a in zip(blocks, As, Ss, rows)]
 
 
-def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk):
+def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, curvature=None):
     """(blocks, fits, rem_idx, rem_var, rem_prior); the prior is checked before anything is allocated"""
     blocks = block_table(map_state)
     D = flatten_nn_params(map_state.params)[0].numel()
     rows = [block_prior_rows(alpha, b, D) for b in blocks]
     rem = remainder_indices(blocks, D)
     a_rem = _remainder_prior(alpha, rem, D)
-    blocks, As, Ss, M = compute_kfac_factors(map_state, Z, model_type, example_chunk=example_chunk)
+    blocks, As, Ss, M = compute_kfac_factors(map_state, Z, model_type, example_chunk=example_chunk, curvature=curvature)
     fits = fit_blocks(blocks, As, Ss, rows, _recal(map_state, M, model_type, full_set_size), M, model_type != "regressor")
     dev = As[0].device
     rem_var = torch.zeros(0, device=dev, dtype=torch.float64)
     if rem.numel():
-        diag = _ggn.compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk)
+        diag = _ggn.compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk,
+                                     curvature=curvature)
         rem_var = 1.0 / (a_rem.to(dev) + diag.double()[rem.to(dev)])
     return blocks, fits, rem.to(dev), rem_var, a_rem.to(dev)
 
@@ -136,16 +148,20 @@ def _prior_key(alpha):
 _FIT_CACHE = {}          # one entry, as last_layer_kron._FIT_CACHE
 
 
-def _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk):
-    """the fit, computed once per (binding, prior, N, chunking); ``clear_engine_cache`` drops the entry"""
+def _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, curvature=None):
+    """the fit, computed once per (binding, prior, N, chunking, curvature spec); ``clear_engine_cache`` drops the entry"""
     if _FIT_CACHE.clear not in _ggn._CLEAR_HOOKS:
         _ggn._CLEAR_HOOKS.append(_FIT_CACHE.clear)
     key = (_ggn.engine_key(map_state, Z, model_type), _prior_key(alpha), full_set_size, example_chunk)
+    if curvature is not None:
+        from .fisher import spec_key
+        if spec_key(curvature) is not None:
+            key = key + (spec_key(curvature),)
     hit = _FIT_CACHE.get(key)
     if hit is None:
-        fit = _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+        fit = _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, curvature)
         _FIT_CACHE.clear()
-        hit = _FIT_CACHE[key] = (fit, (map_state.params, map_state.batch_stats, Z))
+        hit = _FIT_CACHE[key] = (fit, (map_state.params, map_state.batch_stats, Z, curvature))
     return hit[0]
 
 
@@ -158,17 +174,20 @@ def posterior_from_fit(flat: torch.Tensor, blocks, fits, rem_idx, rem_var, rem_p
     return KFACNormal(loc, parts, (rem_idx, rem_var), remainder_prior=rem_prior)
 
 
-def posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=None, example_chunk: Optional[int] = None) -> KFACNormal:
+def posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=None, example_chunk: Optional[int] = None, *,
+                       curvature=None) -> KFACNormal:
     """N(theta_MAP, blockdiag((G_l + diag(a))^-1, remainder)) over the whole flat vector in factored form, float64 on
     the device; nothing of size D x D, and no Mt N x Mt N matrix, is built.  The fit is cached per
-    (state, Z, prior, N, chunking) (a one-entry cache)."""
-    blocks, fits, rem_idx, rem_var, rem_prior = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+    (state, Z, prior, N, chunking, curvature spec) (a one-entry cache).  ``curvature``: a spec of ``fisher.py`` for the
+    output factors and the remainder's diagonal (:func:`compute_kfac_factors`)."""
+    blocks, fits, rem_idx, rem_var, rem_prior = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk,
+                                                            curvature)
     flat, _ = flatten_nn_params(map_state.params)
     return posterior_from_fit(flat, blocks, fits, rem_idx, rem_var, rem_prior)
 
 
 def predict_lla_kfac(map_state, Xnew, Z, model_type, alpha, full_set_size=None, cov: str = "full", batch: int = 256,
-                     example_chunk: Optional[int] = None):
+                     example_chunk: Optional[int] = None, *, curvature=None):
     """Closed-form linearised predictive of :func:`posterior_lla_kfac`: mean f(x; theta_MAP) and
     sum_l J_l(x) Sigma_l J_l(x)^T + sum_d J_d(x)^2 var_d per test point (``lip_kfac_predict`` per layer block on the
     Jacobian rows of ``lip_vjp_rows``), in the return shapes and types of
@@ -176,7 +195,7 @@ def predict_lla_kfac(map_state, Xnew, Z, model_type, alpha, full_set_size=None, 
     ``cov="full"`` when their (K, batch, D) float32 rows would exceed 2 GiB."""
     if cov not in ("diag", "full"):
         raise ValueError("cov must be 'diag' or 'full'")
-    _, fits, rem_idx, rem_var, _ = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+    _, fits, rem_idx, rem_var, _ = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, curvature)
     return predictive_from_fit(map_state, Xnew, model_type, [(V, R, Ub) for V, R, Ub, _, _, _ in fits], (rem_idx, rem_var),
                                cov, batch)
 
@@ -206,13 +225,14 @@ def predictive_from_fit(map_state, Xnew, model_type, triples, rem, cov: str, bat
 
 
 def predict_lla_kfac_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1,
-                              example_chunk: Optional[int] = None) -> torch.Tensor:
+                              example_chunk: Optional[int] = None, *, curvature=None) -> torch.Tensor:
     """Draws of the outputs under :func:`posterior_lla_kfac`: f(x; theta_MAP) + J(x) d_theta_s -> (S, B, K) float32,
     d_theta_s the zero-mean part of ``num_samples`` draws of :meth:`KFACNormal.sample` pushed through the engine's JVP
     ('raw'), as :func:`lla.predict_lla_diag_scalable` does.  This is the route for heads like ResNet-50's: K = 1000
     Jacobian rows per test point make the closed form of :func:`predict_lla_kfac` impractical there, while a draw costs
     one tangent-forward pass whatever K is."""
-    post = posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=full_set_size, example_chunk=example_chunk)
+    post = posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=full_set_size, example_chunk=example_chunk,
+                              curvature=curvature)
     return draws_from_posterior(post, map_state, Xnew, model_type, key, num_samples)
 
 
@@ -237,10 +257,10 @@ def kfac_spectrum(blocks, As, Ss, M: int, classifier: bool) -> torch.Tensor:
     return torch.cat(parts)
 
 
-def _spectrum_kfac(X, state, model_type) -> Tuple[torch.Tensor, int, float]:
+def _spectrum_kfac(X, state, model_type, curvature=None) -> Tuple[torch.Tensor, int, float]:
     """eigenvalues (float64, clamped at 0) of the Kronecker-factored curvature built at N/M = 1 (x exp(-logvar) for the
     regressor) with the remainder's GGN diagonal appended, D, ||theta||^2"""
-    blocks, As, Ss, M = compute_kfac_factors(state, X, model_type)
+    blocks, As, Ss, M = compute_kfac_factors(state, X, model_type, curvature=curvature)
     spec = kfac_spectrum(blocks, As, Ss, M, model_type != "regressor")
     if model_type == "regressor":
         spec = spec * math.exp(-_ggn._logvar(state))
@@ -248,6 +268,6 @@ def _spectrum_kfac(X, state, model_type) -> Tuple[torch.Tensor, int, float]:
     D = flat.numel()
     rem = remainder_indices(blocks, D)
     if rem.numel():
-        diag = _ggn.compute_ggn_diag(state, X, model_type)
+        diag = _ggn.compute_ggn_diag(state, X, model_type, curvature=curvature)
         spec = torch.cat([spec, diag.double()[rem.to(diag.device)].clamp_min(0.0)])
     return spec, D, float((flat.detach().double() ** 2).sum())

@@ -20,6 +20,7 @@ from .last_layer import (LAST_LAYER_MAX_DIM, posterior_lla_last_layer, predict_l
 from .last_layer_kron import (posterior_lla_last_layer_kron, predict_lla_last_layer_kron,            # noqa: F401
                               predict_lla_last_layer_kron_scalable)
 from .kfac import posterior_lla_kfac, predict_lla_kfac, predict_lla_kfac_scalable                 # noqa: F401
+from .fisher import Cotangents, EmpiricalFisher, MCFisher, sample_head_cotangents                 # noqa: F401
 from .ekfac import posterior_lla_ekfac, predict_lla_ekfac, predict_lla_ekfac_scalable             # noqa: F401
 from .lowrank import posterior_lla_lowrank, predict_lla_lowrank, predict_lla_lowrank_scalable     # noqa: F401
 from .subnetwork import (SUBNETWORK_MAX_DIM, posterior_lla_subnetwork, predict_lla_subnetwork,      # noqa: F401
@@ -129,11 +130,12 @@ def predict_lla_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_s
     return fmu[None] + dys
 
 
-def posterior_lla_diag(map_state, Z, model_type, alpha, full_set_size=None) -> MultivariateNormalDiag:
+def posterior_lla_diag(map_state, Z, model_type, alpha, full_set_size=None, *, curvature=None) -> MultivariateNormalDiag:
     """Diagonal Laplace posterior N(theta_MAP, diag(1 / (alpha + diag(GGN)))) with the GGN of
     :func:`compute_ggn_vp` (N/M, exp(-logvar)).  Not a reference function: the diagonal-LA baseline; its variances
-    are the per-weight uncertainties."""
-    diag = compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size)
+    are the per-weight uncertainties.  ``curvature``: a spec of ``fisher.py`` (Monte-Carlo or empirical Fisher diagonal
+    in place of the exact one)."""
+    diag = compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size, curvature=curvature)
     flat_params, _ = flatten_nn_params(map_state.params)
     loc = flat_params.detach().to(device=diag.device, dtype=diag.dtype)
     if is_grouped(alpha):
@@ -141,14 +143,15 @@ def posterior_lla_diag(map_state, Z, model_type, alpha, full_set_size=None) -> M
     return MultivariateNormalDiag(loc, variance=1.0 / (float(alpha) + diag))
 
 
-def predict_lla_diag_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1):
+def predict_lla_diag_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1, *,
+                              curvature=None):
     """:func:`predict_lla_scalable` with draws of the diagonal posterior (:func:`sample_diag`):
     f(x; theta_MAP) + J(x) w_s -> (S, B, C).  Not a reference function."""
     flat_params, _ = flatten_nn_params(map_state.params)
     D = flat_params.shape[0]
     key = key if key is not None else 123
     w_samples = sample_diag(map_state, Z, D, alpha=alpha, key=key, model_type=model_type, num_samples=num_samples,
-                            full_set_size=full_set_size)
+                            full_set_size=full_set_size, curvature=curvature)
     eng = get_engine(map_state, Xnew, model_type, workspace_bytes=4 << 30)
     fmu = eng.outputs()
     dys = eng.jvp(w_samples, "raw")
@@ -256,7 +259,8 @@ def covariance_from_polarisation(q: torch.Tensor, ks: torch.Tensor, kps: torch.T
     return S
 
 
-def predict_lla_diag(map_state, Xnew, Z, model_type, alpha, full_set_size=None, cov: str = "diag", batch: int = 256):
+def predict_lla_diag(map_state, Xnew, Z, model_type, alpha, full_set_size=None, cov: str = "diag", batch: int = 256, *,
+                     curvature=None):
     """Closed-form linearised predictive of the diagonal posterior of :func:`posterior_lla_diag`: the mean
     f(x; theta_MAP) (B, K) and the variances var_k(x) = sum_d sigma_d^2 J(x)[k, d]^2 (B, K), float64 — what
     :func:`predict_lla_diag_scalable` estimates from draws, without draws.  One weighted-norm backward sweep of K
@@ -267,7 +271,7 @@ def predict_lla_diag(map_state, Xnew, Z, model_type, alpha, full_set_size=None, 
     (B, B) diagonal matrix).  Not a reference function."""
     if cov not in ("diag", "full"):
         raise ValueError("cov must be 'diag' or 'full'")
-    w = posterior_lla_diag(map_state, Z, model_type, alpha, full_set_size=full_set_size).variance()
+    w = posterior_lla_diag(map_state, Z, model_type, alpha, full_set_size=full_set_size, curvature=curvature).variance()
     means, outs = [], []
     for s0 in range(0, Xnew.shape[0], batch):
         eng = get_engine(map_state, Xnew[s0:s0 + batch], model_type)

@@ -342,12 +342,12 @@ def sample(state, Z, D, alpha, key, model_type, num_samples=1, full_set_size=Non
     return out
 
 
-def sample_diag(state, Z, D, alpha, key, model_type, num_samples=1, full_set_size=None):
+def sample_diag(state, Z, D, alpha, key, model_type, num_samples=1, full_set_size=None, *, curvature=None):
     """``num_samples`` zero-mean draws of the DIAGONAL Laplace posterior -> (S, D): eps / sqrt(alpha + diag(GGN)),
     eps ~ N(0, I) from the same in-kernel generator and seeding as :func:`sample` (theta_MAP not added, as there).
     Not a reference function: the diagonal-LA baseline an inducing-point posterior is compared against
-    (diag from :func:`ggn.compute_ggn_diag`)."""
-    diag = compute_ggn_diag(state, Z, model_type, full_set_size=full_set_size)
+    (diag from :func:`ggn.compute_ggn_diag`, with its ``curvature`` spec when one is given)."""
+    diag = compute_ggn_diag(state, Z, model_type, full_set_size=full_set_size, curvature=curvature)
     if diag.numel() != D:
         raise ValueError(f"D = {D} does not match the network's {diag.numel()} parameters")
     out = krylov.fill_normal(num_samples, D, _seed(key) * 1000003, diag.device)

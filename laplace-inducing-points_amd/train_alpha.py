@@ -151,22 +151,25 @@ def fit_alpha_last_layer_kron(X, state, model_type, full_set_size=None, alpha0: 
     return _fit_from_spectrum(lam, DL, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
-def log_marginal_likelihood_kfac(alpha, X, state, model_type: str, full_set_size: Optional[int] = None) -> float:
+def log_marginal_likelihood_kfac(alpha, X, state, model_type: str, full_set_size: Optional[int] = None, *,
+                                 curvature=None) -> float:
     """:func:`log_marginal_likelihood` under the Kronecker-factored curvature of every layer (``kfac.py``): the spectrum
     is the concatenation of outer(lam_l, mu_l) / (M T_l) over the layer blocks and the GGN diagonal of the parameters
-    outside every block, D and ||theta||^2 those of the whole vector.  Scalar alpha.  Not a reference function."""
+    outside every block, D and ||theta||^2 those of the whole vector.  Scalar alpha.  ``curvature``: a spec of
+    ``fisher.py`` for the output factors and that diagonal.  Not a reference function."""
     from .kfac import _spectrum_kfac
     N = full_set_size or X.shape[0]
-    lam, D, theta2 = _spectrum_kfac(X, state, model_type)
+    lam, D, theta2 = _spectrum_kfac(X, state, model_type, curvature)
     return _lml_from_spectrum(float(alpha), lam, D, theta2, N / X.shape[0])[0]
 
 
-def fit_alpha_kfac(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200):
+def fit_alpha_kfac(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200, *,
+                   curvature=None):
     """:func:`fit_alpha` on the Kronecker-factored evidence: ``(alpha, history)``; the factors and their
-    eigendecompositions are computed once."""
+    eigendecompositions are computed once (with the curvature spec ``curvature`` of ``fisher.py`` when one is given)."""
     from .kfac import _spectrum_kfac
     N = full_set_size or X.shape[0]
-    lam, D, theta2 = _spectrum_kfac(X, state, model_type)
+    lam, D, theta2 = _spectrum_kfac(X, state, model_type, curvature)
     return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
