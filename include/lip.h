@@ -419,6 +419,47 @@ int lip_kfac_predict(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_
 int lip_kfac_eigen_sqsum_scratch(int32_t R, int32_t Mt, int32_t N, int64_t* doubles);
 int lip_kfac_eigen_sqsum(const float* W, int64_t ldw, int32_t R, int64_t off, int32_t Mt, int32_t N, const double* V,
                          const double* Ub, double* Lam, double* scratch, int64_t scratch_doubles, void* stream);
+/* The same second moments from one backward sweep, without factor rows.  The slice of a factor row that belongs to a
+ * layer block is a per-example weight gradient, mat_l(J_i^T u) = At_i^T G_i diag(s) (At_i the (OH OW, Mt) im2col patches of
+ * example i with the leading 1 of a bias, G_i the (OH OW, N) cotangent rows of the block's WGRAD op, s the frozen BN
+ * scale), so V^T mat_l(.) Ub = (At_i V)^T (G_i Ub') with Ub' = diag(s) Ub: a per-example weight gradient of a 1x1
+ * convolution with Mt input channels on the OH x OW map, both operands projected first.
+ *
+ * lip_kfac_project_patches: AV ((n OH OW), Mt) float32 row-major, overwritten, AV[(i,t)][j] = sum_e at_{i,t}[e] V[e][j];
+ * X, the geometry and the patch order are those of lip_kfac_input_gram, V (Mt, Mt) float64 row-major.  The sum runs in
+ * e order on the float64 matrix pipe and is rounded once, on the store; rows of AV are 16-byte aligned when Mt % 4 == 0
+ * and AV is.  No scratch, no atomics, bitwise reproducible, nothing outside X is read.  A null pointer, a non-positive
+ * extent, or 2^31 or more elements of X, AV or V returns LIP_ERR_ARG and leaves AV untouched.
+ *
+ * lip_rows_project: GU ((P R), N) float32 row-major, overwritten, GU[p R + r][m] = sum_c G[p pstride + r ldg + c] Ub[c][m];
+ * G the float32 cotangent rows of a WGRAD op (R rows of N per probe, row stride ldg >= N, per-probe stride pstride),
+ * Ub (N, N) float64 row-major (the caller folds diag(s) into it).  One launch when the probes are adjacent
+ * (P == 1 or pstride == R ldg), one per probe otherwise; the same accumulation and single rounding.  A null pointer, a
+ * non-positive extent, ldg < N, pstride < (R - 1) ldg + N with P > 1, or 2^31 or more elements of GU or Ub returns
+ * LIP_ERR_ARG and leaves GU untouched. */
+int lip_kfac_project_patches(const float* X, int32_t n, int32_t IH, int32_t IW, int32_t C, int32_t KH, int32_t KW,
+                             int32_t stride, int32_t pad_h, int32_t pad_w, int32_t OH, int32_t OW, int32_t bias, const double* V,
+                             float* AV, void* stream);
+int lip_rows_project(const float* G, int64_t ldg, int64_t pstride, int32_t P, int32_t R, int32_t N, const double* Ub, float* GU,
+                     void* stream);
+/* The sweep that joins them, ADDED into Lam: the backward sweep of lip_vjp_kron (same U, head modes and c, no weight
+ * gradient into parameter space, no bias / BN reduction) in which every WGRAD op projects its activation operand with
+ * V[k] (once per op and pass) and the cotangent rows of the pass's probes with Ub[k], runs the square-accumulating
+ * per-(probe, example) weight gradient of lip_vjp_sqsum on the projected pair (C = Mt, 1x1, stride 1, no padding, no
+ * scale) into a zeroed (Mt, N) float32 block, and adds that block to Lam[k] in float64:
+ *   Lam[k][j][m] += sum_{p < P} sum_{i < n} ( ((At_i V[k])^T (G_pi Ub[k]))[j][m] )^2.
+ * V, Ub, Lam, Mt are HOST arrays of nblocks entries, one per WGRAD op in tape order (the order of lip_vjp_kron_layout):
+ * device pointers to V (Mt, Mt), Ub (N, N) and Lam (Mt, N), float64 row-major, and the block's rows Mt[k] = KH KW C of
+ * the op, plus 1 for a block with a bias row.  scratch: device, 16-byte aligned, >= lip_vjp_eigen_scratch(e, P) floats
+ * (per op n OH OW Mt + P' n OH OW N + Mt N floats and the square sums' own scratch, P' the probes of a pass).  Passes
+ * add in order and every kernel sums in a fixed order: bitwise reproducible for a given binding, probe count and
+ * chunking.  Every op of every pass is checked before the first launch: a null operand, nblocks other than the number of
+ * WGRAD ops, an Mt[k] that is not the op's KH KW C (+ 1), 2^31 or more elements of an operand on a pass, or too small a
+ * scratch returns LIP_ERR_ARG and leaves every Lam untouched; LIP_ERR_STATE as lip_vjp_sqsum. */
+int lip_vjp_eigen_scratch(lip_engine_t* e, int32_t P, int64_t* floats);
+int lip_vjp_eigen(lip_engine_t* e, const float* U, const double* const* V, const double* const* Ub, double* const* Lam,
+                  const int32_t* Mt, int32_t nblocks, int32_t P, int32_t head_mode, float c, float* scratch,
+                  int64_t scratch_floats, void* stream);
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);

@@ -51,6 +51,8 @@ struct lip_engine {
   // total; filled when the backward tape is set
   std::vector<int64_t> kron_off;
   int64_t kron_total = 0;
+  // lip_vjp_eigen: the number of WGRAD ops before backward op i (the index of its block in the call's host arrays)
+  std::vector<int> wgrad_index;
   ~lip_engine() { delete cache; }
 };
 
@@ -65,6 +67,17 @@ enum class Sweep {
             // norm of every cotangent is added to wout[p * n + i]
   KRON,     // lip_vjp_kron: no parameter cotangent is formed; every WGRAD op Gram-multiplies the rows of its cotangent
             // operand into its (N, N) float64 block of kron (the output factors of a Kronecker-factored curvature)
+  EIGEN,    // lip_vjp_eigen: no parameter cotangent is formed; every WGRAD op projects its activation patches with the
+            // block's V and its cotangent rows with the block's Ub, and the per-(probe, example) products of the projected
+            // pair are squared and summed into the block's (Mt, N) float64 Lam (the second moments EKFAC needs)
+};
+
+// The operands of one WGRAD op in an EIGEN sweep: the block's bases and output, and its rows Mt = KH KW C (+ 1: a bias row)
+struct EigenBlock {
+  const double* V;
+  const double* Ub;
+  double* Lam;
+  int Mt;
 };
 
 struct RunCtx {
@@ -84,12 +97,14 @@ struct RunCtx {
   double* kron = nullptr;         // KRON: the (N, N) block of the op being run (run_tape shifts the output buffer per op)
   double* kron_scratch = nullptr; // ... and the partial tiles of one Gram
   long long kron_doubles = 0;
+  const EigenBlock* eigen = nullptr;  // EIGEN: the blocks of the WGRAD ops in tape order (run_tape picks the op's), scratch as SQSUM's
   // summed products (lip_ggn_vp / lip_vjp): a weight gradient that reduces all rows in one block may WRITE
   // y = s acc + alpha v instead of adding to an initialised block (the initialisation then skips its parameters)
   bool fuse = false;
   float alpha = 0.f;
 
   bool per_example() const { return mode != Sweep::SUMMED; }      // cotangents are taken per example
+  bool no_params() const { return mode == Sweep::KRON || mode == Sweep::EIGEN; }      // no parameter cotangent is formed
   bool may_overwrite(const lip_ref_t& out) const { return fuse && mode == Sweep::SUMMED && out.space == LIP_SP_YOUT; }
 };
 
@@ -107,6 +122,10 @@ inline RunCtx weighted_norm(RunCtx c, float* scratch, long long floats, bool won
 
 inline RunCtx kron_factors(RunCtx c, double* out, double* scratch, long long doubles) {
   c.mode = Sweep::KRON; c.kron = out; c.kron_scratch = scratch; c.kron_doubles = doubles;
+  return c;
+}
+inline RunCtx eigen_moments(RunCtx c, const EigenBlock* blocks, float* scratch, long long floats) {
+  c.mode = Sweep::EIGEN; c.eigen = blocks; c.scratch = scratch; c.scratch_floats = floats;
   return c;
 }
 
@@ -172,7 +191,7 @@ int reduce_params(const RunCtx& c, const ReduceP& r, int n_img, const char* who)
 // without them and takes them by a segmented reduce over the op's freshly written output [P][n][rows][N] instead.
 template <class Prm, class Launch>
 int launch_with_reductions(const RunCtx& c, Prm& p, Launch launch, const char* who, int n_img, int rows, int N, const float* xhat) {
-  if (c.mode == Sweep::KRON) { p.red0 = nullptr; p.red1 = nullptr; }      // no parameter cotangent is formed
+  if (c.no_params()) { p.red0 = nullptr; p.red1 = nullptr; }
   if (!c.per_example() || (!p.red0 && !p.red1)) { RUN_CHECK(launch(p), who); return LIP_OK; }
   ReduceP r;
   memset(&r, 0, sizeof(r));
@@ -257,6 +276,75 @@ int kron_wgrad(const RunCtx& c, const lip_op_t& op) {
   return LIP_OK;
 }
 
+// EIGEN: the scratch floats of one WGRAD op with Mt rows on a pass of pc probes, in the order eigen_wgrad lays them out
+// (every part a whole number of float4): the projected patches AV (n OH OW, Mt), the projected rows GU (pc n OH OW, N),
+// the pass's (Mt, N) float32 sums, and the scratch of the square-accumulating weight gradient on the projected pair
+struct EigenLayout {
+  long long av, gu, y, sq;
+  long long total() const { return av + gu + y + sq; }
+};
+inline long long round4(long long x) { return (x + 3) / 4 * 4; }
+EigenLayout eigen_layout(const lip_op_t& op, int Mt, int pc) {
+  const long long Rp = (long long)op.n_img * op.OH * op.OW;
+  EigenLayout l;
+  l.av = round4(Rp * Mt); l.gu = round4(Rp * pc * op.N); l.y = round4((long long)Mt * op.N);
+  l.sq = wgrad_sqsum_scratch(Mt, op.N, op.OH * op.OW, (long long)pc * op.n_img);
+  return l;
+}
+
+// can the op run in an EIGEN sweep with Mt rows on a pass of pc probes?  (the 32-bit index arithmetic of the weight
+// gradient on the projected pair, the projections' grids, and a window geometry whose clamped gather stays in the tensor)
+bool eigen_op_fits(const lip_op_t& op, int Mt, int pc) {
+  const lip_seg_t& g = op.seg[0];
+  if (op.n_img <= 0 || op.OH <= 0 || op.OW <= 0 || op.N <= 0 || pc <= 0 || g.IH <= 0 || g.IW <= 0 || g.C <= 0 || g.KH <= 0 ||
+      g.KW <= 0 || g.stride <= 0 || g.pad_h < 0 || g.pad_w < 0)
+    return false;
+  const long long M = (long long)g.KH * g.KW * g.C, Rp = (long long)op.n_img * op.OH * op.OW, lim = 1ll << 31;
+  if (Mt != M && Mt != M + 1) return false;
+  if (pc > 1 && g.b.pstride < Rp * op.N) return false;                  // the probes' row blocks would overlap
+  if ((long long)(op.OH - 1) * g.stride - g.pad_h >= g.IH || (long long)(op.OW - 1) * g.stride - g.pad_w >= g.IW) return false;
+  return Rp * Mt < lim && Rp * pc * op.N < lim && (long long)Mt * op.N < lim && (long long)Mt * Mt < lim &&
+         (long long)op.N * op.N < lim && (long long)op.n_img * g.IH * g.IW * g.C < lim && (long long)pc * op.n_img < lim &&
+         ll_project_fits(Rp, Mt) && ll_project_fits(Rp * pc, op.N);
+}
+
+// EIGEN: Lam_l += sum over the (probe, example) pairs of ((At_i V)^T (G_pi Ub))^2, At_i the example's patches, G_pi the
+// pair's cotangent rows.  The patches are projected once for the pass, the rows of all its probes next; the projected
+// pair is a 1x1 convolution with Mt input channels on the OH x OW map, whose per-pair weight gradients the
+// square-accumulating launcher of lip_vjp_sqsum forms, squares and sums into the pass's float32 block.
+int eigen_wgrad(const RunCtx& c, const lip_op_t& op) {
+  const lip_seg_t& g = op.seg[0];
+  const float* a = resolve(c, g.a);
+  const float* rows = resolve(c, g.b);
+  const EigenBlock* b = c.eigen;
+  if (!a || !rows || !b || !b->V || !b->Ub || !b->Lam || !c.scratch || g.a.pstride != 0) { set_error("WGRAD (eigen): bad operands"); return LIP_ERR_ARG; }
+  if (!eigen_op_fits(op, b->Mt, c.P)) {       // lip_vjp_eigen has checked every op before its first launch
+    set_error("WGRAD (eigen): the block does not match the op, or a tensor of 2^31 or more elements");
+    return LIP_ERR_ARG;
+  }
+  const EigenLayout l = eigen_layout(op, b->Mt, c.P);
+  if (l.total() > c.scratch_floats) { set_error("WGRAD (eigen): scratch too small"); return LIP_ERR_ARG; }
+  float* AV = c.scratch;
+  float* GU = AV + l.av;
+  float* y = GU + l.gu;
+  float* sq = y + l.y;
+  const int Mt = b->Mt, OHW = op.OH * op.OW, Rp = op.n_img * OHW;
+  RUN_CHECK(launch_project_patches(a, op.n_img, g.IH, g.IW, g.C, g.KH, g.KW, g.stride, g.pad_h, g.pad_w, op.OH, op.OW,
+                                   Mt - g.KH * g.KW * g.C, b->V, AV, c.st), "patch projection launch");
+  RUN_CHECK(launch_rows_project(rows, op.N, g.b.pstride, c.P, Rp, op.N, b->Ub, GU, c.st), "row projection launch");
+  RUN_CHECK(hipMemsetAsync(y, 0, sizeof(float) * (size_t)Mt * op.N, c.st), "memset eigen sums");
+  WgradP p = WgradP();
+  p.a = AV; p.IH = op.OH; p.IW = op.OW; p.C = Mt; p.KH = 1; p.KW = 1; p.stride = 1; p.pad_h = 0; p.pad_w = 0;
+  p.g = GU; p.g_ps = (long long)Rp * op.N;
+  p.R = Rp; p.OHW = OHW; p.OW = op.OW; p.N = op.N; p.M = Mt;
+  p.dOHW = FastDiv((unsigned)OHW); p.dOW = FastDiv((unsigned)op.OW);
+  p.y = y; p.y_ps = 0; p.scale = nullptr;
+  p.ksplit = 1; p.seg_rows = OHW; p.seg_ys = 0;
+  RUN_CHECK(launch_wgrad_sqsum(p, c.P, op.n_img, sq, l.sq, c.st), "square-sum wgrad launch (eigen)");
+  RUN_CHECK(launch_eigen_fold(y, (long long)Mt * op.N, b->Lam, c.st), "eigen fold launch");
+  return LIP_OK;
+}
+
 int run_op(const RunCtx& c, const lip_op_t& op) {
   switch (op.kind) {
     case LIP_OP_IGEMM: {
@@ -310,6 +398,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
     }
     case LIP_OP_WGRAD: {
       if (c.mode == Sweep::KRON) return kron_wgrad(c, op);
+      if (c.mode == Sweep::EIGEN) return eigen_wgrad(c, op);
       WgradP p;
       const int rc = make_wgrad(c, op, p);
       if (rc) return rc;
@@ -324,7 +413,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       return LIP_OK;
     }
     case LIP_OP_REDUCE: {
-      if (c.mode == Sweep::KRON) return LIP_OK;
+      if (c.no_params()) return LIP_OK;
       ReduceP p;
       memset(&p, 0, sizeof(p));
       p.g = resolve(c, op.seg[0].a); p.g_ps = op.seg[0].a.pstride;
@@ -439,6 +528,10 @@ int run_tape(const RunCtx& c, int which, bool skip_head) {
     if (c.mode == Sweep::KRON && t[i].kind == LIP_OP_WGRAD) {
       RunCtx ck = c;                                   // this op's block of the output buffer
       ck.kron = c.kron + c.e->kron_off[i];
+      rc = run_op(ck, t[i]);
+    } else if (c.mode == Sweep::EIGEN && t[i].kind == LIP_OP_WGRAD) {
+      RunCtx ck = c;                                   // this op's block of the call's arrays
+      ck.eigen = c.eigen + c.e->wgrad_index[i];
       rc = run_op(ck, t[i]);
     } else {
       rc = run_op(c, t[i]);
@@ -605,10 +698,13 @@ int lip_engine_set_tape(lip_engine_t* e, int32_t which, const lip_op_t* ops, int
   e->tape[which].assign(ops, ops + nops);
   if (which == LIP_TAPE_BACKWARD) {
     e->kron_off.assign(nops, 0);
+    e->wgrad_index.assign(nops, 0);
     e->kron_total = 0;
+    int wgrads = 0;
     for (int i = 0; i < nops; ++i) {
       e->kron_off[i] = e->kron_total;
-      if (ops[i].kind == LIP_OP_WGRAD) e->kron_total += (int64_t)ops[i].N * ops[i].N;
+      e->wgrad_index[i] = wgrads;
+      if (ops[i].kind == LIP_OP_WGRAD) { e->kron_total += (int64_t)ops[i].N * ops[i].N; ++wgrads; }
     }
   }
   if (which == LIP_TAPE_PRIMAL) e->primal_done = false;
@@ -799,6 +895,55 @@ int lip_vjp_kron(lip_engine_t* e, const float* U, double* S, int32_t P, int32_t 
   return for_each_pass(e, P, [&](int c0, int pc) {
     const RunCtx c{e, nullptr, nullptr, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
     return run_tape(kron_factors(c, S, scratch, scratch_doubles), LIP_TAPE_BACKWARD, false);
+  });
+}
+
+int lip_vjp_eigen_scratch(lip_engine_t* e, int32_t P, int64_t* floats) {
+  if (!e || !floats || P <= 0) { set_error("lip_vjp_eigen_scratch: bad argument"); return LIP_ERR_ARG; }
+  if (e->tape[LIP_TAPE_BACKWARD].empty()) { set_error("lip_vjp_eigen_scratch: backward tape missing"); return LIP_ERR_STATE; }
+  // every part of an op's scratch grows with the probes of a pass, so the full pass bounds the shorter last one; the
+  // square sums' part is not monotone in the rows, so both row counts a block can have (with and without a bias row)
+  const int pc = e->max_chunk > 0 ? balanced_chunk(P, e->max_chunk) : P;
+  int64_t need = 0;
+  for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
+    if (op.kind != LIP_OP_WGRAD) continue;
+    const int M = op.seg[0].KH * op.seg[0].KW * op.seg[0].C;
+    for (int Mt = M; Mt <= M + 1; ++Mt) need = std::max<int64_t>(need, eigen_layout(op, Mt, pc).total());
+  }
+  *floats = need;
+  return LIP_OK;
+}
+
+int lip_vjp_eigen(lip_engine_t* e, const float* U, const double* const* V, const double* const* Ub, double* const* Lam,
+                  const int32_t* Mt, int32_t nblocks, int32_t P, int32_t head_mode, float cc, float* scratch,
+                  int64_t scratch_floats, void* stream) {
+  int rc = ready_vjp(e, "lip_vjp_eigen", U, Lam, P, head_mode, V && Ub && Mt && nblocks > 0 && scratch && scratch_floats > 0);
+  if (rc) return rc;
+  if (((uintptr_t)scratch) & 15) { set_error("lip_vjp_eigen: scratch must be 16-byte aligned"); return LIP_ERR_ARG; }
+  // every op of every pass is checked before the first launch, so that a refusal leaves every Lam untouched
+  const int step = balanced_chunk(P, e->max_chunk), last = P - (P - 1) / step * step;
+  std::vector<EigenBlock> blocks;
+  for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
+    if (op.kind != LIP_OP_WGRAD) continue;
+    const size_t k = blocks.size();
+    if (k >= (size_t)nblocks) { set_error("lip_vjp_eigen: %d blocks, the backward tape has more weight gradients", (int)nblocks); return LIP_ERR_ARG; }
+    if (!V[k] || !Ub[k] || !Lam[k]) { set_error("lip_vjp_eigen: block %zu has a null operand", k); return LIP_ERR_ARG; }
+    if (op.seg[0].a.pstride != 0 || !eigen_op_fits(op, Mt[k], step) || !eigen_op_fits(op, Mt[k], last)) {
+      set_error("lip_vjp_eigen: block %zu (Mt = %d) does not match its weight gradient, or a tensor of 2^31 or more "
+                "elements on a pass; bind fewer examples per engine", k, (int)Mt[k]);
+      return LIP_ERR_ARG;
+    }
+    const long long need = eigen_layout(op, Mt[k], step).total();
+    if (need > scratch_floats) {
+      set_error("lip_vjp_eigen: scratch of %lld floats, %lld needed (lip_vjp_eigen_scratch)", (long long)scratch_floats, need);
+      return LIP_ERR_ARG;
+    }
+    blocks.push_back(EigenBlock{V[k], Ub[k], Lam[k], (int)Mt[k]});
+  }
+  if (blocks.size() != (size_t)nblocks) { set_error("lip_vjp_eigen: %d blocks, the backward tape has %zu weight gradients", (int)nblocks, blocks.size()); return LIP_ERR_ARG; }
+  return for_each_pass(e, P, [&](int c0, int pc) {
+    const RunCtx c{e, nullptr, nullptr, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    return run_tape(eigen_moments(c, blocks.data(), scratch, scratch_floats), LIP_TAPE_BACKWARD, false);
   });
 }
 

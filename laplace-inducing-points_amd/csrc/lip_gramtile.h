@@ -1,6 +1,7 @@
 // The float64 Gram tile loop shared by the last-layer kernels (lip_lastlayer.hip) and the subnetwork kernels
 // (lip_subnetwork.hip): a 32 x 32 tile of sum_i row_i col_i^T over a range of examples on v_mfma_f64_16x16x4_f64, the
-// operands supplied by a functor, and the split of the examples over blocks that goes with it.
+// operands supplied by a functor, and the split of the examples over blocks that goes with it; and the float64 tile
+// product with a float32 result that the two projections of the EIGEN sweep share (ll_project_kernel).
 #ifndef LIP_GRAMTILE_H
 #define LIP_GRAMTILE_H
 #include "lip_internal.h"
@@ -82,6 +83,83 @@ __device__ __forceinline__ void ll_gram_tile(const Operands& op, int ib, int ie,
   }
 }
 
+// out (rows, cols) float32 = A (rows, L) B (L, cols): A's elements come from a functor (float32 values, up-cast before any
+// multiplication), B is float64 row-major, the sum runs in l order on v_mfma_f64_16x16x4_f64 and is rounded ONCE on the
+// store.  A wave per 32 x 32 tile of out (the lane map of kfac_jub_kernel), a block per row tile and four column tiles:
+// grid = (ceil(rows / 32), ceil(cols / 128)).  Rows and columns past the matrix are clamped on the loads and never
+// stored; A.row(r) prepares a row once per lane, A.at(row, l) reads one element and never reads outside its tensor.
+template <class AOp>
+__global__ __launch_bounds__(256) void ll_project_kernel(const AOp A, long long rows, int L, const double* __restrict__ B,
+                                                         int cols, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const int ct = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (ct * 32 >= cols) return;
+  const long long r0 = (long long)blockIdx.x * 32;
+  typename AOp::Row ra[2];
+  const double* pb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const long long r = r0 + 16 * t + i16;
+    ra[t] = A.row(r < rows ? r : rows - 1);                                                  // clamped: never written back
+    pb[t] = B + min(ct * 32 + 16 * t + i16, cols - 1);
+  }
+  ll_f64x4 acc[2][2];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  int l0 = 0;
+  // four k-steps per round, every load issued before the first product
+  for (; l0 + 16 <= L; l0 += 16) {
+    double a[4][2], b[4][2];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int l = l0 + 4 * s + q;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        a[s][t] = A.at(ra[t], l);
+        b[s][t] = pb[t][(long long)l * cols];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+          acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][tm], b[s][tn], acc[tm][tn], 0, 0, 0);
+  }
+  for (; l0 < L; l0 += 4) {
+    const int l = l0 + q;
+    const bool ok = l < L;
+    const int lc = ok ? l : L - 1;
+    double a[2], b[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const double av = A.at(ra[t], lc), bv = pb[t][(long long)lc * cols];
+      a[t] = ok ? av : 0.0;
+      b[t] = ok ? bv : 0.0;
+    }
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+  }
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long long row = r0 + 16 * tm + q + 4 * r;
+        const int col = ct * 32 + 16 * tn + i16;
+        if (row < rows && col < cols) out[row * cols + col] = (float)acc[tm][tn][r];
+      }
+}
+
+// can ll_project_kernel's grid take a (rows, cols) output?
+inline bool ll_project_fits(long long rows, int cols) { return (rows + 31) / 32 <= 0x7fffffffll && (cols + 127) / 128 <= 65535; }
+
 // (row, column) of lower-triangle tile number `tile`, rows first: tile = tr (tr + 1) / 2 + tc, tc <= tr
 __device__ __forceinline__ void ll_tri_tile(int tile, int& tr, int& tc) {
   tr = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
@@ -98,6 +176,17 @@ bool panel_gram_fits(int R, int S);
 long long panel_gram_scratch(int R, int S);
 hipError_t launch_panel_gram(const float* panel, int R, int S, double* G, double* part, hipStream_t st);
 hipError_t launch_gram_assemble(const double* part, long long tiles, int ys, int S, double* G, hipStream_t st);
+
+// The two projections of the EIGEN sweep of lip_engine.hip, on operands the caller has checked (the entry points
+// lip_kfac_project_patches / lip_rows_project check and then call these):
+//   AV ((n OH OW), Mt) = patches(X) V      (lip_kfac.hip; the geometry arguments of lip_kfac_input_gram)
+//   GU ((P R), N)      = G Ub              (lip_subnetwork.hip; row r of probe p at G + p pstride + r ldg)
+// and the fold of a pass's float32 sums into a block's float64 second moments, Lam[e] += y[e].
+hipError_t launch_project_patches(const float* X, int n, int IH, int IW, int C, int KH, int KW, int stride, int pad_h,
+                                  int pad_w, int OH, int OW, int bias, const double* V, float* AV, hipStream_t st);
+hipError_t launch_rows_project(const float* G, long long ldg, long long pstride, int P, int R, int N, const double* Ub,
+                               float* GU, hipStream_t st);
+hipError_t launch_eigen_fold(const float* y, long long E, double* Lam, hipStream_t st);
 
 }  // namespace lip
 

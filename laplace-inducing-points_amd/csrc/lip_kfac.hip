@@ -21,6 +21,10 @@
 //   Lam[j][l]     += sum_{r < R} T_r[j][l]^2
 // Stage one is the predictive's (kfac_jub_kernel with Kc = 1); stage two forms V^T W_r tile by tile, squares it in
 // registers and sums over groups of rows, so T is never written; the groups' partial sums are folded in group order.
+//
+// Patch projection (lip_kfac_project_patches, for the EIGEN sweep of lip_engine.hip, which forms the same Lam without
+// factor rows):  AV[(i,t)][j] = sum_e at_{i,t}[e] V[e][j], float32, rounded once.  ll_project_kernel (lip_gramtile.h)
+// with an operand functor that gathers the patch entries as the input Gram's does.
 #include <algorithm>
 #include "lip_internal.h"
 #include "lip_gramtile.h"
@@ -366,6 +370,59 @@ __global__ __launch_bounds__(256) void kfac_sqsum_fold_kernel(const double* __re
   Lam[e] += t;
 }
 
+// The A operand of ll_project_kernel for the patch projection AV = patches(X) V: row i = (image, oh, ow), element e the
+// patch entry KfacPatchOperands gathers ((kh, kw, ci) order after the leading 1 of a bias; zero outside the image; the
+// address clamped, so nothing outside X is read)
+struct KfacPatchRows {
+  const float* __restrict__ X;
+  int IH, IW, C, KW, stride, pad_h, pad_w, bias, OHW, OW;
+  FastDiv dOHW, dOW, dC, dKW;
+  struct Row {
+    long long img;
+    int h0, w0;                                       // input row / column of the window's tap (0, 0)
+  };
+  __device__ __forceinline__ Row row(long long r) const {
+    const int i = (int)r, img = dOHW.div(i), t = i - img * OHW;
+    const int oh = dOW.div(t), ow = t - oh * OW;
+    return Row{(long long)img, oh * stride - pad_h, ow * stride - pad_w};
+  }
+  __device__ __forceinline__ double at(const Row& r, int e) const {
+    e -= bias;
+    const int ec = max(e, 0);
+    const int k = dC.div(ec), ci = ec - k * C;
+    const int kh = dKW.div(k), kw = k - kh * KW;
+    const int ih = r.h0 + kh, iw = r.w0 + kw;
+    const bool in = ih >= 0 && ih < IH && iw >= 0 && iw < IW;
+    const int ihc = min(max(ih, 0), IH - 1), iwc = min(max(iw, 0), IW - 1);                   // clamped: the load stays inside
+    const float v = X[((r.img * IH + ihc) * IW + iwc) * C + ci];
+    return e < 0 ? 1.0 : (in ? (double)v : 0.0);
+  }
+};
+
+// Lam[e] += y[e]: a thread per entry
+__global__ __launch_bounds__(256) void kfac_eigen_fold_kernel(const float* __restrict__ y, long long E, double* __restrict__ Lam) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e < E) Lam[e] += (double)y[e];
+}
+
+hipError_t launch_project_patches(const float* X, int n, int IH, int IW, int C, int KH, int KW, int stride, int pad_h,
+                                  int pad_w, int OH, int OW, int bias, const double* V, float* AV, hipStream_t st) {
+  KfacPatchRows A;
+  A.X = X, A.IH = IH, A.IW = IW, A.C = C, A.KW = KW, A.stride = stride, A.pad_h = pad_h, A.pad_w = pad_w;
+  A.bias = bias ? 1 : 0, A.OHW = OH * OW, A.OW = OW;
+  A.dOHW = FastDiv((unsigned)(OH * OW)), A.dOW = FastDiv((unsigned)OW), A.dC = FastDiv((unsigned)C), A.dKW = FastDiv((unsigned)KW);
+  const int Mt = KH * KW * C + A.bias;
+  const long long rows = (long long)n * OH * OW;
+  hipLaunchKernelGGL(ll_project_kernel<KfacPatchRows>, dim3((unsigned)((rows + 31) / 32), (unsigned)((Mt + 127) / 128)), dim3(256),
+                     0, st, A, rows, Mt, V, Mt, AV);
+  return hipGetLastError();
+}
+
+hipError_t launch_eigen_fold(const float* y, long long E, double* Lam, hipStream_t st) {
+  hipLaunchKernelGGL(kfac_eigen_fold_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, y, E, Lam);
+  return hipGetLastError();
+}
+
 }  // namespace lip
 
 using namespace lip;
@@ -428,6 +485,20 @@ int lip_kfac_input_gram(const float* X, int32_t n, int32_t IH, int32_t IW, int32
                      FastDiv((unsigned)(OH * OW)), FastDiv((unsigned)OW), scratch);
   LIP_CHECK_HIP(hipGetLastError());
   LIP_CHECK_HIP(launch_gram_assemble(scratch, pl.tiles, pl.ys, g.Mt, A, st));
+  return LIP_OK;
+}
+
+int lip_kfac_project_patches(const float* X, int32_t n, int32_t IH, int32_t IW, int32_t C, int32_t KH, int32_t KW,
+                             int32_t stride, int32_t pad_h, int32_t pad_w, int32_t OH, int32_t OW, int32_t bias, const double* V,
+                             float* AV, void* stream) {
+  const KfacGeom g = kfac_geom(IH, IW, C, KH, KW, stride, pad_h, pad_w, OH, OW, bias);
+  if (!X || !V || !AV || !kfac_geom_ok(n, g)) { set_error("lip_kfac_project_patches: bad argument"); return LIP_ERR_ARG; }
+  const long long rows = (long long)n * OH * OW;
+  if (!kfac_fits(n, g) || rows * g.Mt >= (1ll << 31) || (long long)g.Mt * g.Mt >= (1ll << 31) || !ll_project_fits(rows, g.Mt)) {
+    set_error("lip_kfac_project_patches: a tensor of 2^31 or more elements; pass fewer images per call");
+    return LIP_ERR_ARG;
+  }
+  LIP_CHECK_HIP(launch_project_patches(X, n, IH, IW, C, KH, KW, stride, pad_h, pad_w, OH, OW, g.bias, V, AV, (hipStream_t)stream));
   return LIP_OK;
 }
 

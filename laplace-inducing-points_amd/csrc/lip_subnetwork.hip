@@ -246,6 +246,31 @@ static void sub_gather(const float* W, long long ldw, long long D, long long R, 
                      (const long long*)idx, S, K, B, panel);
 }
 
+// The A operand of ll_project_kernel for GU = G Ub: the float32 rows of a cotangent block, row r at G + r ldg
+struct PanelRows {
+  const float* __restrict__ G;
+  long long ldg;
+  typedef const float* Row;
+  __device__ __forceinline__ Row row(long long r) const { return G + r * ldg; }
+  __device__ __forceinline__ double at(Row r, int l) const { return (double)r[l]; }
+};
+
+// One launch over all P R rows when the probes are adjacent (one probe, or the per-probe stride is the row block), else
+// one launch per probe: the rule of the KRON sweep's Grams
+hipError_t launch_rows_project(const float* G, long long ldg, long long pstride, int P, int R, int N, const double* Ub,
+                               float* GU, hipStream_t st) {
+  const bool packed = P == 1 || pstride == (long long)R * ldg;
+  const long long rows = packed ? (long long)P * R : R;
+  const dim3 grid((unsigned)((rows + 31) / 32), (unsigned)((N + 127) / 128));
+  for (int p = 0; p < (packed ? 1 : P); ++p) {
+    hipLaunchKernelGGL(ll_project_kernel<PanelRows>, grid, dim3(256), 0, st, PanelRows{G + p * pstride, ldg}, rows, N, Ub, N,
+                       GU + (long long)p * R * N);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+
 }  // namespace lip
 
 using namespace lip;
@@ -261,6 +286,20 @@ int lip_sub_gather(const float* W, int64_t ldw, int64_t D, int32_t R, const int6
   if (!W || !idx || !panel || R <= 0 || S <= 0 || D <= 0 || ldw < D) { set_error("lip_sub_gather: bad argument"); return LIP_ERR_ARG; }
   sub_gather(W, (long long)ldw, (long long)D, R, idx, S, 0, 0, panel, (hipStream_t)stream);
   LIP_CHECK_HIP(hipGetLastError());
+  return LIP_OK;
+}
+
+int lip_rows_project(const float* G, int64_t ldg, int64_t pstride, int32_t P, int32_t R, int32_t N, const double* Ub, float* GU,
+                     void* stream) {
+  if (!G || !Ub || !GU || P <= 0 || R <= 0 || N <= 0 || ldg < N || (P > 1 && pstride < (long long)(R - 1) * ldg + N)) {
+    set_error("lip_rows_project: bad argument");
+    return LIP_ERR_ARG;
+  }
+  if ((long long)P * R * N >= (1ll << 31) || (long long)N * N >= (1ll << 31) || !ll_project_fits((long long)P * R, N)) {
+    set_error("lip_rows_project: a tensor of 2^31 or more elements; pass fewer rows per call");
+    return LIP_ERR_ARG;
+  }
+  LIP_CHECK_HIP(launch_rows_project(G, (long long)ldg, (long long)pstride, P, R, N, Ub, GU, (hipStream_t)stream));
   return LIP_OK;
 }
 

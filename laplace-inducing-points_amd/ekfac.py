@@ -23,8 +23,16 @@ The precision is D^-1 (D G D + I) D^-1 and diag((U_t (x) Ub)^T D G D (U_t (x) Ub
 predictive (``lip_kfac_predict``), the draws and the JVP route run unchanged.  The parameters outside every block keep
 the exact GGN diagonal.
 
-Cost: the fit needs the M K factor rows of width D once, in class blocks of at most ``ROW_BLOCK_BYTES``, next to the
-KFAC fit.  It is meant for heads with few outputs, like the closed-form KFAC predictive, not for K = 1000.
+Cost: the default fit (``moments="rows"``) needs the M K factor rows of width D once, in class blocks of at most
+``ROW_BLOCK_BYTES``, next to the KFAC fit.  It is meant for heads with few outputs, like the closed-form KFAC predictive,
+not for K = 1000.
+
+``moments="sweep"`` forms the same Lam without any row: the block's slice of a row is the per-example weight gradient
+At_i^T G_i diag(s) (At_i the im2col patches, G_i the cotangent rows of the layer, s the frozen BN scale), so
+V^T mat_l(.) Ub = (At_i V)^T (G_i diag(s) Ub), and one backward sweep projects both operands per layer and square-sums the
+per-(probe, example) products (:meth:`LinearizedNet.kfac_eigen_sqsums_sweep`, ``lip_vjp_eigen``).  That route also takes
+the curvature specs of ``fisher.py`` (``curvature=``; the basis' KFAC factors and the remainder's diagonal then use the
+same spec), which makes the fit usable at K = 1000.
 """
 from __future__ import annotations
 
@@ -41,18 +49,50 @@ from .last_layer_kron import _eigh, centre
 from .utils import flatten_nn_params
 
 
+MOMENTS = ("rows", "sweep")
+
+
+def _route(moments, curvature):
+    """the checked ``moments`` of a fit: a curvature spec implies the sweep when ``moments`` is left at None, and is
+    refused with the rows route; ``ValueError`` before anything is bound"""
+    from . import fisher
+    spec = fisher.resolve(curvature)
+    if moments is None:
+        moments = "rows" if spec is None else "sweep"
+    if moments not in MOMENTS:
+        raise ValueError(f"moments must be 'rows' or 'sweep', got {moments!r}")
+    if spec is not None and moments == "rows":
+        raise ValueError("a curvature spec is taken by moments='sweep' only: the rows route pushes the K one-hot probes "
+                         "of the exact GGN")
+    return moments
+
+
 def compute_ekfac_scales(state, Z, model_type, bases, example_chunk: Optional[int] = None,
-                         class_chunk: Optional[int] = None) -> List[torch.Tensor]:
+                         class_chunk: Optional[int] = None, *, moments: str = "rows", curvature=None) -> List[torch.Tensor]:
     """``[Lam_l (Mt, N)]``: sum_i sum_k (V_l^T mat_l(J_i^T L_i e_k) Ub_l)^2 over the M = len(Z) examples for the
-    ``bases[l] = (V_l, Ub_l)`` of every layer block, float64 on the device, unscaled
-    (:meth:`LinearizedNet.kfac_eigen_sqsums`); chunked like :func:`kfac.compute_kfac_factors`, all chunks add into one
-    matrix per block."""
+    ``bases[l] = (V_l, Ub_l)`` of every layer block, float64 on the device, unscaled; chunked like
+    :func:`kfac.compute_kfac_factors`, all chunks add into one matrix per block.  ``moments="rows"`` reads the factor
+    rows (:meth:`LinearizedNet.kfac_eigen_sqsums`); ``moments="sweep"`` forms the same sums inside backward sweeps
+    without any D-wide row (:meth:`LinearizedNet.kfac_eigen_sqsums_sweep`) and also takes a ``curvature`` spec of
+    ``fisher.py``: (1 / divisor) sum_p sum_i (V_l^T mat_l(J_i^T u_pi) Ub_l)^2 over that spec's raw cotangents."""
+    from . import fisher
+    moments = _route(moments, curvature)
+    spec = fisher.checked(curvature, state, Z, model_type)
     blocks = _kfac.block_table(state)
     engines = _engines(state, Z, model_type, None, example_chunk)
     dev = engines[0].device
     Lams = [torch.zeros(b.Mt, b.N, device=dev, dtype=torch.float64) for b in blocks]
-    for eng in engines:
-        eng.kfac_eigen_sqsums(bases, Lams, class_chunk=class_chunk)
+    if moments == "rows":
+        for eng in engines:
+            eng.kfac_eigen_sqsums(bases, Lams, class_chunk=class_chunk)
+    elif spec is None:
+        for eng in engines:
+            eng.kfac_eigen_sqsums_sweep(bases, Lams, class_chunk=class_chunk)
+    else:
+        source = fisher.source_for(spec, state, Z, model_type)
+        for j, eng in enumerate(engines):
+            U, divisor = source(eng, j * example_chunk if len(engines) > 1 else 0)
+            eng.kfac_eigen_sqsums_sweep(bases, Lams, class_chunk=class_chunk, probes=U, divisor=divisor)
     return Lams
 
 
@@ -62,22 +102,25 @@ def corrected_fits(fits, Lams, recal: float):
     return [(f[0], (1.0 / (recal * Lam.clamp_min(0.0) + 1.0)).contiguous(), f[2]) for f, Lam in zip(fits, Lams)]
 
 
-def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk):
-    """(blocks, [(V, R, Ub)], rem_idx, rem_var, rem_prior); the prior is checked before anything is allocated"""
+def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments="rows", curvature=None):
+    """(blocks, [(V, R, Ub)], rem_idx, rem_var, rem_prior); the prior is checked before anything is allocated.  Under a
+    curvature spec the KFAC factors that give the basis, the second moments and the remainder's diagonal all use it."""
     blocks = _kfac.block_table(map_state)
     D = flatten_nn_params(map_state.params)[0].numel()
     rows = [_kfac.block_prior_rows(alpha, b, D) for b in blocks]
     rem = _kfac.remainder_indices(blocks, D)
     a_rem = _kfac._remainder_prior(alpha, rem, D)
-    blocks, As, Ss, M = _kfac.compute_kfac_factors(map_state, Z, model_type, example_chunk=example_chunk)
+    blocks, As, Ss, M = _kfac.compute_kfac_factors(map_state, Z, model_type, example_chunk=example_chunk, curvature=curvature)
     recal = _recal(map_state, M, model_type, full_set_size)
     kfits = _kfac.fit_blocks(blocks, As, Ss, rows, recal, M, model_type != "regressor")
-    Lams = compute_ekfac_scales(map_state, Z, model_type, [(f[0], f[2]) for f in kfits], example_chunk=example_chunk)
+    Lams = compute_ekfac_scales(map_state, Z, model_type, [(f[0], f[2]) for f in kfits], example_chunk=example_chunk,
+                                **_route_kwargs(moments, curvature))
     fits = corrected_fits(kfits, Lams, recal)
     dev = As[0].device
     rem_var = torch.zeros(0, device=dev, dtype=torch.float64)
     if rem.numel():
-        diag = _ggn.compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk)
+        diag = _ggn.compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk,
+                                     curvature=curvature)
         rem_var = 1.0 / (a_rem.to(dev) + diag.double()[rem.to(dev)])
     return blocks, fits, rem.to(dev), rem_var, a_rem.to(dev)
 
@@ -85,16 +128,36 @@ def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk):
 _FIT_CACHE = {}          # one entry, as kfac._FIT_CACHE
 
 
-def _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk):
-    """the fit, computed once per (binding, prior, N, chunking); ``clear_engine_cache`` drops the entry"""
+def _route_kwargs(moments, curvature):
+    """the keywords of :func:`compute_ekfac_scales` for a route: none for the default, so the rows route is called as
+    it always was"""
+    kw = {}
+    if moments != "rows":
+        kw["moments"] = moments
+    if curvature is not None:
+        kw["curvature"] = curvature
+    return kw
+
+
+def _fit_key(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments, curvature):
+    """the cache key of a fit: (binding, prior, N, chunking, moments route, curvature spec)"""
+    from .fisher import spec_key
+    return (_ggn.engine_key(map_state, Z, model_type), _kfac._prior_key(alpha), full_set_size, example_chunk, moments,
+            spec_key(curvature))
+
+
+def _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments=None, curvature=None):
+    """the fit, computed once per (binding, prior, N, chunking, moments route, curvature spec); ``clear_engine_cache``
+    drops the entry"""
+    moments = _route(moments, curvature)
     if _FIT_CACHE.clear not in _ggn._CLEAR_HOOKS:
         _ggn._CLEAR_HOOKS.append(_FIT_CACHE.clear)
-    key = (_ggn.engine_key(map_state, Z, model_type), _kfac._prior_key(alpha), full_set_size, example_chunk)
+    key = _fit_key(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments, curvature)
     hit = _FIT_CACHE.get(key)
     if hit is None:
-        fit = _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+        fit = _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments, curvature)
         _FIT_CACHE.clear()
-        hit = _FIT_CACHE[key] = (fit, (map_state.params, map_state.batch_stats, Z))
+        hit = _FIT_CACHE[key] = (fit, (map_state.params, map_state.batch_stats, Z, curvature))
     return hit[0]
 
 
@@ -108,31 +171,38 @@ def posterior_from_fit(flat: torch.Tensor, blocks, fits, rem_idx, rem_var, rem_p
     return KFACNormal(loc, parts, (rem_idx, rem_var), remainder_prior=rem_prior)
 
 
-def posterior_lla_ekfac(map_state, Z, model_type, alpha, full_set_size=None, example_chunk: Optional[int] = None) -> KFACNormal:
+def posterior_lla_ekfac(map_state, Z, model_type, alpha, full_set_size=None, example_chunk: Optional[int] = None, *,
+                        moments: Optional[str] = None, curvature=None) -> KFACNormal:
     """N(theta_MAP, blockdiag((V_l (x) Ub_l) diag(R_l) (V_l (x) Ub_l)^T, remainder)) over the whole flat vector in
     factored form, float64 on the device, R_l from the eigenbasis second moments of the module docstring; nothing of
-    size D x D, and no Mt N x Mt N matrix, is built.  The fit is cached per (state, Z, prior, N, chunking) (a one-entry
-    cache)."""
-    blocks, fits, rem_idx, rem_var, rem_prior = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+    size D x D, and no Mt N x Mt N matrix, is built.  The fit is cached per (state, Z, prior, N, chunking, moments,
+    curvature spec) (a one-entry cache).  ``moments``: "rows" (the default without a spec) or "sweep"
+    (:func:`compute_ekfac_scales`); ``curvature``: a spec of ``fisher.py`` for the basis' factors, the second moments
+    and the remainder's diagonal, which implies the sweep."""
+    blocks, fits, rem_idx, rem_var, rem_prior = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk,
+                                                            moments, curvature)
     flat, _ = flatten_nn_params(map_state.params)
     return posterior_from_fit(flat, blocks, fits, rem_idx, rem_var, rem_prior)
 
 
 def predict_lla_ekfac(map_state, Xnew, Z, model_type, alpha, full_set_size=None, cov: str = "full", batch: int = 256,
-                      example_chunk: Optional[int] = None):
+                      example_chunk: Optional[int] = None, *, moments: Optional[str] = None, curvature=None):
     """Closed-form linearised predictive of :func:`posterior_lla_ekfac` (:meth:`LinearizedNet.kfac_predict` with the
     corrected R), in the return shapes and types, and with the batching and refusals, of :func:`kfac.predict_lla_kfac`."""
     if cov not in ("diag", "full"):
         raise ValueError("cov must be 'diag' or 'full'")
-    _, fits, rem_idx, rem_var, _ = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk)
+    _, fits, rem_idx, rem_var, _ = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments,
+                                               curvature)
     return _kfac.predictive_from_fit(map_state, Xnew, model_type, fits, (rem_idx, rem_var), cov, batch)
 
 
 def predict_lla_ekfac_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1,
-                               example_chunk: Optional[int] = None) -> torch.Tensor:
+                               example_chunk: Optional[int] = None, *, moments: Optional[str] = None,
+                               curvature=None) -> torch.Tensor:
     """Draws of the outputs under :func:`posterior_lla_ekfac`: f(x; theta_MAP) + J(x) d_theta_s -> (S, B, K) float32
     through the engine's JVP, as :func:`kfac.predict_lla_kfac_scalable` draws them."""
-    post = posterior_lla_ekfac(map_state, Z, model_type, alpha, full_set_size=full_set_size, example_chunk=example_chunk)
+    post = posterior_lla_ekfac(map_state, Z, model_type, alpha, full_set_size=full_set_size, example_chunk=example_chunk,
+                               moments=moments, curvature=curvature)
     return _kfac.draws_from_posterior(post, map_state, Xnew, model_type, key, num_samples)
 
 
@@ -143,13 +213,15 @@ def orthonormal_bases(blocks, As, Ss, classifier: bool):
             for b, A, S in zip(blocks, As, Ss)]
 
 
-def _spectrum_ekfac(X, state, model_type) -> Tuple[torch.Tensor, int, float]:
+def _spectrum_ekfac(X, state, model_type, *, moments: Optional[str] = None, curvature=None) -> Tuple[torch.Tensor, int, float]:
     """eigenvalues (float64, clamped at 0) of the eigenvalue-corrected curvature built at N/M = 1 (x exp(-logvar) for the
     regressor): the concatenation of Lam0_l, the second moments in the orthonormal basis U_t (x) Ub summed over the M
     examples (the diagonal of Q^T (sum_i J_i^T H_i J_i) Q, where KFAC has outer(lam_l, mu_l) / (M T_l)), with the
     remainder's GGN diagonal appended, D, ||theta||^2.  For a scalar prior the basis does not depend on alpha."""
-    blocks, As, Ss, M = _kfac.compute_kfac_factors(state, X, model_type)
-    Lams = compute_ekfac_scales(state, X, model_type, orthonormal_bases(blocks, As, Ss, model_type != "regressor"))
+    moments = _route(moments, curvature)
+    blocks, As, Ss, M = _kfac.compute_kfac_factors(state, X, model_type, curvature=curvature)
+    Lams = compute_ekfac_scales(state, X, model_type, orthonormal_bases(blocks, As, Ss, model_type != "regressor"),
+                                **_route_kwargs(moments, curvature))
     spec = torch.cat([Lam.clamp_min(0.0).reshape(-1) for Lam in Lams])
     if model_type == "regressor":
         spec = spec * math.exp(-_ggn._logvar(state))
@@ -157,6 +229,6 @@ def _spectrum_ekfac(X, state, model_type) -> Tuple[torch.Tensor, int, float]:
     D = flat.numel()
     rem = _kfac.remainder_indices(blocks, D)
     if rem.numel():
-        diag = _ggn.compute_ggn_diag(state, X, model_type)
+        diag = _ggn.compute_ggn_diag(state, X, model_type, curvature=curvature)
         spec = torch.cat([spec, diag.double()[rem.to(diag.device)].clamp_min(0.0)])
     return spec, D, float((flat.detach().double() ** 2).sum())

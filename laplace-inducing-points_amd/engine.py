@@ -1078,6 +1078,65 @@ class LinearizedNet:
                          "lip_kfac_eigen_sqsum")
         return Lams
 
+    def kfac_eigen_sqsums_sweep(self, bases, Lams: List[torch.Tensor], class_chunk: Optional[int] = None,
+                                probes: Optional[torch.Tensor] = None, divisor: float = 1.0) -> List[torch.Tensor]:
+        """:meth:`kfac_eigen_sqsums` from backward sweeps instead of factor rows (``lip_vjp_eigen``): the block's slice of
+        a row is the per-example weight gradient At_i^T G_i diag(s), so V^T mat_l(.) Ub = (At_i V)^T (G_i diag(s) Ub) and
+        every WGRAD op of the sweep projects its patches and its cotangent rows and square-sums the per-(probe, example)
+        products of the pair; no D-wide row exists.  Same operand checks and the same ADD into ``Lams``; the frozen BN
+        scale of a block is folded into its Ub here, in float64.  The probes are chunked as in
+        :meth:`kfac_output_grams`: one-hot 'l' probes in class blocks, or a raw (P, n, K) block ``probes`` whose sums
+        are divided by ``divisor`` before they are added (``fisher.py``).  The sums of a sweep are float32 (those of
+        ``lip_vjp_sqsum``), added to ``Lams`` in float64 pass by pass."""
+        blocks = self.kfac_blocks()
+        if len(bases) != len(blocks) or len(Lams) != len(blocks):
+            raise ValueError(f"{len(blocks)} layer blocks need {len(blocks)} (V, Ub) pairs in bases and {len(blocks)} matrices in Lams")
+        for b, (V, Ub), Lam in zip(blocks, bases, Lams):
+            for name, t, shape in (("V", V, (b.Mt, b.Mt)), ("Ub", Ub, (b.N, b.N)), ("Lam", Lam, (b.Mt, b.N))):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"{name} of the block at offset {b.off} must be a contiguous float64 device matrix of "
+                                     f"{shape[0]} x {shape[1]}")
+        cap = len(blocks)
+        koff, ooff, Ns = (C.c_int64 * cap)(), (C.c_int64 * cap)(), (C.c_int32 * cap)()
+        count, total = C.c_int32(0), C.c_int64(0)
+        nv.check(self.lib.lip_vjp_kron_layout(self.h, cap, koff, ooff, Ns, C.byref(count), C.byref(total)), "lip_vjp_kron_layout")
+        order = {int(koff[i]): i for i in range(min(cap, count.value))}
+        if count.value != cap or any(b.kernel_off not in order or int(Ns[order[b.kernel_off]]) != b.N for b in blocks):
+            raise nv.NativeError("lip_vjp_kron_layout: the backward tape's weight gradients do not match the layer blocks")
+        divided = probes is not None and divisor != 1.0
+        Ubs, outs = [], []
+        for b, (V, Ub), Lam in zip(blocks, bases, Lams):
+            if b.bn is not None:
+                Ub = (self.consts[b.bn[0]:b.bn[0] + b.N].double()[:, None] * Ub).contiguous()
+            Ubs.append(Ub)
+            outs.append(torch.zeros_like(Lam) if divided else Lam)
+        Vp, Up, Lp, Mts = (C.c_void_p * cap)(), (C.c_void_p * cap)(), (C.c_void_p * cap)(), (C.c_int32 * cap)()
+        for b, (V, _), Ub, out in zip(blocks, bases, Ubs, outs):
+            k = order[b.kernel_off]
+            Vp[k], Up[k], Lp[k], Mts[k] = V.data_ptr(), Ub.data_ptr(), out.data_ptr(), b.Mt
+        if probes is None:
+            eye = torch.eye(self.K, device=self.device, dtype=torch.float32)
+            sweeps = ((eye[k0:k1, None, :].expand(k1 - k0, self.n, self.K).contiguous(), nv.HEAD_L)
+                      for k0, k1 in self._class_blocks(class_chunk))
+        else:
+            U, head = self._cotangents(probes, "raw")
+            pc = max(1, (self.ROW_BLOCK_BYTES // (4 * self.D)) // self.n)        # the cap of _class_blocks, not cut at K
+            pc = pc if class_chunk is None else max(1, min(pc, int(class_chunk)))
+            sweeps = ((U[p0:p0 + pc], head) for p0 in range(0, U.shape[0], pc))
+        for E, head in sweeps:
+            floats = C.c_int64(0)
+            nv.check(self.lib.lip_vjp_eigen_scratch(self.h, E.shape[0], C.byref(floats)), "lip_vjp_eigen_scratch")
+            scratch = self._scratches.get("lip_vjp_eigen")
+            if scratch is None or scratch.numel() < floats.value:
+                scratch = self._scratches["lip_vjp_eigen"] = torch.empty(max(4, floats.value), device=self.device,
+                                                                         dtype=torch.float32)
+            nv.check(self.lib.lip_vjp_eigen(self.h, nv.ptr(E), Vp, Up, Lp, Mts, cap, E.shape[0], head, 1.0,
+                                            scratch.data_ptr(), scratch.numel(), nv.stream_ptr()), "lip_vjp_eigen")
+        if divided:
+            for Lam, out in zip(Lams, outs):
+                Lam += out / float(divisor)
+        return Lams
+
     # ------------------------------------------------------------------------------ measurement
     def profile(self, enable: bool):
         nv.check(self.lib.lip_engine_profile(self.h, int(enable)), "lip_engine_profile")

@@ -151,15 +151,16 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
     (``lla.predict_lla_ekfac``, fitted once for all batches), ``"lowrank"``: the low-rank posterior from the ``rank``
     leading eigenpairs of the GGN of Z (``lla.predict_lla_lowrank``, fitted once for all batches; ``rank`` is read by this
     value alone, ``None``: ``lowrank.DEFAULT_RANK``).  ``curvature``: a spec of ``fisher.py`` for the fit of
-    ``posterior="diag"`` and ``"kfac"``; the other posteriors refuse one.
+    ``posterior="diag"``, ``"kfac"`` and ``"ekfac"`` (whose second moments then come from the backward sweep,
+    ``moments="sweep"``); the other posteriors refuse one.
     -> (NLL, accuracy, Brier, ECE, probs, labels)"""
     from .lla import (predict_lla_diag, predict_lla_ekfac, predict_lla_kfac, predict_lla_last_layer, predict_lla_last_layer_kron,
                       predict_lla_lowrank, predict_lla_subnetwork, predict_lla_variances, probit_predictive)
     rank_kw = {} if rank is None else {"rank": rank}
     curv_kw = {}
     if curvature is not None:
-        if posterior not in ("diag", "kfac"):
-            raise ValueError(f"curvature is taken by posterior='diag' and 'kfac' only, not {posterior!r}")
+        if posterior not in ("diag", "kfac", "ekfac"):
+            raise ValueError(f"curvature is taken by posterior='diag', 'kfac' and 'ekfac' only, not {posterior!r}")
         curv_kw = {"curvature": curvature}
     if posterior == "subnetwork" and indices is None:
         raise ValueError("posterior='subnetwork' needs indices")

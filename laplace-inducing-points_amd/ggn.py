@@ -286,11 +286,13 @@ def compute_kfac_factors(state, Z, model_type, example_chunk: Optional[int] = No
 
 
 def compute_ekfac_scales(state, Z, model_type, bases, example_chunk: Optional[int] = None,
-                         class_chunk: Optional[int] = None):
+                         class_chunk: Optional[int] = None, *, moments: str = "rows", curvature=None):
     """``[Lam_l (Mt, N)]``: the second moments of the per-example factor rows in the Kronecker eigenbasis
-    ``bases[l] = (V_l, Ub_l)`` of every layer block, float64, unscaled (:func:`ekfac.compute_ekfac_scales`)."""
+    ``bases[l] = (V_l, Ub_l)`` of every layer block, float64, unscaled (:func:`ekfac.compute_ekfac_scales`);
+    ``moments="sweep"`` forms them inside backward sweeps without factor rows and takes a ``curvature`` spec."""
     from . import ekfac
-    return ekfac.compute_ekfac_scales(state, Z, model_type, bases, example_chunk=example_chunk, class_chunk=class_chunk)
+    return ekfac.compute_ekfac_scales(state, Z, model_type, bases, example_chunk=example_chunk, class_chunk=class_chunk,
+                                      moments=moments, curvature=curvature)
 
 
 def compute_ggn_lowrank(state, Z, model_type, rank, prior=None, example_chunk: Optional[int] = None, **solver):

@@ -173,22 +173,27 @@ def fit_alpha_kfac(X, state, model_type, full_set_size=None, alpha0: float = 1.0
     return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
-def log_marginal_likelihood_ekfac(alpha, X, state, model_type: str, full_set_size: Optional[int] = None) -> float:
+def log_marginal_likelihood_ekfac(alpha, X, state, model_type: str, full_set_size: Optional[int] = None, *,
+                                  moments: Optional[str] = None, curvature=None) -> float:
     """:func:`log_marginal_likelihood_kfac` under the eigenvalue-corrected curvature (``ekfac.py``): in the spectrum every
     block's outer(lam_l, mu_l) / (M T_l) is replaced by the second moments of the factor rows in the block's orthonormal
-    Kronecker eigenbasis, which a scalar alpha does not move.  Scalar alpha.  Not a reference function."""
+    Kronecker eigenbasis, which a scalar alpha does not move.  Scalar alpha.  ``moments`` / ``curvature``: the route of
+    the second moments and the curvature spec of ``fisher.py`` (:func:`ekfac.posterior_lla_ekfac`).  Not a reference
+    function."""
     from .ekfac import _spectrum_ekfac
     N = full_set_size or X.shape[0]
-    lam, D, theta2 = _spectrum_ekfac(X, state, model_type)
+    lam, D, theta2 = _spectrum_ekfac(X, state, model_type, moments=moments, curvature=curvature)
     return _lml_from_spectrum(float(alpha), lam, D, theta2, N / X.shape[0])[0]
 
 
-def fit_alpha_ekfac(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200):
+def fit_alpha_ekfac(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200, *,
+                    moments: Optional[str] = None, curvature=None):
     """:func:`fit_alpha` on the eigenvalue-corrected evidence: ``(alpha, history)``; the factors, their
-    eigendecompositions and the pass over the factor rows are computed once."""
+    eigendecompositions and the second moments (``moments`` / ``curvature`` as in
+    :func:`log_marginal_likelihood_ekfac`) are computed once."""
     from .ekfac import _spectrum_ekfac
     N = full_set_size or X.shape[0]
-    lam, D, theta2 = _spectrum_ekfac(X, state, model_type)
+    lam, D, theta2 = _spectrum_ekfac(X, state, model_type, moments=moments, curvature=curvature)
     return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
 
 
