@@ -460,6 +460,26 @@ int lip_vjp_eigen_scratch(lip_engine_t* e, int32_t P, int64_t* floats);
 int lip_vjp_eigen(lip_engine_t* e, const float* U, const double* const* V, const double* const* Ub, double* const* Lam,
                   const int32_t* Mt, int32_t nblocks, int32_t P, int32_t head_mode, float c, float* scratch,
                   int64_t scratch_floats, void* stream);
+/* The other reduction of the same products, ADDED into out (P n,) float32 like lip_vjp_wnorm: the predictive of a
+ * Kronecker-factored posterior without any D-wide row,
+ *   out[p n + i] += sum_k sum_{j,m} Rw[k][j][m] ( ((At_i V[k])^T (G_pi Ub[k]))[j][m] )^2  +  sum_{d in reductions} w_rem[d] (J_i^T u_p)_d^2.
+ * Every WGRAD op projects its operands exactly as lip_vjp_eigen does and hands the projected pair (C = Mt, 1x1, stride
+ * 1, no padding, no scale) to the weighted-norm weight gradient of lip_vjp_wnorm with the block's weights Rw[k]: a
+ * device (Mt, N) row-major FLOAT32 matrix (at OH OW = 1 the bilinear route (av^2)^T Rw (gu^2)).  V, Ub, Rw, Mt: host
+ * arrays of nblocks entries in tape order, as in lip_vjp_eigen.  w_rem: a (D,) float32 device vector addressed as the w
+ * of lip_vjp_wnorm and read ONLY at the slices of the bias / BN reductions; the bias of a block with a bias row is
+ * already counted by the block (its row 0), so the caller passes w_rem = 0 on every parameter inside a block.  w_rem
+ * may be NULL: then no reduction is launched at all.  head_mode: LIP_HEAD_IN or LIP_HEAD_L.  scratch: device, 16-byte
+ * aligned, >= lip_vjp_eigen_wnorm_scratch(e, P) floats (per op n OH OW Mt + P' n OH OW N floats and one float per
+ * (output tile, pair) of the weighted norm, P' the probes of a pass; the largest op, against the reductions' need).
+ * No atomics; the tiles of an op and the ops of the tape add in a fixed order and probe passes write disjoint slices:
+ * bitwise reproducible.  Every op of every pass is checked before the first launch: a null operand, nblocks other than
+ * the number of WGRAD ops, an Mt[k] that is not the op's KH KW C (+ 1), 2^31 or more elements of an operand on a pass,
+ * or a scratch below the query returns LIP_ERR_ARG and leaves out untouched; LIP_ERR_STATE as lip_vjp_sqsum. */
+int lip_vjp_eigen_wnorm_scratch(lip_engine_t* e, int32_t P, int64_t* floats);
+int lip_vjp_eigen_wnorm(lip_engine_t* e, const float* U, const double* const* V, const double* const* Ub,
+                        const float* const* Rw, const int32_t* Mt, int32_t nblocks, const float* w_rem, float* out, int32_t P,
+                        int32_t head_mode, float c, float* scratch, int64_t scratch_floats, void* stream);
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);

@@ -129,6 +129,9 @@ SIGNATURES = {
     "lip_vjp_eigen_scratch": (C.c_int, [_V, C.c_int32, C.POINTER(C.c_int64)]),
     "lip_vjp_eigen": (C.c_int, [_V, _V, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V), C.POINTER(C.c_int32), C.c_int32,
                                 C.c_int32, C.c_int32, C.c_float, _V, C.c_int64, _V]),
+    "lip_vjp_eigen_wnorm_scratch": (C.c_int, [_V, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_vjp_eigen_wnorm": (C.c_int, [_V, _V, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V), C.POINTER(C.c_int32), C.c_int32,
+                                      _V, _V, C.c_int32, C.c_int32, C.c_float, _V, C.c_int64, _V]),
     "lip_fill_rademacher": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_fill_normal": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_head_sample": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _V, _V, _V]),

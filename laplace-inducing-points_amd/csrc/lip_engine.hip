@@ -70,14 +70,20 @@ enum class Sweep {
   EIGEN,    // lip_vjp_eigen: no parameter cotangent is formed; every WGRAD op projects its activation patches with the
             // block's V and its cotangent rows with the block's Ub, and the per-(probe, example) products of the projected
             // pair are squared and summed into the block's (Mt, N) float64 Lam (the second moments EKFAC needs)
+  EWNORM,   // lip_vjp_eigen_wnorm: the projections of EIGEN, then the other reduction of the per-(probe, example) products:
+            // squared, weighted by the block's (Mt, N) float32 Rw and added to wout[p * n + i]; no parameter cotangent of a
+            // block tensor is formed.  The reductions (bias / BN cotangents) run as in WNORM against the weight vector Y,
+            // or not at all when Y is null
 };
 
-// The operands of one WGRAD op in an EIGEN sweep: the block's bases and output, and its rows Mt = KH KW C (+ 1: a bias row)
+// The operands of one WGRAD op in an EIGEN / EWNORM sweep: the block's bases, its output (EIGEN) or its weights (EWNORM),
+// and its rows Mt = KH KW C (+ 1: a bias row)
 struct EigenBlock {
   const double* V;
   const double* Ub;
   double* Lam;
   int Mt;
+  const float* Rw = nullptr;
 };
 
 struct RunCtx {
@@ -97,14 +103,15 @@ struct RunCtx {
   double* kron = nullptr;         // KRON: the (N, N) block of the op being run (run_tape shifts the output buffer per op)
   double* kron_scratch = nullptr; // ... and the partial tiles of one Gram
   long long kron_doubles = 0;
-  const EigenBlock* eigen = nullptr;  // EIGEN: the blocks of the WGRAD ops in tape order (run_tape picks the op's), scratch as SQSUM's
+  const EigenBlock* eigen = nullptr;  // EIGEN / EWNORM: the blocks of the WGRAD ops in tape order (run_tape picks the op's), scratch as SQSUM's
   // summed products (lip_ggn_vp / lip_vjp): a weight gradient that reduces all rows in one block may WRITE
   // y = s acc + alpha v instead of adding to an initialised block (the initialisation then skips its parameters)
   bool fuse = false;
   float alpha = 0.f;
 
   bool per_example() const { return mode != Sweep::SUMMED; }      // cotangents are taken per example
-  bool no_params() const { return mode == Sweep::KRON || mode == Sweep::EIGEN; }      // no parameter cotangent is formed
+  // no parameter cotangent is formed (an EWNORM sweep without a weight vector launches no reduction either)
+  bool no_params() const { return mode == Sweep::KRON || mode == Sweep::EIGEN || (mode == Sweep::EWNORM && !Y); }
   bool may_overwrite(const lip_ref_t& out) const { return fuse && mode == Sweep::SUMMED && out.space == LIP_SP_YOUT; }
 };
 
@@ -126,6 +133,10 @@ inline RunCtx kron_factors(RunCtx c, double* out, double* scratch, long long dou
 }
 inline RunCtx eigen_moments(RunCtx c, const EigenBlock* blocks, float* scratch, long long floats) {
   c.mode = Sweep::EIGEN; c.eigen = blocks; c.scratch = scratch; c.scratch_floats = floats;
+  return c;
+}
+inline RunCtx eigen_weighted_norm(RunCtx c, const EigenBlock* blocks, float* scratch, long long floats, float* wout) {
+  c.mode = Sweep::EWNORM; c.eigen = blocks; c.scratch = scratch; c.scratch_floats = floats; c.wout = wout;
   return c;
 }
 
@@ -159,7 +170,7 @@ long long wgrad_scratch(Sweep mode, int M, int N, int OHW, long long pairs) {
   return mode == Sweep::WNORM ? wgrad_wnorm_tiles(M, N, OHW) * pairs : mode == Sweep::SQSUM ? wgrad_sqsum_scratch(M, N, OHW, pairs) : 0;
 }
 long long reduce_scratch(Sweep mode, int N, long long pairs) {
-  return mode == Sweep::WNORM ? reduce_wnorm_tiles(N) * pairs : mode == Sweep::SQSUM ? reduce_sqsum_scratch(N, pairs) : 0;
+  return mode == Sweep::WNORM || mode == Sweep::EWNORM ? reduce_wnorm_tiles(N) * pairs : mode == Sweep::SQSUM ? reduce_sqsum_scratch(N, pairs) : 0;
 }
 
 template <class Prm>
@@ -180,7 +191,8 @@ int reduce_params(const RunCtx& c, const ReduceP& r, int n_img, const char* who)
   if (!r.g || r.N <= 0 || r.N > MAX_REDUCED_WIDTH || (r.red1 && !r.xhat)) { set_error("%s: bad reduction operands", who); return LIP_ERR_ARG; }
   if (reduce_scratch(c.mode, r.N, (long long)c.P * n_img) > c.scratch_floats) { set_error("%s: reduction scratch too small", who); return LIP_ERR_ARG; }
   switch (c.mode) {
-    case Sweep::WNORM: RUN_CHECK(launch_reduce_wnorm(r, c.P, c.wones, c.wout, c.scratch, c.scratch_floats, c.st), who); break;
+    case Sweep::WNORM:
+    case Sweep::EWNORM: RUN_CHECK(launch_reduce_wnorm(r, c.P, c.wones, c.wout, c.scratch, c.scratch_floats, c.st), who); break;
     case Sweep::SQSUM: RUN_CHECK(launch_reduce_sqsum(r, c.P, c.scratch, c.scratch_floats, c.st), who); break;
     default: RUN_CHECK(launch_reduce(r, c.P, c.st), who);
   }
@@ -345,6 +357,50 @@ int eigen_wgrad(const RunCtx& c, const lip_op_t& op) {
   return LIP_OK;
 }
 
+// EWNORM: the scratch floats of one WGRAD op with Mt rows on a pass of pc probes, in the order ewnorm_wgrad lays them out:
+// the AV and GU of EigenLayout, then the (output tile, pair) partials of the weighted-norm weight gradient
+struct EwnormLayout {
+  long long av, gu, wn;
+  long long total() const { return av + gu + wn; }
+};
+EwnormLayout ewnorm_layout(const lip_op_t& op, int Mt, int pc) {
+  const EigenLayout e = eigen_layout(op, Mt, pc);
+  return EwnormLayout{e.av, e.gu, wgrad_wnorm_tiles(Mt, op.N, op.OH * op.OW) * pc * op.n_img};
+}
+
+// EWNORM: wout[p n + i] += sum_{j,m} Rw[j][m] (((At_i V)^T (G_pi Ub))[j][m])^2.  The projections of eigen_wgrad; the
+// projected pair goes to the weighted-norm weight gradient of lip_vjp_wnorm as the same 1x1 convolution with Mt input
+// channels, its weights the block's Rw (at OH OW = 1 the launcher's bilinear route: the product is an outer product still).
+int ewnorm_wgrad(const RunCtx& c, const lip_op_t& op) {
+  const lip_seg_t& g = op.seg[0];
+  const float* a = resolve(c, g.a);
+  const float* rows = resolve(c, g.b);
+  const EigenBlock* b = c.eigen;
+  if (!a || !rows || !b || !b->V || !b->Ub || !b->Rw || !c.wout || !c.scratch || g.a.pstride != 0) { set_error("WGRAD (eigen wnorm): bad operands"); return LIP_ERR_ARG; }
+  if (!eigen_op_fits(op, b->Mt, c.P)) {       // lip_vjp_eigen_wnorm has checked every op before its first launch
+    set_error("WGRAD (eigen wnorm): the block does not match the op, or a tensor of 2^31 or more elements");
+    return LIP_ERR_ARG;
+  }
+  const EwnormLayout l = ewnorm_layout(op, b->Mt, c.P);
+  if (l.total() > c.scratch_floats) { set_error("WGRAD (eigen wnorm): scratch too small"); return LIP_ERR_ARG; }
+  float* AV = c.scratch;
+  float* GU = AV + l.av;
+  float* part = GU + l.gu;
+  const int Mt = b->Mt, OHW = op.OH * op.OW, Rp = op.n_img * OHW;
+  RUN_CHECK(launch_project_patches(a, op.n_img, g.IH, g.IW, g.C, g.KH, g.KW, g.stride, g.pad_h, g.pad_w, op.OH, op.OW,
+                                   Mt - g.KH * g.KW * g.C, b->V, AV, c.st), "patch projection launch");
+  RUN_CHECK(launch_rows_project(rows, op.N, g.b.pstride, c.P, Rp, op.N, b->Ub, GU, c.st), "row projection launch");
+  WgradP p = WgradP();
+  p.a = AV; p.IH = op.OH; p.IW = op.OW; p.C = Mt; p.KH = 1; p.KW = 1; p.stride = 1; p.pad_h = 0; p.pad_w = 0;
+  p.g = GU; p.g_ps = (long long)Rp * op.N;
+  p.R = Rp; p.OHW = OHW; p.OW = op.OW; p.N = op.N; p.M = Mt;
+  p.dOHW = FastDiv((unsigned)OHW); p.dOW = FastDiv((unsigned)op.OW);
+  p.y = nullptr; p.y_ps = 0; p.scale = nullptr;
+  p.ksplit = 1; p.seg_rows = OHW; p.seg_ys = 0;
+  RUN_CHECK(launch_wgrad_wnorm(p, c.P, op.n_img, b->Rw, c.wout, part, l.wn, c.st), "weighted-norm wgrad launch (eigen)");
+  return LIP_OK;
+}
+
 int run_op(const RunCtx& c, const lip_op_t& op) {
   switch (op.kind) {
     case LIP_OP_IGEMM: {
@@ -399,6 +455,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
     case LIP_OP_WGRAD: {
       if (c.mode == Sweep::KRON) return kron_wgrad(c, op);
       if (c.mode == Sweep::EIGEN) return eigen_wgrad(c, op);
+      if (c.mode == Sweep::EWNORM) return ewnorm_wgrad(c, op);
       WgradP p;
       const int rc = make_wgrad(c, op, p);
       if (rc) return rc;
@@ -529,7 +586,7 @@ int run_tape(const RunCtx& c, int which, bool skip_head) {
       RunCtx ck = c;                                   // this op's block of the output buffer
       ck.kron = c.kron + c.e->kron_off[i];
       rc = run_op(ck, t[i]);
-    } else if (c.mode == Sweep::EIGEN && t[i].kind == LIP_OP_WGRAD) {
+    } else if ((c.mode == Sweep::EIGEN || c.mode == Sweep::EWNORM) && t[i].kind == LIP_OP_WGRAD) {
       RunCtx ck = c;                                   // this op's block of the call's arrays
       ck.eigen = c.eigen + c.e->wgrad_index[i];
       rc = run_op(ck, t[i]);
@@ -624,6 +681,12 @@ int ggn_sweep(const lip_engine* e, const float* V, float* Y, int P, float scale,
   });
 }
 
+// does the op form bias / BN cotangents (a REDUCE op, or reductions fused into another op)?
+inline bool has_reductions(const lip_op_t& op) {
+  return (op.kind == LIP_OP_IGEMM || op.kind == LIP_OP_REDUCE || op.kind == LIP_OP_POOL_BWD || op.kind == LIP_OP_MAXPOOL_BWD) &&
+         (op.red0.space != LIP_SP_NONE || op.red1.space != LIP_SP_NONE);
+}
+
 // Scratch floats of a lip_vjp_sqsum / lip_vjp_wnorm call of P probes (doubles of a lip_vjp_kron call): the largest need
 // of one backward op on one pass (ops run in stream order and reuse it).  Depends on the tape geometry and the probes
 // per pass only.
@@ -641,10 +704,26 @@ int64_t sweep_scratch(const lip_engine* e, Sweep mode, int P) {
           if (kron_op_fits(op, q)) k = std::max<int64_t>(k, panel_gram_scratch((int)kron_rows(op, q, nullptr), op.N));
     } else if (op.kind == LIP_OP_WGRAD)
       k = wgrad_scratch(mode, op.seg[0].KH * op.seg[0].KW * op.seg[0].C, op.N, op.OH * op.OW, pairs);
-    else if ((op.kind == LIP_OP_IGEMM || op.kind == LIP_OP_REDUCE || op.kind == LIP_OP_POOL_BWD || op.kind == LIP_OP_MAXPOOL_BWD) &&
-             (op.red0.space != LIP_SP_NONE || op.red1.space != LIP_SP_NONE))
+    else if (has_reductions(op))
       k = reduce_scratch(mode, op.N, pairs);
     need = std::max(need, k);
+  }
+  return need;
+}
+
+// Scratch floats of a lip_vjp_eigen_wnorm call of P probes: the largest need of one backward op on a full pass (every
+// part grows with the probes, so it bounds the shorter last pass), a WGRAD op with either row count a block can have,
+// against the reductions' own need
+int64_t ewnorm_scratch(const lip_engine* e, int P) {
+  const int pc = e->max_chunk > 0 ? balanced_chunk(P, e->max_chunk) : P;
+  int64_t need = 0;
+  for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
+    if (op.kind == LIP_OP_WGRAD) {
+      const int M = op.seg[0].KH * op.seg[0].KW * op.seg[0].C;
+      for (int Mt = M; Mt <= M + 1; ++Mt) need = std::max<int64_t>(need, ewnorm_layout(op, Mt, pc).total());
+    } else if (has_reductions(op)) {
+      need = std::max<int64_t>(need, reduce_scratch(Sweep::EWNORM, op.N, (long long)pc * op.n_img));
+    }
   }
   return need;
 }
@@ -944,6 +1023,53 @@ int lip_vjp_eigen(lip_engine_t* e, const float* U, const double* const* V, const
   return for_each_pass(e, P, [&](int c0, int pc) {
     const RunCtx c{e, nullptr, nullptr, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
     return run_tape(eigen_moments(c, blocks.data(), scratch, scratch_floats), LIP_TAPE_BACKWARD, false);
+  });
+}
+
+int lip_vjp_eigen_wnorm_scratch(lip_engine_t* e, int32_t P, int64_t* floats) {
+  if (!e || !floats || P <= 0) { set_error("lip_vjp_eigen_wnorm_scratch: bad argument"); return LIP_ERR_ARG; }
+  if (e->tape[LIP_TAPE_BACKWARD].empty()) { set_error("lip_vjp_eigen_wnorm_scratch: backward tape missing"); return LIP_ERR_STATE; }
+  *floats = ewnorm_scratch(e, P);
+  return LIP_OK;
+}
+
+int lip_vjp_eigen_wnorm(lip_engine_t* e, const float* U, const double* const* V, const double* const* Ub, const float* const* Rw,
+                        const int32_t* Mt, int32_t nblocks, const float* w_rem, float* out, int32_t P, int32_t head_mode,
+                        float cc, float* scratch, int64_t scratch_floats, void* stream) {
+  int rc = ready_vjp(e, "lip_vjp_eigen_wnorm", U, out, P, head_mode, V && Ub && Rw && Mt && nblocks > 0 && scratch && scratch_floats > 0);
+  if (rc) return rc;
+  if (((uintptr_t)scratch) & 15) { set_error("lip_vjp_eigen_wnorm: scratch must be 16-byte aligned"); return LIP_ERR_ARG; }
+  // every op of every pass is checked before the first launch, so that a refusal leaves out untouched
+  const int64_t need = ewnorm_scratch(e, P);
+  if (scratch_floats < need) {
+    set_error("lip_vjp_eigen_wnorm: scratch of %lld floats, %lld needed (lip_vjp_eigen_wnorm_scratch)", (long long)scratch_floats, (long long)need);
+    return LIP_ERR_ARG;
+  }
+  const int step = balanced_chunk(P, e->max_chunk), last = P - (P - 1) / step * step;
+  std::vector<EigenBlock> blocks;
+  for (const lip_op_t& op : e->tape[LIP_TAPE_BACKWARD]) {
+    if (w_rem && has_reductions(op) && !(op.N > 0 && op.N <= MAX_REDUCED_WIDTH && (long long)step * op.n_img < (1ll << 31))) {
+      set_error("lip_vjp_eigen_wnorm: a parameter reduction of %d columns, or 2^31 or more pairs on a pass", (int)op.N);
+      return LIP_ERR_ARG;
+    }
+    if (op.kind != LIP_OP_WGRAD) continue;
+    const size_t k = blocks.size();
+    if (k >= (size_t)nblocks) { set_error("lip_vjp_eigen_wnorm: %d blocks, the backward tape has more weight gradients", (int)nblocks); return LIP_ERR_ARG; }
+    if (!V[k] || !Ub[k] || !Rw[k]) { set_error("lip_vjp_eigen_wnorm: block %zu has a null operand", k); return LIP_ERR_ARG; }
+    if (op.seg[0].a.pstride != 0 || !eigen_op_fits(op, Mt[k], step) || !eigen_op_fits(op, Mt[k], last)) {
+      set_error("lip_vjp_eigen_wnorm: block %zu (Mt = %d) does not match its weight gradient, or a tensor of 2^31 or more "
+                "elements on a pass; bind fewer examples per engine", k, (int)Mt[k]);
+      return LIP_ERR_ARG;
+    }
+    EigenBlock b{V[k], Ub[k], nullptr, (int)Mt[k]};
+    b.Rw = Rw[k];
+    blocks.push_back(b);
+  }
+  if (blocks.size() != (size_t)nblocks) { set_error("lip_vjp_eigen_wnorm: %d blocks, the backward tape has %zu weight gradients", (int)nblocks, blocks.size()); return LIP_ERR_ARG; }
+  return for_each_pass(e, P, [&](int c0, int pc) {
+    // (Y is the remainder's weight vector, read at the slices of the reductions only; null: no reduction runs)
+    const RunCtx c{e, nullptr, const_cast<float*>(w_rem), head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    return run_tape(eigen_weighted_norm(c, blocks.data(), scratch, scratch_floats, out + (int64_t)c0 * e->n_img), LIP_TAPE_BACKWARD, false);
   });
 }
 

@@ -186,14 +186,19 @@ def posterior_lla_ekfac(map_state, Z, model_type, alpha, full_set_size=None, exa
 
 
 def predict_lla_ekfac(map_state, Xnew, Z, model_type, alpha, full_set_size=None, cov: str = "full", batch: int = 256,
-                      example_chunk: Optional[int] = None, *, moments: Optional[str] = None, curvature=None):
+                      example_chunk: Optional[int] = None, *, moments: Optional[str] = None, curvature=None,
+                      route: Optional[str] = None):
     """Closed-form linearised predictive of :func:`posterior_lla_ekfac` (:meth:`LinearizedNet.kfac_predict` with the
-    corrected R), in the return shapes and types, and with the batching and refusals, of :func:`kfac.predict_lla_kfac`."""
+    corrected R), in the return shapes and types, and with the batching and refusals, of :func:`kfac.predict_lla_kfac`;
+    ``route="sweep"`` as there (:meth:`LinearizedNet.kfac_predict_sweep`: no Jacobian rows), independent of ``moments``
+    and ``curvature``, which choose the fit."""
     if cov not in ("diag", "full"):
         raise ValueError("cov must be 'diag' or 'full'")
+    _kfac.checked_route(route)
     _, fits, rem_idx, rem_var, _ = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments,
                                                curvature)
-    return _kfac.predictive_from_fit(map_state, Xnew, model_type, fits, (rem_idx, rem_var), cov, batch)
+    return _kfac.predictive_from_fit(map_state, Xnew, model_type, fits, (rem_idx, rem_var), cov, batch,
+                                     **_kfac.route_kwargs(route))
 
 
 def predict_lla_ekfac_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1,

@@ -1137,6 +1137,100 @@ class LinearizedNet:
                 Lam += out / float(divisor)
         return Lams
 
+    def kfac_predict_sweep(self, fits, rem, diag: bool = True, class_chunk: Optional[int] = None,
+                           probes: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """:meth:`kfac_predict` from backward sweeps instead of Jacobian rows (``lip_vjp_eigen_wnorm``): with
+        T = V^T mat_l(J_i^T u) Ub = (At_i V)^T (G_i diag(s) Ub) of :meth:`kfac_eigen_sqsums_sweep`,
+
+            u^T J_i Sigma J_i^T u = sum_l sum_{j,m} R_l[j][m] T_l[j][m]^2 + sum_{d in remainder} var_d (J_i^T u)_d^2,
+
+        so every WGRAD op of the sweep projects its patches and its cotangent rows and the weighted-norm kernel of
+        :meth:`vjp_wnorm` reduces the per-(probe, example) products of the pair against the block's R; the remainder's
+        term is that kernel's own reduction.  No D-wide row and no float64 Mt x N stage exists, so there is no row-block
+        cap: the probes go in blocks of ``class_chunk`` (None: all at once; the engine splits them into its passes).
+        The working set is the call's scratch instead, kept on the engine: per op the projected patches (n OH OW Mt
+        floats) and the projected rows of one pass's probes (P' n OH OW N floats), the largest op counting (609 MiB at
+        the CIFAR config with 256 points, 6 GiB at ResNet-50 with K = 1000 probes in one pass; ``class_chunk`` cuts
+        the second part).
+        Same operands and operand checks as :meth:`kfac_predict`; the BN scale of a block is folded into its Ub in
+        float64, R and the remainder's variances are cast to float32 once.  The remainder's variances are scattered into
+        a zero (D,) vector, so a bias that a block carries as its row 0 has weight 0 in its own reduction and is counted
+        once; a net without a remainder launches no reduction.  ``diag=True``: one-hot 'raw' probes, (n, K) float64.
+        ``diag=False``: the K (K + 1) / 2 probes of ``lla.polarisation_probes`` combined in float64, (n, K, K), exactly
+        symmetric; K > 32 raises ``ValueError`` before anything runs.  ``probes``: a raw (P, n, K) block of head
+        cotangents swept instead; the (P, n) float32 weighted norms come back as they are.  The sums are float32 (those
+        of ``lip_vjp_wnorm``), bitwise reproducible for a given chunking."""
+        from .lla import POLARISATION_MAX_K, covariance_from_polarisation, polarisation_probes
+        blocks = self.kfac_blocks()
+        if len(fits) != len(blocks):
+            raise ValueError(f"{len(blocks)} layer blocks need {len(blocks)} fitted factor triples")
+        for b, (V, R, Ub) in zip(blocks, fits):
+            for name, t, shape in (("V", V, (b.Mt, b.Mt)), ("R", R, (b.Mt, b.N)), ("Ub", Ub, (b.N, b.N))):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"{name} of the block at offset {b.off} must be a contiguous float64 device matrix of "
+                                     f"{shape[0]} x {shape[1]}")
+        K, n = self.K, self.n
+        if class_chunk is not None and class_chunk < 1:
+            raise ValueError("class_chunk must be positive")
+        if probes is None and not diag and K > POLARISATION_MAX_K:
+            raise ValueError(f"the full predictive takes K (K + 1) / 2 probes per binding: refused for K = {K} > "
+                             f"{POLARISATION_MAX_K} outputs (use diag)")
+        if probes is not None and (probes.dim() != 3 or tuple(probes.shape[1:]) != (n, K)):
+            raise ValueError(f"probes must be a (P, {n}, {K}) block of head cotangents, got {tuple(probes.shape)}")
+        idx, var = rem[0].to(self.device), rem[1].to(device=self.device, dtype=torch.float64)
+        if idx.numel() != var.numel():
+            raise ValueError("the remainder needs one variance per index")
+        cap = len(blocks)
+        koff, ooff, Ns = (C.c_int64 * cap)(), (C.c_int64 * cap)(), (C.c_int32 * cap)()
+        count, total = C.c_int32(0), C.c_int64(0)
+        nv.check(self.lib.lip_vjp_kron_layout(self.h, cap, koff, ooff, Ns, C.byref(count), C.byref(total)), "lip_vjp_kron_layout")
+        order = {int(koff[i]): i for i in range(min(cap, count.value))}
+        if count.value != cap or any(b.kernel_off not in order or int(Ns[order[b.kernel_off]]) != b.N for b in blocks):
+            raise nv.NativeError("lip_vjp_kron_layout: the backward tape's weight gradients do not match the layer blocks")
+        keep = []                                                       # the operands the pointer arrays refer to
+        Vp, Up, Rp, Mts = (C.c_void_p * cap)(), (C.c_void_p * cap)(), (C.c_void_p * cap)(), (C.c_int32 * cap)()
+        for b, (V, R, Ub) in zip(blocks, fits):
+            if b.bn is not None:
+                Ub = (self.consts[b.bn[0]:b.bn[0] + b.N].double()[:, None] * Ub).contiguous()
+            Rw = R.float().contiguous()
+            keep.append((V, Ub, Rw))
+            k = order[b.kernel_off]
+            Vp[k], Up[k], Rp[k], Mts[k] = V.data_ptr(), Ub.data_ptr(), Rw.data_ptr(), b.Mt
+        w_rem = None
+        if idx.numel():
+            w_rem = torch.zeros(self.D, device=self.device, dtype=torch.float32)
+            w_rem[idx] = var.float()
+
+        def sweep(E: torch.Tensor, head: int) -> torch.Tensor:
+            """(P, n) float32 weighted norms of the (P, n K) cotangents E"""
+            P = E.shape[0]
+            out = torch.zeros(P, n, device=self.device, dtype=torch.float32)
+            floats = C.c_int64(0)
+            nv.check(self.lib.lip_vjp_eigen_wnorm_scratch(self.h, P, C.byref(floats)), "lip_vjp_eigen_wnorm_scratch")
+            scratch = self._scratches.get("lip_vjp_eigen_wnorm")
+            if scratch is None or scratch.numel() < floats.value:
+                scratch = self._scratches["lip_vjp_eigen_wnorm"] = torch.empty(max(4, floats.value), device=self.device,
+                                                                               dtype=torch.float32)
+            nv.check(self.lib.lip_vjp_eigen_wnorm(self.h, nv.ptr(E), Vp, Up, Rp, Mts, cap, nv.ptr(w_rem), nv.ptr(out), P, head,
+                                                  1.0, scratch.data_ptr(), scratch.numel(), nv.stream_ptr()),
+                     "lip_vjp_eigen_wnorm")
+            return out
+
+        def chunked(U: torch.Tensor, head: int) -> torch.Tensor:
+            pc = U.shape[0] if class_chunk is None else int(class_chunk)
+            return torch.cat([sweep(U[p0:p0 + pc], head) for p0 in range(0, U.shape[0], pc)])
+
+        if probes is not None:
+            return chunked(*self._cotangents(probes, "raw"))
+        if diag:
+            E = torch.eye(K, device=self.device, dtype=torch.float32)
+        else:
+            E, ks, kps = polarisation_probes(K)
+            E = E.to(self.device)
+        U, head = self._cotangents(E[:, None, :].expand(E.shape[0], n, K), "raw")
+        q = chunked(U, head).T.double()                                                     # (n, P)
+        return q if diag else covariance_from_polarisation(q, ks.to(self.device), kps.to(self.device), K)
+
     # ------------------------------------------------------------------------------ measurement
     def profile(self, enable: bool):
         nv.check(self.lib.lip_engine_profile(self.h, int(enable)), "lip_engine_profile")

@@ -139,7 +139,7 @@ def auroc_ood(state, id_probs: torch.Tensor, ood_loader: Iterable, Z, alpha, ful
 
 
 def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, model_type="classifier",
-                        posterior: str = "diag", indices=None, rank=None, *, curvature=None):
+                        posterior: str = "diag", indices=None, rank=None, *, curvature=None, route=None):
     """:func:`eval_dataset_extended` without draws: the class probabilities are the probit predictive
     (``lla.probit_predictive``) of the closed-form output variances — ``posterior="diag"``: the diagonal Laplace
     posterior (``lla.predict_lla_diag``), ``"inducing"``: the inducing-point posterior (``lla.predict_lla_variances``),
@@ -152,7 +152,9 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
     leading eigenpairs of the GGN of Z (``lla.predict_lla_lowrank``, fitted once for all batches; ``rank`` is read by this
     value alone, ``None``: ``lowrank.DEFAULT_RANK``).  ``curvature``: a spec of ``fisher.py`` for the fit of
     ``posterior="diag"``, ``"kfac"`` and ``"ekfac"`` (whose second moments then come from the backward sweep,
-    ``moments="sweep"``); the other posteriors refuse one.
+    ``moments="sweep"``); the other posteriors refuse one.  ``route``: ``"rows"`` or ``"sweep"`` for the predictive of
+    ``posterior="kfac"`` and ``"ekfac"`` (``kfac.predict_lla_kfac``; ``"sweep"`` forms no Jacobian row, so it runs at any
+    D and K); the other posteriors refuse one.
     -> (NLL, accuracy, Brier, ECE, probs, labels)"""
     from .lla import (predict_lla_diag, predict_lla_ekfac, predict_lla_kfac, predict_lla_last_layer, predict_lla_last_layer_kron,
                       predict_lla_lowrank, predict_lla_subnetwork, predict_lla_variances, probit_predictive)
@@ -162,6 +164,10 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
         if posterior not in ("diag", "kfac", "ekfac"):
             raise ValueError(f"curvature is taken by posterior='diag', 'kfac' and 'ekfac' only, not {posterior!r}")
         curv_kw = {"curvature": curvature}
+    if route is not None:
+        if posterior not in ("kfac", "ekfac"):
+            raise ValueError(f"route is taken by posterior='kfac' and 'ekfac' only, not {posterior!r}")
+        curv_kw = dict(curv_kw, route=route)
     if posterior == "subnetwork" and indices is None:
         raise ValueError("posterior='subnetwork' needs indices")
     predict = {"diag": predict_lla_diag, "inducing": predict_lla_variances,

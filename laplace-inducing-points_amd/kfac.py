@@ -187,25 +187,55 @@ def posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=None, exam
 
 
 def predict_lla_kfac(map_state, Xnew, Z, model_type, alpha, full_set_size=None, cov: str = "full", batch: int = 256,
-                     example_chunk: Optional[int] = None, *, curvature=None):
+                     example_chunk: Optional[int] = None, *, curvature=None, route: Optional[str] = None):
     """Closed-form linearised predictive of :func:`posterior_lla_kfac`: mean f(x; theta_MAP) and
     sum_l J_l(x) Sigma_l J_l(x)^T + sum_d J_d(x)^2 var_d per test point (``lip_kfac_predict`` per layer block on the
     Jacobian rows of ``lip_vjp_rows``), in the return shapes and types of
     :func:`last_layer_kron.predict_lla_last_layer_kron`.  ``batch`` test points are bound at a time, fewer for
-    ``cov="full"`` when their (K, batch, D) float32 rows would exceed 2 GiB."""
+    ``cov="full"`` when their (K, batch, D) float32 rows would exceed 2 GiB.  ``route="sweep"`` forms the same sums
+    inside one backward sweep per test batch without any Jacobian row (:func:`predictive_from_fit`); the default
+    (None) is ``"rows"``."""
     if cov not in ("diag", "full"):
         raise ValueError("cov must be 'diag' or 'full'")
+    checked_route(route)
     _, fits, rem_idx, rem_var, _ = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, curvature)
     return predictive_from_fit(map_state, Xnew, model_type, [(V, R, Ub) for V, R, Ub, _, _, _ in fits], (rem_idx, rem_var),
-                               cov, batch)
+                               cov, batch, **route_kwargs(route))
 
 
-def predictive_from_fit(map_state, Xnew, model_type, triples, rem, cov: str, batch: int):
+ROUTES = ("rows", "sweep")
+
+
+def checked_route(route) -> str:
+    """the route of a predictive, None standing for the default; ``ValueError`` for anything else"""
+    route = "rows" if route is None else route
+    if route not in ROUTES:
+        raise ValueError(f"route must be 'rows' or 'sweep', got {route!r}")
+    return route
+
+
+def route_kwargs(route):
+    """the keywords of :func:`predictive_from_fit` for a route: none for the default, so the rows route is called as it
+    always was"""
+    return {} if checked_route(route) == "rows" else {"route": route}
+
+
+def predictive_from_fit(map_state, Xnew, model_type, triples, rem, cov: str, batch: int, route: str = "rows"):
     """the predictive of :func:`predict_lla_kfac` from the (V, R, Ub) of every block and the remainder's
-    (indices, variances): :meth:`LinearizedNet.kfac_predict` on ``batch`` test points at a time"""
+    (indices, variances): :meth:`LinearizedNet.kfac_predict` on ``batch`` test points at a time.  ``route="sweep"``:
+    :meth:`LinearizedNet.kfac_predict_sweep` instead, which forms no Jacobian row, so it has no row-block cap and does
+    not reduce ``batch`` for ``cov="full"`` (which it takes for K <= 32 outputs, by polarisation); its sums are float32
+    where the rows route multiplies in float64.  An unknown route raises ``ValueError`` before any engine is bound."""
     from .distributions import MultivariateNormalFullCovariance
     rem_idx, rem_var = rem
-    if cov == "full":
+    sweep = checked_route(route) == "sweep"
+    if sweep and cov == "full":
+        from .lla import POLARISATION_MAX_K
+        K = int(map_state.net.num_outputs)
+        if K > POLARISATION_MAX_K:
+            raise ValueError(f"cov='full' on the sweep route takes K (K + 1) / 2 probes per test batch: refused for K = {K} "
+                             f"> {POLARISATION_MAX_K} outputs (use cov='diag')")
+    if cov == "full" and not sweep:
         D = flatten_nn_params(map_state.params)[0].numel()
         fit = (LinearizedNet.ROW_BLOCK_BYTES // (4 * D)) // int(map_state.net.num_outputs)
         if fit < 1:
@@ -214,7 +244,8 @@ def predictive_from_fit(map_state, Xnew, model_type, triples, rem, cov: str, bat
     means, outs = [], []
     for s0 in range(0, Xnew.shape[0], batch):
         eng = _ggn.get_engine(map_state, Xnew[s0:s0 + batch], model_type)
-        outs.append(eng.kfac_predict(triples, (rem_idx, rem_var), diag=cov == "diag"))
+        predict = eng.kfac_predict_sweep if sweep else eng.kfac_predict
+        outs.append(predict(triples, (rem_idx, rem_var), diag=cov == "diag"))
         means.append(eng.outputs().double())
     f_mean, f_out = torch.cat(means), torch.cat(outs)
     if cov == "diag":
@@ -229,8 +260,8 @@ def predict_lla_kfac_scalable(map_state, Xnew, Z, model_type, alpha, key=None, f
     """Draws of the outputs under :func:`posterior_lla_kfac`: f(x; theta_MAP) + J(x) d_theta_s -> (S, B, K) float32,
     d_theta_s the zero-mean part of ``num_samples`` draws of :meth:`KFACNormal.sample` pushed through the engine's JVP
     ('raw'), as :func:`lla.predict_lla_diag_scalable` does.  This is the route for heads like ResNet-50's: K = 1000
-    Jacobian rows per test point make the closed form of :func:`predict_lla_kfac` impractical there, while a draw costs
-    one tangent-forward pass whatever K is."""
+    Jacobian rows per test point make the default closed form of :func:`predict_lla_kfac` impractical there (its
+    ``route="sweep"`` forms no rows), while a draw costs one tangent-forward pass whatever K is."""
     post = posterior_lla_kfac(map_state, Z, model_type, alpha, full_set_size=full_set_size, example_chunk=example_chunk,
                               curvature=curvature)
     return draws_from_posterior(post, map_state, Xnew, model_type, key, num_samples)
