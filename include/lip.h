@@ -495,6 +495,44 @@ int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream)
  * K > 8192, example_offset < 0 or example_offset + n > 2^32 returns LIP_ERR_ARG and writes nothing. */
 int lip_head_sample(const float* probs, int32_t n, int32_t K, int32_t S, uint64_t seed, int64_t example_offset, float* U,
                     int32_t* labels, void* stream);
+/* Layer-wise evidence of the structured posteriors: for every prior group g < G, with alpha_g = exp(log_alphas[g]),
+ *   out[g][0] = L_g = sum_x log1p(r x / alpha_g),   out[g][1] = T_g = sum_x (r x / alpha_g) / (1 + r x / alpha_g),
+ * x over the curvature eigenvalues of the group; out (G, 2) float64 is overwritten.  The eigenvalues are named by a
+ * segment table over one float64 value pool vals (n_vals) on the device and are never written out:
+ *   LIP_EV_KRON: x = scale * max(lam_i, 0) * max(mu_j, 0), lam = vals[off .. off + rows), mu = vals[off + rows ..
+ *                off + rows + cols): rows * cols terms, term t = i cols + j;
+ *   LIP_EV_LIST: x = scale * max(vals[off + i], 0), i < rows (cols = 1).
+ * A group may own any number of segments of either kind.  The caller cuts every segment, in table order, into chunks of
+ * chunk_terms consecutive terms (the last one of a segment shorter): chunks[c] = (first term, segment), n_chunks of them;
+ * group_ptr (G + 1) / group_chunks (n_chunks) list every group's chunks in the order in which their partial sums are
+ * added.  segs, chunks, group_ptr, group_chunks and log_alphas are device arrays (log_alphas is read by the kernel, so
+ * an optimiser loop launches without a host round trip); segs_host is the host copy of segs, which the entry point
+ * checks before any launch.  One workgroup reduces one chunk in a fixed order (per-lane strided sums, the halving tree
+ * of a 64-lane wave, waves in index order through LDS) and stores its pair to scratch (device, >=
+ * lip_evidence_terms_scratch(n_chunks) doubles); a second launch adds each group's pairs in table order.  No atomics,
+ * two launches whatever G is: bitwise reproducible and a function of the tables alone.  A term is
+ * (scale * (r / alpha_g)) * (max(lam_i, 0) * max(mu_j, 0)): four roundings after exp.  A null pointer, n_vals, n_seg,
+ * n_chunks, chunk_terms or G <= 0, chunk_terms > 2^30, a non-finite or negative r, a segment with an unknown kind, a
+ * group outside [0, G), non-positive rows or cols (cols != 1 for a list, rows or cols >= 2^31 for a product), a
+ * negative or non-finite scale or an end past the pool, an n_chunks other than what the segments cut into, or too small
+ * a scratch returns LIP_ERR_ARG and leaves out untouched.  A device table that differs from the checked host copy
+ * cannot make the kernels read outside vals, the tables or scratch: they answer it with NaN. */
+#define LIP_EV_KRON 0
+#define LIP_EV_LIST 1
+typedef struct {
+  int32_t kind, group;
+  int64_t off, rows, cols;
+  double scale;
+} lip_ev_seg_t;
+typedef struct {
+  int64_t start;               /* first term of the chunk inside its segment */
+  int32_t seg, reserved;
+} lip_ev_chunk_t;
+int lip_evidence_terms_scratch(int64_t n_chunks, int64_t* doubles);
+int lip_evidence_terms(const double* vals, int64_t n_vals, const lip_ev_seg_t* segs_host, const lip_ev_seg_t* segs, int32_t n_seg,
+                       const lip_ev_chunk_t* chunks, int64_t n_chunks, int64_t chunk_terms, const int64_t* group_ptr,
+                       const int32_t* group_chunks, const double* log_alphas, int32_t G, double r, double* out,
+                       double* scratch, int64_t scratch_doubles, void* stream);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,19 @@ class Op(C.Structure):
                 ("aux0", Ref), ("aux1", Ref)]
 
 
+class EvSeg(C.Structure):
+    """``lip_ev_seg_t``: one segment of the evidence table (``lip_evidence_terms``)"""
+    _fields_ = [("kind", C.c_int32), ("group", C.c_int32), ("off", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64),
+                ("scale", C.c_double)]
+
+
+class EvChunk(C.Structure):
+    """``lip_ev_chunk_t``: the first term of a chunk inside its segment, and the segment"""
+    _fields_ = [("start", C.c_int64), ("seg", C.c_int32), ("reserved", C.c_int32)]
+
+
+EV_KRON, EV_LIST = 0, 1
+
 REF_FIELDS = ("out", "out2", "out3", "scale", "e0", "e1", "xhat", "res", "dphi", "red0", "red1", "xhat2",
               "aux0", "aux1")
 
@@ -132,6 +145,9 @@ SIGNATURES = {
     "lip_vjp_eigen_wnorm_scratch": (C.c_int, [_V, C.c_int32, C.POINTER(C.c_int64)]),
     "lip_vjp_eigen_wnorm": (C.c_int, [_V, _V, C.POINTER(_V), C.POINTER(_V), C.POINTER(_V), C.POINTER(C.c_int32), C.c_int32,
                                       _V, _V, C.c_int32, C.c_int32, C.c_float, _V, C.c_int64, _V]),
+    "lip_evidence_terms_scratch": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "lip_evidence_terms": (C.c_int, [_V, C.c_int64, _V, _V, C.c_int32, _V, C.c_int64, C.c_int64, _V, _V, _V, C.c_int32,
+                                     C.c_double, _V, _V, C.c_int64, _V]),
     "lip_fill_rademacher": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_fill_normal": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_head_sample": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _V, _V, _V]),

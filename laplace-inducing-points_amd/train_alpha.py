@@ -314,3 +314,97 @@ def fit_alpha_layerwise(X, state, model_type, full_set_size=None, groups="layer"
     grams, _, t2 = grouped_spectrum(X, state, model_type, prior)
     la, history = fit_log_alphas(grams, t2, N / X.shape[0], torch.log(prior.values), alpha_lr, steps)
     return prior.with_values(torch.exp(la).cpu()), history
+
+
+# ---- the diagonal posterior, and layer-wise precisions for the structured posteriors (``evidence.py``) -----------------
+def _spectrum_diag(X, state, model_type, curvature=None):
+    """the GGN diagonal built at N/M = 1 (float64, clamped at 0), D, ||theta||^2: the spectrum of the diagonal posterior"""
+    from .ggn import compute_ggn_diag
+    diag = compute_ggn_diag(state, X, model_type, curvature=curvature).double().clamp_min(0.0)
+    flat_p, _ = flatten_nn_params(state.params)
+    return diag, flat_p.numel(), float((flat_p.detach().double() ** 2).sum())
+
+
+def log_marginal_likelihood_diag(alpha, X, state, model_type: str, full_set_size: Optional[int] = None, *,
+                                 curvature=None) -> float:
+    """:func:`log_marginal_likelihood` under the diagonal posterior (``lla.posterior_lla_diag``): the spectrum is the exact
+    GGN diagonal.  ``alpha``: a scalar or a :class:`prior.GroupedPrior` with any grouping; ``curvature``: a spec of
+    ``fisher.py`` for the diagonal.  Not a reference function."""
+    N = full_set_size or X.shape[0]
+    if isinstance(alpha, GroupedPrior):
+        from . import evidence
+        plan = evidence.plan_diag(state, X, model_type, alpha, curvature=curvature)
+        return evidence.lml_structured(torch.log(alpha.values), plan, N / X.shape[0])[0]
+    lam, D, theta2 = _spectrum_diag(X, state, model_type, curvature)
+    return _lml_from_spectrum(float(alpha), lam, D, theta2, N / X.shape[0])[0]
+
+
+def fit_alpha_diag(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alpha_lr: float = 5e-2, steps: int = 200, *,
+                   curvature=None):
+    """:func:`fit_alpha` on the evidence of the diagonal posterior: ``(alpha, history)``; the diagonal is built once."""
+    N = full_set_size or X.shape[0]
+    lam, D, theta2 = _spectrum_diag(X, state, model_type, curvature)
+    return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
+
+
+def _fit_structured(plan, prior: GroupedPrior, rescale: float, alpha_lr: float, steps: int):
+    from . import evidence
+    la, history = evidence.fit_log_alphas_structured(plan, rescale, torch.log(prior.values), alpha_lr, steps)
+    return prior.with_values(torch.exp(la).cpu()), history
+
+
+def fit_alpha_diag_layerwise(X, state, model_type, full_set_size=None, groups="layer", alpha0: float = 1.0,
+                             alpha_lr: float = 5e-2, steps: int = 200, *, curvature=None):
+    """:func:`fit_alpha_diag` with one precision per group (``groups`` as in :class:`prior.GroupedPrior`, any grouping)
+    for a fixed theta: ``(GroupedPrior, history)``, the history that of :func:`fit_log_alphas`.  The diagonal is built
+    once; every step is one evaluation of ``lip_evidence_terms``.  The prior goes into ``lla.posterior_lla_diag``."""
+    from . import evidence
+    N = full_set_size or X.shape[0]
+    prior = GroupedPrior(state.params, alpha0, groups)
+    plan = evidence.plan_diag(state, X, model_type, prior, curvature=curvature)
+    return _fit_structured(plan, prior, N / X.shape[0], alpha_lr, steps)
+
+
+def log_marginal_likelihood_kfac_layerwise(prior: GroupedPrior, X, state, model_type: str, full_set_size: Optional[int] = None,
+                                           *, curvature=None) -> float:
+    """:func:`log_marginal_likelihood_kfac` at the precisions of ``prior``, which must be constant over every layer block
+    (``groups="layer"``): then the Kronecker eigenbasis of a block does not move with the precisions and the evidence is
+    two grouped sums over c_l lam_i mu_j and the remainder's GGN diagonal (``evidence.py``)."""
+    from . import evidence
+    N = full_set_size or X.shape[0]
+    plan = evidence.plan_kfac(state, X, model_type, prior, curvature=curvature)
+    return evidence.lml_structured(torch.log(prior.values), plan, N / X.shape[0])[0]
+
+
+def fit_alpha_kfac_layerwise(X, state, model_type, full_set_size=None, groups="layer", alpha0: float = 1.0,
+                             alpha_lr: float = 5e-2, steps: int = 200, *, curvature=None):
+    """:func:`fit_alpha_kfac` with one precision per group: ``(GroupedPrior, history)``.  The factors and their
+    eigenvalues are computed once; a grouping that cuts a layer block (``"tensor"`` on a layer with a bias) is refused
+    before anything is bound.  The prior goes into ``kfac.posterior_lla_kfac`` and its predictives."""
+    from . import evidence
+    N = full_set_size or X.shape[0]
+    prior = GroupedPrior(state.params, alpha0, groups)
+    plan = evidence.plan_kfac(state, X, model_type, prior, curvature=curvature)
+    return _fit_structured(plan, prior, N / X.shape[0], alpha_lr, steps)
+
+
+def log_marginal_likelihood_ekfac_layerwise(prior: GroupedPrior, X, state, model_type: str, full_set_size: Optional[int] = None,
+                                            *, moments: Optional[str] = None, curvature=None) -> float:
+    """:func:`log_marginal_likelihood_ekfac` at the precisions of ``prior`` (constant over every layer block, as
+    :func:`log_marginal_likelihood_kfac_layerwise` asks): the grouped sums run over the eigenbasis second moments."""
+    from . import evidence
+    N = full_set_size or X.shape[0]
+    plan = evidence.plan_ekfac(state, X, model_type, prior, moments=moments, curvature=curvature)
+    return evidence.lml_structured(torch.log(prior.values), plan, N / X.shape[0])[0]
+
+
+def fit_alpha_ekfac_layerwise(X, state, model_type, full_set_size=None, groups="layer", alpha0: float = 1.0,
+                              alpha_lr: float = 5e-2, steps: int = 200, *, moments: Optional[str] = None, curvature=None):
+    """:func:`fit_alpha_ekfac` with one precision per group: ``(GroupedPrior, history)``; the factors, their
+    eigendecompositions and the second moments are computed once.  The prior goes into ``ekfac.posterior_lla_ekfac`` and
+    its predictives."""
+    from . import evidence
+    N = full_set_size or X.shape[0]
+    prior = GroupedPrior(state.params, alpha0, groups)
+    plan = evidence.plan_ekfac(state, X, model_type, prior, moments=moments, curvature=curvature)
+    return _fit_structured(plan, prior, N / X.shape[0], alpha_lr, steps)
