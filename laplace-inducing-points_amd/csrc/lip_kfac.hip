@@ -13,13 +13,13 @@
 // lip_subnetwork.hip adds the ranges in index order, both triangles from the same sums: no atomics, bitwise
 // reproducible, exactly symmetric.  The gather clamps the address and selects zero: it never reads outside the tensor.
 //
-// Predict: W = J Ub and T = V^T W on v_mfma_f64_16x16x4_f64 (the tile code of sub_tsigma_kernel), both in the caller's
+// Predict: W = J Ub and T = V^T W on v_mfma_f64_16x16x4_f64 (ll_tile_mac of lip_gramtile.h), both in the caller's
 // scratch, for chunks of test points that fit it; then one block per output entry walks R o T_k o T_m.  The diag form
 // runs the k == m entries through the same function, so it equals the diagonal of the full form bitwise.
 //
 // Eigenbasis square sums (lip_kfac_eigen_sqsum, the fit-time twin of the predictive, for EKFAC):
 //   Lam[j][l]     += sum_{r < R} T_r[j][l]^2
-// Stage one is the predictive's (kfac_jub_kernel with Kc = 1); stage two forms V^T W_r tile by tile, squares it in
+// Stage one is the predictive's (KfacBlockRows with Kc = 1); stage two forms V^T W_r tile by tile, squares it in
 // registers and sums over groups of rows, so T is never written; the groups' partial sums are folded in group order.
 //
 // Patch projection (lip_kfac_project_patches, for the EIGEN sweep of lip_engine.hip, which forms the same Lam without
@@ -62,21 +62,7 @@ struct KfacPatchOperands {
   __device__ __forceinline__ double col(int i, int t) const { return at(i, ch[t], cw[t], cc[t]); }
 };
 
-struct KfacPlan {
-  int T;                 // tiles per edge
-  long long tiles;       // lower-triangle tiles
-  int ys, nper;          // row ranges and rows per range (a multiple of LL_SPAN)
-};
-
-static KfacPlan kfac_plan(int R, int Mt) {
-  KfacPlan p;
-  p.T = (Mt + LL_B - 1) / LL_B;
-  p.tiles = (long long)p.T * (p.T + 1) / 2;
-  ll_split(R, p.tiles, p.ys, p.nper);
-  return p;
-}
-
-__global__ __launch_bounds__(256) void kfac_input_gram_kernel(const float* __restrict__ X, KfacGeom g, int R, KfacPlan pl,
+__global__ __launch_bounds__(256) void kfac_input_gram_kernel(const float* __restrict__ X, KfacGeom g, int R, TriPlan pl,
                                                               FastDiv dOHW, FastDiv dOW, double* __restrict__ part) {
   __shared__ double red[3 * LL_TILE];
   const int i16 = threadIdx.x & 15;
@@ -95,59 +81,20 @@ __global__ __launch_bounds__(256) void kfac_input_gram_kernel(const float* __res
   ll_gram_tile(op, ib, min(ib + pl.nper, R), red, part + ((long long)blockIdx.y * pl.tiles + tile) * LL_TILE);
 }
 
-// W (rows Mt, N) = J Ub: local row rho = (lr, j), lr = bl Kc + k the row of point b0 + bl and class k (source row
-// k B + b0 + bl of Jr), j the row of its (Mt, N) block.  A wave per 32 x 32 tile of W, a block per four column tiles; the
-// lane map is that of sub_tsigma_kernel and the sum stays in l order.
-__global__ __launch_bounds__(256) void kfac_jub_kernel(const float* __restrict__ Jr, long long ldj, long long off, int B,
-                                                       int Kc, int b0, long long rows, int Mt, int N,
-                                                       const double* __restrict__ Ub, double* __restrict__ W) {
-  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
-  const int ct = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long r0 = (long long)blockIdx.x * 32;
-  if (ct * 32 >= N) return;
-  const float* pa[2];
-  const double* pb[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    long long r = r0 + 16 * t + i16;
-    r = r < rows ? r : rows - 1;                                                             // clamped: never written back
+// The A operand of ll_project_kernel for W (rows Mt, N) = J Ub: local row rho = (lr, j), lr = bl Kc + k the row of point
+// b0 + bl and class k (source row k B + b0 + bl of Jr), j the row of its (Mt, N) block at flat offset off
+struct KfacBlockRows {
+  const float* __restrict__ Jr;
+  long long ldj, off;
+  int B, Kc, b0, Mt, N;
+  typedef const float* Row;
+  __device__ __forceinline__ Row row(long long r) const {
     const long long lr = r / Mt;
     const int j = (int)(r - lr * Mt), bl = (int)(lr / Kc), k = (int)(lr - (long long)bl * Kc);
-    pa[t] = Jr + ((long long)k * B + b0 + bl) * ldj + off + (long long)j * N;
-    pb[t] = Ub + min(ct * 32 + 16 * t + i16, N - 1);
+    return Jr + ((long long)k * B + b0 + bl) * ldj + off + (long long)j * N;
   }
-  ll_f64x4 acc[2][2];
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
-  for (int l0 = 0; l0 < N; l0 += 4) {
-    const int l = l0 + q;
-    const bool ok = l < N;
-    const int lc = ok ? l : N - 1;
-    double a[2], b[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const double av = (double)pa[t][lc], bv = pb[t][(long long)lc * N];
-      a[t] = ok ? av : 0.0;
-      b[t] = ok ? bv : 0.0;
-    }
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
-  }
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long long row = r0 + 16 * tm + q + 4 * r;
-        const int col = ct * 32 + 16 * tn + i16;
-        if (row < rows && col < N) W[row * N + col] = acc[tm][tn][r];
-      }
-}
+  __device__ __forceinline__ double at(Row r, int l) const { return (double)r[l]; }
+};
 
 // T_lr (Mt, N) = V^T W_lr for every local row lr: T[j][l] = sum_f V[f][j] W[f][l].  blockIdx.x = (lr, row tile), a wave
 // per 32 x 32 tile, a block per four column tiles; the sum stays in f order.
@@ -171,53 +118,8 @@ __global__ __launch_bounds__(256) void kfac_vt_kernel(const double* __restrict__
   for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
-  int f0 = 0;
-  // four k-steps per round, every load issued before the first product
-  for (; f0 + 16 <= Mt; f0 += 16) {
-    double a[4][2], b[4][2];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int f = f0 + 4 * s + q;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        a[s][t] = pa[t][(long long)f * Mt];
-        b[s][t] = pb[t][(long long)f * N];
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-          acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][tm], b[s][tn], acc[tm][tn], 0, 0, 0);
-  }
-  for (; f0 < Mt; f0 += 4) {
-    const int f = f0 + q;
-    const bool ok = f < Mt;
-    const int fc = ok ? f : Mt - 1;
-    double a[2], b[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const double av = pa[t][(long long)fc * Mt], bv = pb[t][(long long)fc * N];
-      a[t] = ok ? av : 0.0;
-      b[t] = ok ? bv : 0.0;
-    }
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
-  }
-  double* Tr = T + lr * Mt * N;
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rt * 32 + 16 * tm + q + 4 * r, col = ct * 32 + 16 * tn + i16;
-        if (row < Mt && col < N) Tr[(long long)row * N + col] = acc[tm][tn][r];
-      }
+  ll_tile_mac(F64Cols{Mt}, pa, F64Cols{N}, pb, Mt, q, acc);
+  ll_tile_store(acc, rt * 32, Mt, ct * 32, N, i16, q, T + lr * Mt * N);
 }
 
 // One entry sum_e R[e] tk[e] tm[e] by one block: a thread per e (every 256th), the threads' sums met by a fixed tree in
@@ -304,43 +206,7 @@ __global__ __launch_bounds__(256) void kfac_sqsum_kernel(const double* __restric
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
       for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
-    int f0 = 0;
-    // four k-steps per round, every load issued before the first product
-    for (; f0 + 16 <= Mt; f0 += 16) {
-      double a[4][2], b[4][2];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int f = f0 + 4 * s + q;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          a[s][t] = pa[t][(long long)f * Mt];
-          b[s][t] = pb[t][(long long)f * N];
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < 2; ++tn)
-            acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][tm], b[s][tn], acc[tm][tn], 0, 0, 0);
-    }
-    for (; f0 < Mt; f0 += 4) {
-      const int f = f0 + q;
-      const bool ok = f < Mt;
-      const int fc = ok ? f : Mt - 1;
-      double a[2], b[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const double av = pa[t][(long long)fc * Mt], bv = pb[t][(long long)fc * N];
-        a[t] = ok ? av : 0.0;
-        b[t] = ok ? bv : 0.0;
-      }
-#pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
-    }
+    ll_tile_mac(F64Cols{Mt}, pa, F64Cols{N}, pb, Mt, q, acc);
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
@@ -348,16 +214,7 @@ __global__ __launch_bounds__(256) void kfac_sqsum_kernel(const double* __restric
 #pragma unroll
         for (int r = 0; r < 4; ++r) sq[tm][tn][r] = fma(acc[tm][tn][r], acc[tm][tn][r], sq[tm][tn][r]);
   }
-  double* mine = part + (long long)blockIdx.z * E;
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rt * 32 + 16 * tm + q + 4 * r, col = ct * 32 + 16 * tn + i16;
-        if (row < Mt && col < N) mine[(long long)row * N + col] = sq[tm][tn][r];
-      }
+  ll_tile_store(sq, rt * 32, Mt, ct * 32, N, i16, q, part + (long long)blockIdx.z * E);
 }
 
 // Lam[e] += part_0[e] + part_1[e] + ... in group order: a thread per entry
@@ -413,7 +270,7 @@ hipError_t launch_project_patches(const float* X, int n, int IH, int IW, int C, 
   A.dOHW = FastDiv((unsigned)(OH * OW)), A.dOW = FastDiv((unsigned)OW), A.dC = FastDiv((unsigned)C), A.dKW = FastDiv((unsigned)KW);
   const int Mt = KH * KW * C + A.bias;
   const long long rows = (long long)n * OH * OW;
-  hipLaunchKernelGGL(ll_project_kernel<KfacPatchRows>, dim3((unsigned)((rows + 31) / 32), (unsigned)((Mt + 127) / 128)), dim3(256),
+  hipLaunchKernelGGL((ll_project_kernel<KfacPatchRows, float>), dim3((unsigned)((rows + 31) / 32), (unsigned)((Mt + 127) / 128)), dim3(256),
                      0, st, A, rows, Mt, V, Mt, AV);
   return hipGetLastError();
 }
@@ -461,7 +318,7 @@ int lip_kfac_input_gram_scratch(int32_t n, int32_t IH, int32_t IW, int32_t C, in
   const KfacGeom g = kfac_geom(IH, IW, C, KH, KW, stride, pad_h, pad_w, OH, OW, bias);
   if (!doubles || !kfac_geom_ok(n, g)) { set_error("lip_kfac_input_gram_scratch: bad argument"); return LIP_ERR_ARG; }
   if (!kfac_fits(n, g)) { set_error("lip_kfac_input_gram_scratch: a tensor of 2^31 or more elements; pass fewer images per call"); return LIP_ERR_ARG; }
-  const KfacPlan pl = kfac_plan(n * OH * OW, g.Mt);
+  const TriPlan pl = tri_plan(n * OH * OW, g.Mt);
   *doubles = pl.tiles * pl.ys * LL_TILE;
   return LIP_OK;
 }
@@ -473,7 +330,7 @@ int lip_kfac_input_gram(const float* X, int32_t n, int32_t IH, int32_t IW, int32
   if (!X || !A || !scratch || !kfac_geom_ok(n, g)) { set_error("lip_kfac_input_gram: bad argument"); return LIP_ERR_ARG; }
   if (!kfac_fits(n, g)) { set_error("lip_kfac_input_gram: a tensor of 2^31 or more elements; pass fewer images per call"); return LIP_ERR_ARG; }
   const int R = n * OH * OW;
-  const KfacPlan pl = kfac_plan(R, g.Mt);
+  const TriPlan pl = tri_plan(R, g.Mt);
   const long long need = pl.tiles * pl.ys * LL_TILE;
   if (scratch_doubles < need) {
     set_error("lip_kfac_input_gram: scratch of %lld doubles, %lld needed (lip_kfac_input_gram_scratch)", (long long)scratch_doubles, need);
@@ -535,8 +392,9 @@ int lip_kfac_predict(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_
     const long long nb = std::min<long long>(Bc, B - b0), lrows = nb * Kc, rows = lrows * Mt;
     double* W = scratch;
     double* T = scratch + lrows * E;
-    hipLaunchKernelGGL(kfac_jub_kernel, dim3((unsigned)((rows + 31) / 32), gy), dim3(256), 0, st, Jr, (long long)ldj,
-                       (long long)off, (int)B, (int)Kc, (int)b0, rows, (int)Mt, (int)N, Ub, W);
+    hipLaunchKernelGGL((ll_project_kernel<KfacBlockRows, double>), dim3((unsigned)((rows + 31) / 32), gy), dim3(256), 0, st,
+                       KfacBlockRows{Jr, (long long)ldj, (long long)off, (int)B, (int)Kc, (int)b0, (int)Mt, (int)N}, rows, (int)N,
+                       Ub, (int)N, W);
     LIP_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(kfac_vt_kernel, dim3((unsigned)(lrows * MT32), gy), dim3(256), 0, st, V, (const double*)W, (int)Mt, (int)N,
                        MT32, T);
@@ -582,8 +440,9 @@ int lip_kfac_eigen_sqsum(const float* W, int64_t ldw, int32_t R, int64_t off, in
     const KfacSqPlan pl = kfac_sq_plan(nb, Mt, N);
     double* JU = scratch;
     double* part = scratch + nb * E;
-    hipLaunchKernelGGL(kfac_jub_kernel, dim3((unsigned)((rows + 31) / 32), gy), dim3(256), 0, st, W, (long long)ldw,
-                       (long long)off, (int)R, 1, (int)r0, rows, (int)Mt, (int)N, Ub, JU);
+    hipLaunchKernelGGL((ll_project_kernel<KfacBlockRows, double>), dim3((unsigned)((rows + 31) / 32), gy), dim3(256), 0, st,
+                       KfacBlockRows{W, (long long)ldw, (long long)off, (int)R, 1, (int)r0, (int)Mt, (int)N}, rows, (int)N, Ub,
+                       (int)N, JU);
     LIP_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(kfac_sqsum_kernel, dim3((unsigned)MT32, gy, (unsigned)pl.groups), dim3(256), 0, st, V, (const double*)JU,
                        (int)Mt, (int)N, nb, pl.nper, part);

@@ -213,27 +213,22 @@ __global__ __launch_bounds__(256) void ll_kron_gram_kernel(const float* __restri
   ll_gram_tile(op, ib, min(ib + pl.nper, n), red, part + ((long long)blockIdx.y * pl.tiles + tile) * LL_TILE);
 }
 
-// out[r][c] += P[max + shift][min + shift]                              (shift = 0: A from the Gram of phit)
-// out[r][c] += delta_rc P[r + 1][0] - P[max + 1][min + 1]               (shift = 1: Bf from the Gram of [1, p])
-// P the lower-triangle tiles starting at tile0, each entry a sum over the example ranges in index order
+// Bf[r][c] += delta_rc P[r + 1][0] - P[max + 1][min + 1], P = the Gram of [1, p]: the lower-triangle tiles starting at
+// tile0, each entry a sum over the example ranges in index order
 __global__ __launch_bounds__(256) void ll_kron_assemble_kernel(const double* __restrict__ part, long long tiles, int ys,
-                                                               int tile0, int dim, int shift, double* __restrict__ out) {
+                                                               int tile0, int dim, double* __restrict__ out) {
   const int c = blockIdx.x * 16 + (threadIdx.x & 15), r = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (r >= dim || c >= dim) return;
-  const int hi = max(r, c) + shift, lo = min(r, c) + shift;
+  const int hi = max(r, c) + 1, lo = min(r, c) + 1;
   const int th = hi / LL_B, tl = lo / LL_B;
   const double* src = part + ((long long)tile0 + th * (th + 1) / 2 + tl) * LL_TILE + (hi % LL_B) * LL_B + lo % LL_B;
-  double v = 0.0;
+  double v = 0.0, d = 0.0;
   for (int y = 0; y < ys; ++y) v += src[(long long)y * tiles * LL_TILE];
-  if (shift) {
-    double d = 0.0;
-    if (r == c) {
-      const double* sd = part + ((long long)tile0 + th * (th + 1) / 2) * LL_TILE + (hi % LL_B) * LL_B;
-      for (int y = 0; y < ys; ++y) d += sd[(long long)y * tiles * LL_TILE];
-    }
-    v = d - v;
+  if (r == c) {
+    const double* sd = part + ((long long)tile0 + th * (th + 1) / 2) * LL_TILE + (hi % LL_B) * LL_B;
+    for (int y = 0; y < ys; ++y) d += sd[(long long)y * tiles * LL_TILE];
   }
-  out[(long long)r * dim + c] += v;
+  out[(long long)r * dim + c] += d - v;
 }
 
 __global__ void ll_diag_add_kernel(double* __restrict__ M, int dim, double v) {
@@ -260,27 +255,8 @@ __global__ __launch_bounds__(256) void ll_kron_gemm_kernel(const float* __restri
     }
     return j == 0 ? 1.0 : (double)Phi[(long long)b * ldphi + (j - 1)];
   };
-  ll_f64x4 acc = ll_f64x4{0.0, 0.0, 0.0, 0.0};
-  int j0 = 0;
   // eight k-steps per round, every load issued before the first product; the sum stays in j order
-  for (; j0 + 32 <= J; j0 += 32) {
-    double av[8], bv[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const int j = j0 + 4 * s + q;
-      av[s] = a_of(j);
-      bv[s] = Bm[(long long)j * N + c];
-    }
-#pragma unroll
-    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0);
-  }
-  for (; j0 < J; j0 += 4) {
-    const int j = j0 + q;
-    const bool ok = j < J;
-    const int jc = ok ? j : J - 1;
-    const double av = a_of(jc), bv = Bm[(long long)jc * N + c];
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ok ? av : 0.0, ok ? bv : 0.0, acc, 0, 0, 0);
-  }
+  const ll_f64x4 acc = ll_tile16_mac<8>(a_of, [&](int j) { return Bm[(long long)j * N + c]; }, J, q);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = rt * 16 + q + 4 * r, col = ct * 16 + i16;
@@ -402,12 +378,10 @@ int lip_ll_kron_factors(const float* Phi, int64_t ldphi, const float* Pr, int32_
   hipLaunchKernelGGL(ll_kron_gram_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.ys), dim3(256), 0, st, Phi, (long long)ldphi,
                      Pr, n, K, pl, scratch);
   LIP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(ll_kron_assemble_kernel, dim3(ga, ga), dim3(256), 0, st, (const double*)scratch, pl.tiles, pl.ys, 0,
-                     pl.Ft, 0, A);
-  LIP_CHECK_HIP(hipGetLastError());
+  LIP_CHECK_HIP(launch_gram_assemble(scratch, pl.tiles, pl.ys, pl.Ft, A, st));   // A: the Gram of phit, its tiles from tile 0
   if (Pr)
     hipLaunchKernelGGL(ll_kron_assemble_kernel, dim3(gb, gb), dim3(256), 0, st, (const double*)scratch, pl.tiles, pl.ys,
-                       pl.tilesA, (int)K, 1, Bf);
+                       pl.tilesA, (int)K, Bf);
   else
     hipLaunchKernelGGL(ll_diag_add_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st, Bf, (int)K, (double)n);
   LIP_CHECK_HIP(hipGetLastError());

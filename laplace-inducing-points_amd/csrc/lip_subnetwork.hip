@@ -47,21 +47,7 @@ struct SubPanelOperands {
   __device__ __forceinline__ double col(int i, int t) const { return (double)P[(long long)i * ld + c[t]]; }
 };
 
-struct SubPlan {
-  int T;                 // tiles per edge
-  long long tiles;       // lower-triangle tiles
-  int ys, nper;          // row ranges and rows per range (a multiple of LL_SPAN)
-};
-
-static SubPlan sub_plan(int R, int S) {
-  SubPlan p;
-  p.T = (S + LL_B - 1) / LL_B;
-  p.tiles = (long long)p.T * (p.T + 1) / 2;
-  ll_split(R, p.tiles, p.ys, p.nper);
-  return p;
-}
-
-__global__ __launch_bounds__(256) void sub_gram_kernel(const float* __restrict__ panel, int R, int S, SubPlan pl,
+__global__ __launch_bounds__(256) void sub_gram_kernel(const float* __restrict__ panel, int R, int S, TriPlan pl,
                                                        double* __restrict__ part) {
   __shared__ double red[3 * LL_TILE];
   const int i16 = threadIdx.x & 15;
@@ -92,77 +78,6 @@ __global__ __launch_bounds__(256) void sub_assemble_kernel(const double* __restr
   G[(long long)r * S + c] += v;
 }
 
-// T (rows, S) = panel (rows, S) Sigma (S, S).  A wave per 32 x 32 tile of T (four 16 x 16 MFMA tiles), a block per four
-// column tiles.  Lane l holds panel[row l & 15][j0 + (l >> 4)] and Sigma[j0 + (l >> 4)][col l & 15]; result register r of
-// lane l is (row (l >> 4) + 4 r, col l & 15).  The sum stays in j order.
-__global__ __launch_bounds__(256) void sub_tsigma_kernel(const float* __restrict__ panel, long long rows, int S,
-                                                         const double* __restrict__ Sigma, double* __restrict__ T) {
-  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
-  const int ct = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long r0 = (long long)blockIdx.y * 32;
-  if (ct * 32 >= S) return;
-  const float* pa[2];
-  const double* pb[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const long long r = r0 + 16 * t + i16;
-    pa[t] = panel + (r < rows ? r : rows - 1) * S;                                           // clamped: never written back
-    pb[t] = Sigma + min(ct * 32 + 16 * t + i16, S - 1);
-  }
-  ll_f64x4 acc[2][2];
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
-  int j0 = 0;
-  // four k-steps per round, every load issued before the first product
-  for (; j0 + 16 <= S; j0 += 16) {
-    double a[4][2], b[4][2];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int j = j0 + 4 * s + q;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        a[s][t] = (double)pa[t][j];
-        b[s][t] = pb[t][(long long)j * S];
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < 2; ++tn)
-          acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s][tm], b[s][tn], acc[tm][tn], 0, 0, 0);
-  }
-  for (; j0 < S; j0 += 4) {
-    const int j = j0 + q;
-    const bool ok = j < S;
-    const int jc = ok ? j : S - 1;
-    double a[2], b[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const double av = (double)pa[t][jc], bv = pb[t][(long long)jc * S];
-      a[t] = ok ? av : 0.0;
-      b[t] = ok ? bv : 0.0;
-    }
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
-  }
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long long row = r0 + 16 * tm + q + 4 * r;
-        const int col = ct * 32 + 16 * tn + i16;
-        if (row < rows && col < S) T[row * S + col] = acc[tm][tn][r];
-      }
-}
-
 // out[b][k][l] = sum_a T[b K + k][a] panel[b K + l][a].  Block = (test point b, four tile pairs); a wave per 16 x 16 tile
 // (kt, lt), kt <= lt (diag: kt == lt), of the K x K product.  Entries k <= l are written and mirrored; diag keeps k == l.
 __global__ __launch_bounds__(256) void sub_quad_kernel(const double* __restrict__ T, const float* __restrict__ panel, int K,
@@ -181,25 +96,7 @@ __global__ __launch_bounds__(256) void sub_quad_kernel(const double* __restrict_
   }
   const double* ta = T + ((long long)b * K + min(kt * 16 + i16, K - 1)) * S;                 // clamped: never written back
   const float* pb = panel + ((long long)b * K + min(lt * 16 + i16, K - 1)) * S;
-  ll_f64x4 acc = ll_f64x4{0.0, 0.0, 0.0, 0.0};
-  int a0 = 0;
-  for (; a0 + 16 <= S; a0 += 16) {
-    double av[4], bv[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      av[s] = ta[a0 + 4 * s + q];
-      bv[s] = (double)pb[a0 + 4 * s + q];
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], bv[s], acc, 0, 0, 0);
-  }
-  for (; a0 < S; a0 += 4) {
-    const int a = a0 + q;
-    const bool ok = a < S;
-    const int ac = ok ? a : S - 1;
-    const double av = ta[ac], bv = (double)pb[ac];
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ok ? av : 0.0, ok ? bv : 0.0, acc, 0, 0, 0);
-  }
+  const ll_f64x4 acc = ll_tile16_mac<4>([&](int a) { return ta[a]; }, [&](int a) { return (double)pb[a]; }, S, q);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int k = kt * 16 + q + 4 * r, l = lt * 16 + i16;
@@ -224,16 +121,16 @@ hipError_t launch_gram_assemble(const double* part, long long tiles, int ys, int
 
 bool panel_gram_fits(int R, int S) {
   if (R <= 0 || S <= 0) return false;
-  return sub_plan(R, S).tiles <= 0x7fffffffll && (S + 15) / 16 <= 65535;
+  return tri_plan(R, S).tiles <= 0x7fffffffll && (S + 15) / 16 <= 65535;
 }
 
 long long panel_gram_scratch(int R, int S) {
-  const SubPlan pl = sub_plan(R, S);
+  const TriPlan pl = tri_plan(R, S);
   return pl.tiles * pl.ys * LL_TILE;
 }
 
 hipError_t launch_panel_gram(const float* panel, int R, int S, double* G, double* part, hipStream_t st) {
-  const SubPlan pl = sub_plan(R, S);
+  const TriPlan pl = tri_plan(R, S);
   hipLaunchKernelGGL(sub_gram_kernel, dim3((unsigned)pl.tiles, (unsigned)pl.ys), dim3(256), 0, st, panel, R, S, pl, part);
   const hipError_t err = hipGetLastError();
   return err != hipSuccess ? err : launch_gram_assemble(part, pl.tiles, pl.ys, S, G, st);
@@ -246,15 +143,6 @@ static void sub_gather(const float* W, long long ldw, long long D, long long R, 
                      (const long long*)idx, S, K, B, panel);
 }
 
-// The A operand of ll_project_kernel for GU = G Ub: the float32 rows of a cotangent block, row r at G + r ldg
-struct PanelRows {
-  const float* __restrict__ G;
-  long long ldg;
-  typedef const float* Row;
-  __device__ __forceinline__ Row row(long long r) const { return G + r * ldg; }
-  __device__ __forceinline__ double at(Row r, int l) const { return (double)r[l]; }
-};
-
 // One launch over all P R rows when the probes are adjacent (one probe, or the per-probe stride is the row block), else
 // one launch per probe: the rule of the KRON sweep's Grams
 hipError_t launch_rows_project(const float* G, long long ldg, long long pstride, int P, int R, int N, const double* Ub,
@@ -263,7 +151,7 @@ hipError_t launch_rows_project(const float* G, long long ldg, long long pstride,
   const long long rows = packed ? (long long)P * R : R;
   const dim3 grid((unsigned)((rows + 31) / 32), (unsigned)((N + 127) / 128));
   for (int p = 0; p < (packed ? 1 : P); ++p) {
-    hipLaunchKernelGGL(ll_project_kernel<PanelRows>, grid, dim3(256), 0, st, PanelRows{G + p * pstride, ldg}, rows, N, Ub, N,
+    hipLaunchKernelGGL((ll_project_kernel<F32Rows, float>), grid, dim3(256), 0, st, F32Rows{G + p * pstride, ldg}, rows, N, Ub, N,
                        GU + (long long)p * R * N);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
@@ -305,7 +193,7 @@ int lip_rows_project(const float* G, int64_t ldg, int64_t pstride, int32_t P, in
 
 int lip_sub_gram_scratch(int32_t R, int32_t S, int64_t* doubles) {
   if (!doubles || R <= 0 || S <= 0) { set_error("lip_sub_gram_scratch: bad argument"); return LIP_ERR_ARG; }
-  const SubPlan pl = sub_plan(R, S);
+  const TriPlan pl = tri_plan(R, S);
   *doubles = sub_panel_doubles(R, S) + pl.tiles * pl.ys * LL_TILE;
   return LIP_OK;
 }
@@ -316,7 +204,7 @@ int lip_sub_gram(const float* W, int64_t ldw, int64_t D, int32_t R, const int64_
     set_error("lip_sub_gram: bad argument");
     return LIP_ERR_ARG;
   }
-  const SubPlan pl = sub_plan(R, S);
+  const TriPlan pl = tri_plan(R, S);
   const long long pd = sub_panel_doubles(R, S), need = pd + pl.tiles * pl.ys * LL_TILE;
   if (scratch_doubles < need) {
     set_error("lip_sub_gram: scratch of %lld doubles, %lld needed (lip_sub_gram_scratch)", (long long)scratch_doubles, need);
@@ -361,8 +249,9 @@ int lip_sub_predict(const float* Jr, int64_t ldj, int64_t D, int32_t B, int32_t 
   double* T = scratch + pd;
   sub_gather(Jr, (long long)ldj, (long long)D, rows, idx, S, K, B, panel, st);
   LIP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(sub_tsigma_kernel, dim3((unsigned)((S + 127) / 128), (unsigned)((rows + 31) / 32)), dim3(256), 0, st,
-                     (const float*)panel, rows, (int)S, Sigma, T);
+  // T (rows, S) = panel Sigma
+  hipLaunchKernelGGL((ll_project_kernel<F32Rows, double>), dim3((unsigned)((rows + 31) / 32), (unsigned)((S + 127) / 128)), dim3(256),
+                     0, st, F32Rows{panel, (long long)S}, rows, (int)S, Sigma, (int)S, T);
   LIP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(sub_quad_kernel, dim3((unsigned)B, (unsigned)((pairs + 3) / 4)), dim3(256), 0, st, (const double*)T,
                      (const float*)panel, (int)K, (int)S, out, (int)diag);
