@@ -533,6 +533,39 @@ int lip_evidence_terms(const double* vals, int64_t n_vals, const lip_ev_seg_t* s
                        const lip_ev_chunk_t* chunks, int64_t n_chunks, int64_t chunk_terms, const int64_t* group_ptr,
                        const int32_t* group_chunks, const double* log_alphas, int32_t G, double r, double* out,
                        double* scratch, int64_t scratch_doubles, void* stream);
+/* Semidefinite Cholesky factors for lip_link_mc: for each of the n covariances cov (n, K, K) float64, K <= 64, a lower
+ * factor L (n, K, K) float32 with L L^T = C, computed in float64.  Predictive covariances can be rank-deficient and
+ * come from float32 sums, so the factor is defined for semidefinite input, column by column: with tol = 2^-20 max_i C_ii
+ * and d_j = C_jj - sum_{k<j} L_jk^2, a column with d_j > tol gets L_jj = sqrt(d_j), L_ij = (C_ij - sum_{k<j} L_ik L_jk) /
+ * L_jj (i > j); any other column is zero.  Only the lower triangle of C is read; the strict upper triangle of L is
+ * written as zeros.  An example with a non-finite entry in its lower triangle or a C_ii < -tol is dead: flags[i] = 1 and
+ * an all-zero L; live examples get flags[i] = 0.  L and flags are overwritten.  A null cov / L / flags, n < 1, K < 1 or
+ * K > 64 returns LIP_ERR_ARG and writes nothing. */
+int lip_link_chol(const double* cov, int32_t n, int32_t K, float* L, int32_t* flags, void* stream);
+/* Monte-Carlo softmax link: the class probabilities of a Gaussian over the logits, integrated by S draws per example
+ * without writing a draw.  Exactly one of var (n, K), marginal variances, K <= 8192, and L (n, K, K), a lower factor
+ * (lip_link_chol), K <= 64, is non-null.  For example i < n, draw s < S and class k < K
+ *   z_k = mean_k + sqrt(var_k) eps_k     or     z_k = mean_k + sum_{j<=k} L_kj eps_j,      p^s = softmax(z),
+ *   probs[i] = (1/S) sum_s p^s  (n, K) float64,    mean_entropy[i] = (1/S) sum_s H(p^s)  (n,) float64, in nats,
+ * mean_entropy when not null; both are overwritten.  The normals are defined by their bits, so a host can replay them:
+ * Philox4x32-10 keyed by the two words of seed (the generator of lip_fill_normal) at the counter words (g, s, k >> 2,
+ * 0x4C4E4B31), g = example_offset + i, gives w0..w3; the fourth word differs from lip_head_sample's 0xBB67AE85, so an
+ * MC Fisher fit and an MC link with one seed share no stream.  (eps_{4j}, eps_{4j+1}) is the Box-Muller pair of (w0, w1)
+ * and (eps_{4j+2}, eps_{4j+3}) that of (w2, w3), as in lip_fill_normal: u = ((w >> 8) + 0.5) 2^-24 in float32, rad =
+ * sqrt(-2 ln u1) (__logf, __fsqrt_rn), the pair (rad cos, rad sin)(2 pi u2) (__sincosf).  mean, sqrt(var) and the draws
+ * are float32; the softmax subtracts the row maximum and uses __expf; H = log sum - sum_k e_k x_k / sum.  The sums over
+ * the draws run in float64 in an order that depends on (K, S) alone and end in one division by S: results repeat bit
+ * for bit, and the rows [a, b) computed with example_offset = a equal the rows [a, b) of the whole call.  No atomics.
+ * var_k = 0 or an all-zero L gives softmax(mean) for every draw, whatever S.  A row with a mean that is not finite in
+ * float32, a negative or non-finite var, or a non-finite entry in the lower triangle of L is dead: flags[i] = 1, NaN
+ * probabilities and entropy; it does not touch the other rows, which get flags[i] = 0.  A null mean / probs / flags, both
+ * or neither of var and L, n < 1, S < 1 (as an int32_t: 2^31 and more included), K < 1, K over the cap of the form,
+ * example_offset < 0 or example_offset + n > 2^32 returns LIP_ERR_ARG and writes nothing. */
+int lip_link_mc(const double* mean, const double* var, const float* L, int32_t n, int32_t K, int32_t S, uint64_t seed,
+                int64_t example_offset, double* probs, double* mean_entropy, int32_t* flags, void* stream);
+/* Measurement only: the largest K at which the variance form of lip_link_mc runs a whole draw per lane instead of one
+ * per group of lanes (0..64; negative: leave it).  Returns the previous value.  Results are a function of the setting. */
+int lip_debug_link_lane_max_k(int32_t K);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,9 @@ SIGNATURES = {
     "lip_fill_rademacher": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_fill_normal": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_head_sample": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _V, _V, _V]),
+    "lip_link_chol": (C.c_int, [_V, C.c_int32, C.c_int32, _V, _V, _V]),
+    "lip_link_mc": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _V, _V, _V, _V]),
+    "lip_debug_link_lane_max_k": (C.c_int, [C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None

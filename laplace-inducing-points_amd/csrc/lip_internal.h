@@ -392,4 +392,44 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// ---- counter-based RNG: Philox4x32-10 on four counter words, key = the two words of the seed --------------------
+__device__ __forceinline__ void philox4x32(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3,
+                                           unsigned long long key, unsigned int (&out)[4]) {
+  unsigned int k0 = (unsigned int)key, k1 = (unsigned int)(key >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long m0 = (unsigned long long)0xD2511F53u * c0;
+    const unsigned long long m1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned int n0 = (unsigned int)(m1 >> 32) ^ c1 ^ k0;
+    const unsigned int n1 = (unsigned int)m1;
+    const unsigned int n2 = (unsigned int)(m0 >> 32) ^ c3 ^ k1;
+    const unsigned int n3 = (unsigned int)m0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// the fills and the head sampler: a 64-bit counter in words 0 and 1, two constants in words 2 and 3
+__device__ __forceinline__ void philox4x32(unsigned long long ctr, unsigned long long key, unsigned int (&out)[4]) {
+  philox4x32((unsigned int)ctr, (unsigned int)(ctr >> 32), 0x9E3779B9u, 0xBB67AE85u, key, out);
+}
+
+// Box-Muller on one pair of Philox words: u = ((w >> 8) + 0.5) 2^-24, (a, b) = sqrt(-2 ln u1) (cos, sin)(2 pi u2).
+// Hardware transcendentals (v_log_f32 / v_sin_f32 / v_cos_f32, ~1e-6 relative): the library versions made the normal
+// fill ALU-bound at 3.8 TB/s; u1 >= 2^-25, so the logarithm stays far from its denormal range
+__device__ __forceinline__ void box_muller_pair(unsigned int w1, unsigned int w2, float& a, float& b) {
+  const float u1 = ((float)(w1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = ((float)(w2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float rad = __fsqrt_rn(-2.0f * __logf(u1));
+  float sn, cs;
+  __sincosf(6.283185307179586f * u2, &sn, &cs);
+  a = rad * cs; b = rad * sn;
+}
+
 }  // namespace lip

@@ -623,24 +623,7 @@ __global__ __launch_bounds__(KT) void cols_wsqsum_kernel(const float* __restrict
     if (c < cnt) out[col + c] += acc[c];
 }
 
-// ---- counter-based RNG: Philox4x32-10, counter = flat element index / 4, key = seed ---------------------------
-__device__ __forceinline__ void philox4x32(unsigned long long ctr, unsigned long long key, unsigned int (&out)[4]) {
-  unsigned int c0 = (unsigned int)ctr, c1 = (unsigned int)(ctr >> 32), c2 = 0x9E3779B9u, c3 = 0xBB67AE85u;
-  unsigned int k0 = (unsigned int)key, k1 = (unsigned int)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long m0 = (unsigned long long)0xD2511F53u * c0;
-    const unsigned long long m1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned int n0 = (unsigned int)(m1 >> 32) ^ c1 ^ k0;
-    const unsigned int n1 = (unsigned int)m1;
-    const unsigned int n2 = (unsigned int)(m0 >> 32) ^ c3 ^ k1;
-    const unsigned int n3 = (unsigned int)m0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// ---- counter-based fills: Philox4x32-10 (lip_internal.h), counter = flat element index / 4, key = seed ------------
 template <bool NORMAL>
 __global__ __launch_bounds__(KT) void fill_kernel(float* X, long long total, unsigned long long seed) {
   const long long nq = (total + 3) >> 2;
@@ -652,16 +635,7 @@ __global__ __launch_bounds__(KT) void fill_kernel(float* X, long long total, uns
     if (NORMAL) {
       // Box-Muller on two uniform pairs
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const float u1 = ((float)(u[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float u2 = ((float)(u[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        // hardware transcendentals (v_log_f32 / v_sin_f32 / v_cos_f32, ~1e-6 relative): the library versions made
-        // this fill ALU-bound at 3.8 TB/s; u1 >= 2^-25, so the logarithm stays far from its denormal range
-        const float rad = __fsqrt_rn(-2.0f * __logf(u1));
-        float sn, cs;
-        __sincosf(6.283185307179586f * u2, &sn, &cs);
-        v[2 * h] = rad * cs; v[2 * h + 1] = rad * sn;
-      }
+      for (int h = 0; h < 2; ++h) box_muller_pair(u[2 * h], u[2 * h + 1], v[2 * h], v[2 * h + 1]);
     } else {
 #pragma unroll
       for (int h = 0; h < 4; ++h) v[h] = (u[h] & 0x80000000u) ? 1.f : -1.f;

@@ -186,3 +186,109 @@ def eval_dataset_probit(state, dataloader: Iterable, Z, alpha, full_set_size, mo
     nll = -torch.log(torch.gather(probs, -1, labels[:, None]).squeeze(-1)).mean()
     acc = (probs.argmax(-1) == labels).to(probs.dtype).mean()
     return float(nll), float(acc), brier_score(probs, labels), ece(probs, labels), probs, labels
+
+
+def _closed_form_predict(posterior: str, cov: str, indices=None, rank=None, curvature=None, route=None):
+    """the predictive of :func:`eval_dataset_probit`'s ``posterior`` with its ``curvature`` / ``route`` / ``indices`` /
+    ``rank`` forwarding, returning marginal variances (``cov="diag"``) or full covariances (``cov="full"``)"""
+    from .lla import (predict_lla_diag, predict_lla_ekfac, predict_lla_kfac, predict_lla_last_layer, predict_lla_last_layer_kron,
+                      predict_lla_lowrank, predict_lla_marginals, predict_lla_subnetwork, predict_lla_variances)
+    if cov not in ("diag", "full"):
+        raise ValueError("cov must be 'diag' or 'full'")
+    rank_kw = {} if rank is None else {"rank": rank}
+    curv_kw = {}
+    if curvature is not None:
+        if posterior not in ("diag", "kfac", "ekfac"):
+            raise ValueError(f"curvature is taken by posterior='diag', 'kfac' and 'ekfac' only, not {posterior!r}")
+        curv_kw = {"curvature": curvature}
+    if route is not None:
+        if posterior not in ("kfac", "ekfac"):
+            raise ValueError(f"route is taken by posterior='kfac' and 'ekfac' only, not {posterior!r}")
+        curv_kw = dict(curv_kw, route=route)
+    if posterior == "subnetwork" and indices is None:
+        raise ValueError("posterior='subnetwork' needs indices")
+    table = {"diag": lambda *a, **kw: predict_lla_diag(*a, cov=cov, **kw),
+             "inducing": predict_lla_variances if cov == "diag" else predict_lla_marginals,
+             "last_layer": lambda *a, **kw: predict_lla_last_layer(*a, cov=cov, **kw),
+             "last_layer_kron": lambda *a, **kw: predict_lla_last_layer_kron(*a, cov=cov, **kw),
+             "kfac": lambda *a, **kw: predict_lla_kfac(*a, cov=cov, **kw),
+             "ekfac": lambda *a, **kw: predict_lla_ekfac(*a, cov=cov, **kw),
+             "lowrank": lambda *a, **kw: predict_lla_lowrank(*a, cov=cov, **rank_kw, **kw),
+             "subnetwork": lambda *a, **kw: predict_lla_subnetwork(*a, indices, cov=cov, **kw)}
+    if posterior not in table:
+        raise ValueError(f"posterior must be one of {sorted(table)}, got {posterior!r}")
+    predict = table[posterior]
+    return lambda state, x, Z, model_type, alpha, full_set_size: predict(state, x, Z, model_type, alpha,
+                                                                         full_set_size=full_set_size, **curv_kw)
+
+
+def _closed_form_batches(state, dataloader, Z, alpha, full_set_size, model_type, predict, link, num_samples, seed, offset,
+                         uncertainty=False):
+    """per batch (link_predictive's result, labels); batch b is drawn with ``example_offset`` = ``offset`` + the number of
+    points before it, so the draws of a point do not depend on the loader's batch size"""
+    from .link import link_predictive
+    for x_b, y_b in dataloader:
+        out = predict(state, x_b, Z, model_type, alpha, full_set_size)
+        out = out if isinstance(out, tuple) else (out,)
+        yield link_predictive(*out, link=link, num_samples=num_samples, seed=seed, example_offset=offset,
+                              return_uncertainty=uncertainty), y_b
+        offset += int(x_b.shape[0])
+
+
+def eval_dataset_closed_form(state, dataloader: Iterable, Z, alpha, full_set_size, model_type="classifier",
+                             posterior: str = "diag", link: str = "probit", cov: str = "diag", num_samples: int = 1000,
+                             seed: int = 0, indices=None, rank=None, *, curvature=None, route=None):
+    """:func:`eval_dataset_probit` with the link a parameter (``link.link_predictive``): ``"probit"`` (then the tensors
+    equal :func:`eval_dataset_probit`'s), ``"mc"`` (``num_samples`` draws per point from ``seed``, on the device),
+    ``"bridge"`` or ``"bridge_norm"``.  ``cov="full"`` asks the posterior's predictive for (B, K, K) covariances, which
+    only ``link="mc"`` uses beyond their diagonal (K <= 64; ``posterior="inducing"`` then takes
+    ``lla.predict_lla_marginals``).  Same posteriors and ``curvature`` / ``route`` / ``indices`` / ``rank`` forwarding as
+    :func:`eval_dataset_probit`.  The draws of a test point depend on ``seed`` and its position in the data set alone:
+    the result does not depend on the loader's batch size.  -> (NLL, accuracy, Brier, ECE, probs, labels)"""
+    predict = _closed_form_predict(posterior, cov, indices, rank, curvature, route)
+    all_probs, all_labels = [], []
+    for probs, y_b in _closed_form_batches(state, dataloader, Z, alpha, full_set_size, model_type, predict, link,
+                                           num_samples, seed, 0):
+        all_probs.append(probs)
+        all_labels.append(y_b.reshape(-1).long().to(probs.device))
+    probs, labels = torch.cat(all_probs), torch.cat(all_labels)
+    nll = -torch.log(torch.gather(probs, -1, labels[:, None]).squeeze(-1)).mean()
+    acc = (probs.argmax(-1) == labels).to(probs.dtype).mean()
+    return float(nll), float(acc), brier_score(probs, labels), ece(probs, labels), probs, labels
+
+
+OOD_SCORES = ("max_prob", "entropy", "mutual_information")
+
+
+def auroc_ood_closed_form(state, id_loader: Iterable, ood_loader: Iterable, Z, alpha, full_set_size,
+                          model_type="classifier", posterior: str = "diag", link: str = "probit", cov: str = "diag",
+                          score: str = "max_prob", num_samples: int = 1000, seed: int = 0, indices=None, rank=None, *,
+                          curvature=None, route=None) -> float:
+    """:func:`auroc_ood` for the closed-form predictives: AUROC of in-distribution (label 0) against OOD (label 1) points
+    under ``score`` = ``"max_prob"`` (:func:`ood_scores`), ``"entropy"`` (H of the predictive) or
+    ``"mutual_information"`` (the epistemic part of the entropy, ``link="mc"`` only: it needs the draws).  Both loaders go
+    through :func:`eval_dataset_closed_form`'s predictive and link; the OOD points are drawn after the in-distribution
+    ones (``example_offset`` continues), so no two points share a stream."""
+    if score not in OOD_SCORES:
+        raise ValueError(f"score must be one of {OOD_SCORES}, got {score!r}")
+    if score == "mutual_information" and link != "mc":
+        raise ValueError("score='mutual_information' needs the draws of link='mc'")
+    predict = _closed_form_predict(posterior, cov, indices, rank, curvature, route)
+    want_mi = score == "mutual_information"
+    scores, counts, offset = [], [], 0
+    for loader in (id_loader, ood_loader):
+        part = []
+        for out, _ in _closed_form_batches(state, loader, Z, alpha, full_set_size, model_type, predict, link, num_samples,
+                                           seed, offset, uncertainty=want_mi):
+            if want_mi:
+                part.append(out[1]["epistemic"])
+            elif score == "entropy":
+                part.append(-torch.xlogy(out, out).sum(-1))
+            else:
+                part.append(ood_scores(out))
+        part = torch.cat(part)
+        scores.append(part)
+        counts.append(len(part))
+        offset += len(part)
+    labels = torch.cat([torch.zeros(counts[0]), torch.ones(counts[1])])
+    return roc_auc(labels, torch.cat(scores))

@@ -25,6 +25,7 @@ from .ekfac import posterior_lla_ekfac, predict_lla_ekfac, predict_lla_ekfac_sca
 from .lowrank import posterior_lla_lowrank, predict_lla_lowrank, predict_lla_lowrank_scalable     # noqa: F401
 from .subnetwork import (SUBNETWORK_MAX_DIM, posterior_lla_subnetwork, predict_lla_subnetwork,      # noqa: F401
                          predict_lla_subnetwork_scalable, subnetwork_indices)
+from .link import LINKS, bridge_predictive, cholesky_semidefinite, link_predictive, mc_predictive   # noqa: F401
 from .prior import check_dim, is_grouped
 from .sample import sample, sample_diag
 from .utils import flatten_nn_params
