@@ -405,6 +405,27 @@ int lip_kfac_predict_scratch(int32_t B, int32_t Kc, int32_t Mt, int32_t N, int64
 int lip_kfac_predict(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_t off, int32_t Mt, int32_t N, const double* V,
                      const double* Ub, const double* R, double* out, int32_t diag, double* scratch, int64_t scratch_doubles,
                      void* stream);
+/* The marginal predictive variances of one layer block at G multiples of the fitted prior, float64, ADDED into out
+ * (G, B, Kc).  With a prior s a (a the fitted prior, s > 0) the whitened factor only scales, so the fitted (V, Ub) serve
+ * every s and, with Ev (Mt, N) the block's eigenvalues in the fitted whitened basis (R = 1 / (Ev + 1) at the fit) and
+ * T_r = V^T J_r Ub,
+ *   out[g][b][k] += sum_{j,l} T_{(k,b)}[j][l]^2 / (Ev[j][l] + scales[g]).
+ * Jr, ldj, off, V, Ub and the row order are those of lip_kfac_predict; Ev is a device (Mt, N) float64 row-major matrix
+ * with entries >= 0 (exact zeros included); scales is a HOST array of G finite values > 0, 1 <= G <= LIP_GRID_MAX.  The
+ * weights 1 / (Ev + s_g) are correctly rounded divisions done once per call into scratch; J Ub lives in scratch, V^T (J Ub)
+ * is formed tile by tile on the float64 matrix pipe, squared in registers and reduced against the G weight tiles, and the
+ * (row, tile, g) partial sums (also in scratch) are folded in tile order: T is never written, no atomics.  Two calls with
+ * identical arguments agree bitwise, a result does not depend on the scratch size, and slice g depends on scales[g]
+ * alone, not on G or the other scales.  lip_kfac_predict_grid_scratch gives the doubles for all B points at once; a
+ * smaller scratch, at least G Mt N + Kc (Mt N + ceil(Mt / 32) ceil(N / 32) G) doubles (the weights and one point), makes
+ * the call run in chunks of points.  A null pointer, a non-positive extent, G < 1 or G > LIP_GRID_MAX, a scale that is
+ * not finite or is <= 0, off < 0, ldj < off + Mt N, Mt N >= 2^31 or a scratch below one point returns LIP_ERR_ARG and
+ * leaves out untouched; every check runs on the host before any launch. */
+#define LIP_GRID_MAX 32
+int lip_kfac_predict_grid_scratch(int32_t B, int32_t Kc, int32_t Mt, int32_t N, int32_t G, int64_t* doubles);
+int lip_kfac_predict_grid(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_t off, int32_t Mt, int32_t N,
+                          const double* V, const double* Ub, const double* Ev, const double* scales, int32_t G, double* out,
+                          double* scratch, int64_t scratch_doubles, void* stream);
 /* Second moments of the factor rows in a block's Kronecker eigenbasis (EKFAC), float64, ADDED into Lam (Mt, N):
  *   Lam[j][l] += sum_{r < R} ( sum_{f,k} V[f][j] W_r[f][k] Ub[k][l] )^2
  * W (R, ldw) float32, the rows lip_vjp_rows writes for one-hot probes in LIP_HEAD_L mode; W_r the (Mt, N) row-major

@@ -134,6 +134,9 @@ SIGNATURES = {
     "lip_kfac_predict_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "lip_kfac_predict": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V,
                                    C.c_int32, _V, C.c_int64, _V]),
+    "lip_kfac_predict_grid_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_kfac_predict_grid": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V,
+                                        C.POINTER(C.c_double), C.c_int32, _V, _V, C.c_int64, _V]),
     "lip_kfac_eigen_sqsum_scratch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "lip_kfac_eigen_sqsum": (C.c_int, [_V, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V, C.c_int64,
                                        _V]),

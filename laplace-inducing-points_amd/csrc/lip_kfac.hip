@@ -25,7 +25,14 @@
 // Patch projection (lip_kfac_project_patches, for the EIGEN sweep of lip_engine.hip, which forms the same Lam without
 // factor rows):  AV[(i,t)][j] = sum_e at_{i,t}[e] V[e][j], float32, rounded once.  ll_project_kernel (lip_gramtile.h)
 // with an operand functor that gathers the patch entries as the input Gram's does.
+//
+// Grid predictive (lip_kfac_predict_grid, the marginal variances at G multiples s_g of the fitted prior in one pass):
+//   out[g][b][k]  += sum_{j,l} T_{(k,b)}[j][l]^2 / (Ev[j][l] + s_g)
+// The weights 1 / (Ev + s_g) are divided once per call into scratch; stage one is the predictive's; stage two is the
+// square-sum kernel's tile product, reduced in registers against every weight tile, one partial sum per
+// (row, tile, scale); a fold adds the tiles in tile order.  T is never written, no atomics.
 #include <algorithm>
+#include <cmath>
 #include "lip_internal.h"
 #include "lip_gramtile.h"
 
@@ -227,6 +234,88 @@ __global__ __launch_bounds__(256) void kfac_sqsum_fold_kernel(const double* __re
   Lam[e] += t;
 }
 
+// The scales of one grid call, passed by value: every block reads its own s_g from the kernel arguments
+struct KfacGridScales {
+  double s[LIP_GRID_MAX];
+};
+
+// Wt[g][e] = 1 / (Ev[e] + s_g), one correctly rounded division per entry and scale: blockIdx = (256 entries, g)
+__global__ __launch_bounds__(256) void kfac_grid_weights_kernel(const double* __restrict__ Ev, int E, KfacGridScales sc,
+                                                                double* __restrict__ Wt) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  Wt[(long long)blockIdx.y * E + e] = 1.0 / (Ev[e] + sc.s[blockIdx.y]);
+}
+
+// part[(lr, tile, g)] = sum over the tile of T_lr o T_lr o Wt_g, T_lr = V^T W_lr: the product of kfac_vt_kernel (same
+// grid, same lane map, the sum in f order) squared in registers, entries past the matrix set to zero, then one pass per
+// scale over the weight tile, which is read from Wt where it lies (a tile is owned by one wave, so no weight is read
+// twice by a block).  A lane sums its 16 entries in register order and the wave meets in a fixed butterfly, so a slice
+// depends on its own weights alone.  T is never written.
+__global__ __launch_bounds__(256) void kfac_grid_kernel(const double* __restrict__ V, const double* __restrict__ W,
+                                                        const double* __restrict__ Wt, int Mt, int N, int MT32, int NT32, int G,
+                                                        double* __restrict__ part) {
+  const int lane = threadIdx.x & 63, i16 = lane & 15, q = lane >> 4;
+  const int ct = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (ct * 32 >= N) return;
+  const long long lr = blockIdx.x / MT32;
+  const int rt = (int)(blockIdx.x - lr * MT32);
+  const int E = Mt * N;
+  const double* Wr = W + lr * E;
+  const double* pa[2];
+  const double* pb[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    pa[t] = V + min(rt * 32 + 16 * t + i16, Mt - 1);                                         // clamped: zeroed below
+    pb[t] = Wr + min(ct * 32 + 16 * t + i16, N - 1);
+  }
+  ll_f64x4 acc[2][2];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) acc[tm][tn] = ll_f64x4{0.0, 0.0, 0.0, 0.0};
+  ll_tile_mac(F64Cols{Mt}, pa, F64Cols{N}, pb, Mt, q, acc);
+  // register r of lane (i16, q) is (row q + 4 r, col i16) of its 16 x 16 accumulator (ll_tile_store)
+  double sq[16];
+  int at[16];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rt * 32 + 16 * tm + q + 4 * r, col = ct * 32 + 16 * tn + i16;
+        const int i = (2 * tm + tn) * 4 + r;
+        sq[i] = (row < Mt && col < N) ? acc[tm][tn][r] * acc[tm][tn][r] : 0.0;
+        at[i] = min(row, Mt - 1) * N + min(col, N - 1);                                      // clamped: times zero
+      }
+  double* mine = part + ((lr * MT32 + rt) * NT32 + ct) * G;
+  for (int g = 0; g < G; ++g) {
+    const double* __restrict__ w = Wt + (long long)g * E;
+    double t = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t = fma(sq[i], w[at[i]], t);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
+    if (lane == 0) mine[g] = t;
+  }
+}
+
+// out[g][b0 + bl][k] += the tiles' partial sums of local row lr = bl Kc + k in tile order: a thread per (lr, g)
+__global__ __launch_bounds__(256) void kfac_grid_fold_kernel(const double* __restrict__ part, long long lrows, int tiles, int G,
+                                                             int B, int Kc, int b0, double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= lrows * G) return;
+  const long long lr = i / G;
+  const int g = (int)(i - lr * G);
+  const double* p = part + lr * tiles * G + g;
+  double t = p[0];
+  for (int tile = 1; tile < tiles; ++tile) t += p[(long long)tile * G];
+  const long long bl = lr / Kc;
+  const int k = (int)(lr - bl * Kc);
+  out[((long long)g * B + b0 + bl) * Kc + k] += t;
+}
+
 // The A operand of ll_project_kernel for the patch projection AV = patches(X) V: row i = (image, oh, ow), element e the
 // patch entry KfacPatchOperands gathers ((kh, kw, ci) order after the leading 1 of a bias; zero outside the image; the
 // address clamped, so nothing outside X is read)
@@ -401,6 +490,78 @@ int lip_kfac_predict(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_
     LIP_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(kfac_quad_kernel, dim3((unsigned)(nb * pairs)), dim3(256), 0, st, R, (const double*)T, (int)Kc, E, (int)b0,
                        (int)pairs, out, (int)diag);
+    LIP_CHECK_HIP(hipGetLastError());
+  }
+  return LIP_OK;
+}
+
+// the doubles of a grid call that do not depend on the points (the G weight matrices) and those of one point (J Ub of its
+// Kc rows and their (tile, g) partial sums)
+static long long kfac_grid_fixed(int32_t Mt, int32_t N, int32_t G) { return (long long)G * Mt * N; }
+
+static long long kfac_grid_per_point(int32_t Kc, int32_t Mt, int32_t N, int32_t G) {
+  const long long tiles = (long long)((Mt + 31) / 32) * ((N + 31) / 32);
+  return (long long)Kc * ((long long)Mt * N + tiles * G);
+}
+
+int lip_kfac_predict_grid_scratch(int32_t B, int32_t Kc, int32_t Mt, int32_t N, int32_t G, int64_t* doubles) {
+  if (!doubles || !kfac_block_ok(B, Kc, 0, Mt, N) || G < 1 || G > LIP_GRID_MAX) {
+    set_error("lip_kfac_predict_grid_scratch: bad argument");
+    return LIP_ERR_ARG;
+  }
+  *doubles = kfac_grid_fixed(Mt, N, G) + (long long)B * kfac_grid_per_point(Kc, Mt, N, G);
+  return LIP_OK;
+}
+
+int lip_kfac_predict_grid(const float* Jr, int64_t ldj, int32_t B, int32_t Kc, int64_t off, int32_t Mt, int32_t N,
+                          const double* V, const double* Ub, const double* Ev, const double* scales, int32_t G, double* out,
+                          double* scratch, int64_t scratch_doubles, void* stream) {
+  if (!Jr || !V || !Ub || !Ev || !scales || !out || !scratch || !kfac_block_ok(B, Kc, off, Mt, N) || G < 1 || G > LIP_GRID_MAX ||
+      ldj < off + (long long)Mt * N) {
+    set_error("lip_kfac_predict_grid: bad argument");
+    return LIP_ERR_ARG;
+  }
+  KfacGridScales sc;
+  for (int g = 0; g < LIP_GRID_MAX; ++g) {
+    sc.s[g] = g < G ? scales[g] : 1.0;
+    if (!std::isfinite(sc.s[g]) || sc.s[g] <= 0.0) {
+      set_error("lip_kfac_predict_grid: scale %d is not a finite positive number", g);
+      return LIP_ERR_ARG;
+    }
+  }
+  const int E = Mt * N, MT32 = (Mt + 31) / 32, NT32 = (N + 31) / 32;
+  const long long fixed = kfac_grid_fixed(Mt, N, G), per_point = kfac_grid_per_point(Kc, Mt, N, G);
+  if (scratch_doubles < fixed + per_point) {
+    set_error("lip_kfac_predict_grid: scratch of %lld doubles, at least %lld needed for one point "
+              "(lip_kfac_predict_grid_scratch: all points)", (long long)scratch_doubles, fixed + per_point);
+    return LIP_ERR_ARG;
+  }
+  // points per chunk: what the scratch holds after the weights, within the grids' 2^31 - 1 blocks
+  long long Bc = (scratch_doubles - fixed) / per_point;
+  Bc = std::min<long long>(Bc, B);
+  Bc = std::min<long long>(Bc, 0x7fffffffll / ((long long)Kc * std::max(Mt, 32)));
+  if (Bc < 1 || (N + 127) / 128 > 65535) {
+    set_error("lip_kfac_predict_grid: Kc = %d, Mt = %d, N = %d is too large", (int)Kc, (int)Mt, (int)N);
+    return LIP_ERR_ARG;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned gy = (unsigned)((N + 127) / 128);
+  double* Wt = scratch;
+  hipLaunchKernelGGL(kfac_grid_weights_kernel, dim3((unsigned)((E + 255) / 256), (unsigned)G), dim3(256), 0, st, Ev, E, sc, Wt);
+  LIP_CHECK_HIP(hipGetLastError());
+  for (long long b0 = 0; b0 < B; b0 += Bc) {
+    const long long nb = std::min<long long>(Bc, B - b0), lrows = nb * Kc, rows = lrows * Mt;
+    double* W = scratch + fixed;
+    double* part = W + lrows * E;
+    hipLaunchKernelGGL((ll_project_kernel<KfacBlockRows, double>), dim3((unsigned)((rows + 31) / 32), gy), dim3(256), 0, st,
+                       KfacBlockRows{Jr, (long long)ldj, (long long)off, (int)B, (int)Kc, (int)b0, (int)Mt, (int)N}, rows, (int)N,
+                       Ub, (int)N, W);
+    LIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kfac_grid_kernel, dim3((unsigned)(lrows * MT32), gy), dim3(256), 0, st, V, (const double*)W,
+                       (const double*)Wt, (int)Mt, (int)N, MT32, NT32, (int)G, part);
+    LIP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(kfac_grid_fold_kernel, dim3((unsigned)((lrows * G + 255) / 256)), dim3(256), 0, st, (const double*)part,
+                       lrows, MT32 * NT32, (int)G, (int)B, (int)Kc, (int)b0, out);
     LIP_CHECK_HIP(hipGetLastError());
   }
   return LIP_OK;

@@ -102,9 +102,17 @@ def corrected_fits(fits, Lams, recal: float):
     return [(f[0], (1.0 / (recal * Lam.clamp_min(0.0) + 1.0)).contiguous(), f[2]) for f, Lam in zip(fits, Lams)]
 
 
+def block_eigenvalues(Lams, recal: float) -> List[torch.Tensor]:
+    """[Ev (Mt, N)] = recal Lam clamped at 0: the corrected eigenvalues in the whitened basis, R = 1 / (Ev + 1)
+    (:func:`corrected_fits`); what the grid predictive and ``kfac.rescale_fit`` take next to (V, Ub)"""
+    return [(recal * Lam.clamp_min(0.0)).contiguous() for Lam in Lams]
+
+
 def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments="rows", curvature=None):
     """(blocks, [(V, R, Ub)], rem_idx, rem_var, rem_prior); the prior is checked before anything is allocated.  Under a
-    curvature spec the KFAC factors that give the basis, the second moments and the remainder's diagonal all use it."""
+    curvature spec the KFAC factors that give the basis, the second moments and the remainder's diagonal all use it.
+    The tuple is a ``kfac.Fit``: it carries Ev = recal Lam (clamped at 0) of every block, R = 1 / (Ev + 1), and the
+    remainder's curvature for the grid of prior precisions."""
     blocks = _kfac.block_table(map_state)
     D = flatten_nn_params(map_state.params)[0].numel()
     rows = [_kfac.block_prior_rows(alpha, b, D) for b in blocks]
@@ -117,12 +125,13 @@ def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments=
                                 **_route_kwargs(moments, curvature))
     fits = corrected_fits(kfits, Lams, recal)
     dev = As[0].device
-    rem_var = torch.zeros(0, device=dev, dtype=torch.float64)
+    rem_var = h_rem = torch.zeros(0, device=dev, dtype=torch.float64)
     if rem.numel():
         diag = _ggn.compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk,
                                      curvature=curvature)
-        rem_var = 1.0 / (a_rem.to(dev) + diag.double()[rem.to(dev)])
-    return blocks, fits, rem.to(dev), rem_var, a_rem.to(dev)
+        h_rem = diag.double()[rem.to(dev)]
+        rem_var = 1.0 / (a_rem.to(dev) + h_rem)
+    return _kfac.Fit.of((blocks, fits, rem.to(dev), rem_var, a_rem.to(dev)), block_eigenvalues(Lams, recal), h_rem)
 
 
 _FIT_CACHE = {}          # one entry, as kfac._FIT_CACHE
@@ -199,6 +208,21 @@ def predict_lla_ekfac(map_state, Xnew, Z, model_type, alpha, full_set_size=None,
                                                curvature)
     return _kfac.predictive_from_fit(map_state, Xnew, model_type, fits, (rem_idx, rem_var), cov, batch,
                                      **_kfac.route_kwargs(route))
+
+
+def predict_lla_ekfac_grid(map_state, Xnew, Z, model_type, alpha, scales, full_set_size=None, batch: int = 256,
+                           example_chunk: Optional[int] = None, *, moments: Optional[str] = None, curvature=None,
+                           route: Optional[str] = None):
+    """:func:`predict_lla_ekfac` (``cov="diag"``) at the priors s_g ``alpha`` for every s_g of ``scales`` at once, in
+    the shapes of :func:`kfac.predict_lla_kfac_grid`: one fit at ``alpha`` (the basis and the second moments in it do
+    not move with s: Lam -> Lam / s), one pass over the rows of a test batch, Ev = recal Lam clamped at 0.  ``moments``
+    and ``curvature`` choose the fit, ``route`` the predictive, as in :func:`predict_lla_ekfac`."""
+    _kfac.checked_route(route)
+    scales = _kfac.checked_scales(scales)
+    fit = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, moments, curvature)
+    _, fits, rem_idx, _, a_rem = fit
+    return _kfac.grid_predictive_from_fit(map_state, Xnew, model_type, fits, fit.Evs, (rem_idx, a_rem, fit.h_rem), scales,
+                                          batch, **_kfac.route_kwargs(route))
 
 
 def predict_lla_ekfac_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1,

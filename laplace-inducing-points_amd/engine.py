@@ -1048,6 +1048,61 @@ class LinearizedNet:
             self._kfac_predict_rows(Jr, b1 - b0, K, fits, rem, out[b0:b1], False)
         return out
 
+    KFAC_GRID_MAX = 32                 # LIP_GRID_MAX: the scales of one lip_kfac_predict_grid call
+
+    def kfac_predict_grid(self, bases, Evs: List[torch.Tensor], rem, scales, class_chunk: Optional[int] = None) -> torch.Tensor:
+        """The marginal variances of :meth:`kfac_predict` (``diag``) at the priors s_g a for every s_g of ``scales``, a
+        the prior of the fit: (G, n, K) float64 from ONE pass over the Jacobian rows.  ``bases[l] = (V, Ub)`` and
+        ``Evs[l]`` (Mt, N) are the fitted eigenbasis and the eigenvalues in the whitened basis of every layer block
+        (:meth:`kfac_blocks` order; contiguous float64 device matrices; R = 1 / (Ev + 1) at the fit), so that slice g is
+        sum_{j,l} T[j][l]^2 / (Ev[j][l] + s_g) per block (``lip_kfac_predict_grid``, at most 32 scales per call; more
+        go through it in groups of 32).  ``rem`` = (indices, a_rem, h_rem): the parameters outside every block, their
+        prior precisions at the fit and their curvature; their term (J_d^2) @ (1 / (s_g a + h))^T is float64 torch.  The
+        class blocks, the row-block cap and the ``KFAC_SCRATCH_BYTES`` cap are those of :meth:`kfac_predict`."""
+        blocks = self.kfac_blocks()
+        if len(bases) != len(blocks) or len(Evs) != len(blocks):
+            raise ValueError(f"{len(blocks)} layer blocks need {len(blocks)} (V, Ub) pairs and {len(blocks)} matrices in Evs")
+        for b, (V, Ub), Ev in zip(blocks, bases, Evs):
+            for name, t, shape in (("V", V, (b.Mt, b.Mt)), ("Ub", Ub, (b.N, b.N)), ("Ev", Ev, (b.Mt, b.N))):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"{name} of the block at offset {b.off} must be a contiguous float64 device matrix of "
+                                     f"{shape[0]} x {shape[1]}")
+        s = torch.as_tensor(scales, dtype=torch.float64).reshape(-1).cpu()
+        if s.numel() < 1 or not bool((torch.isfinite(s) & (s > 0)).all()):
+            raise ValueError("scales must be one or more finite positive numbers")
+        idx = rem[0].to(self.device)
+        a_rem, h_rem = (t.to(device=self.device, dtype=torch.float64) for t in rem[1:])
+        G, K, n = s.numel(), self.K, self.n
+        w_rem = 1.0 / (s.to(self.device)[:, None] * a_rem[None, :] + h_rem[None, :]) if idx.numel() else None   # (G, r)
+        out = torch.zeros(G, n, K, device=self.device, dtype=torch.float64)
+        for k0, k1 in self._class_blocks(class_chunk):
+            Kc = k1 - k0
+            rows = self._one_hot_rows(k0, k1, "raw")
+            part = out if Kc == K else torch.zeros(G, n, Kc, device=self.device, dtype=torch.float64)
+            for g0 in range(0, G, self.KFAC_GRID_MAX):
+                Gc = min(self.KFAC_GRID_MAX, G - g0)
+                sc = (C.c_double * Gc)(*s[g0:g0 + Gc].tolist())
+                dst = part[g0:g0 + Gc]                                                       # contiguous (Gc, n, Kc)
+                for b, (V, Ub), Ev in zip(blocks, bases, Evs):
+                    doubles = C.c_int64(0)
+                    nv.check(self.lib.lip_kfac_predict_grid_scratch(n, Kc, b.Mt, b.N, Gc, C.byref(doubles)),
+                             "lip_kfac_predict_grid_scratch")
+                    tiles = ((b.Mt + 31) // 32) * ((b.N + 31) // 32)
+                    one = Gc * b.Mt * b.N + Kc * (b.Mt * b.N + tiles * Gc)
+                    scratch = self._f64_scratch("lip_kfac_predict_grid",
+                                                min(doubles.value, max(one, self.KFAC_SCRATCH_BYTES // 8)))
+                    nv.check(self.lib.lip_kfac_predict_grid(rows.data_ptr(), self.D, n, Kc, b.off, b.Mt, b.N, V.data_ptr(),
+                                                            Ub.data_ptr(), Ev.data_ptr(), sc, Gc, dst.data_ptr(),
+                                                            scratch.data_ptr(), scratch.numel(), nv.stream_ptr()),
+                             "lip_kfac_predict_grid")
+            if w_rem is not None:
+                Jd = rows[:, :, idx].double()                                               # (Kc, n, r)
+                part += ((Jd * Jd) @ w_rem.T).permute(2, 1, 0)                              # (Kc, n, G) -> (G, n, Kc)
+            del rows                                                                        # before the next block's rows
+            if part is not out:
+                out[:, :, k0:k1] = part
+        return out
+
     def kfac_eigen_sqsums(self, bases, Lams: List[torch.Tensor], class_chunk: Optional[int] = None) -> List[torch.Tensor]:
         """ADD Lam_l[j][m] += sum_i sum_k ((V_l^T mat_l(J_i^T L_i e_k) Ub_l)[j][m])^2 of this binding's examples into every
         (Mt, N) float64 matrix of ``Lams``: the second moments of the per-example factor rows in the eigenbasis

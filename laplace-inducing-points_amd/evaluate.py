@@ -257,6 +257,73 @@ def eval_dataset_closed_form(state, dataloader: Iterable, Z, alpha, full_set_siz
     return float(nll), float(acc), brier_score(probs, labels), ece(probs, labels), probs, labels
 
 
+def scaled_prior(alpha, s: float):
+    """the prior s ``alpha``: a float for a scalar, a :class:`prior.GroupedPrior` with every value multiplied otherwise"""
+    from .prior import is_grouped
+    return alpha.with_values(alpha.values * float(s)) if is_grouped(alpha) else float(alpha) * float(s)
+
+
+def _classifier_metrics(probs, labels):
+    nll = -torch.log(torch.gather(probs, -1, labels[:, None]).squeeze(-1)).mean()
+    acc = (probs.argmax(-1) == labels).to(probs.dtype).mean()
+    return float(nll), float(acc), brier_score(probs, labels), ece(probs, labels)
+
+
+def gaussian_nll(y, mean, var) -> float:
+    """the mean negative log density of y under N(mean, var), float64"""
+    y, mean, var = (torch.as_tensor(t).double().reshape(-1) for t in (y, mean, var))
+    return float((0.5 * (torch.log(2.0 * math.pi * var) + (y - mean) ** 2 / var)).mean())
+
+
+def eval_dataset_closed_form_grid(state, dataloader: Iterable, Z, alpha, scales, full_set_size, model_type="classifier",
+                                  posterior: str = "kfac", link: str = "probit", num_samples: int = 1000, seed: int = 0,
+                                  indices=None, rank=None, *, curvature=None, route=None):
+    """:func:`eval_dataset_closed_form` (``cov="diag"``) at the priors s_g ``alpha`` for every s_g of ``scales``: a list
+    of G tuples (NLL, accuracy, Brier, ECE).  ``posterior="kfac"`` / ``"ekfac"``: ONE pass over the loader and one fit
+    at ``alpha``; per batch one grid predictive (``lla.predict_lla_kfac_grid`` / ``predict_lla_ekfac_grid``) and G calls
+    of ``link.link_predictive`` on (f_mean, f_var[g]), batch b drawn with ``example_offset`` = the number of points
+    before it, as :func:`eval_dataset_closed_form` draws.  Every other closed-form posterior loops that function at
+    s_g ``alpha`` (a :class:`prior.GroupedPrior` scaled by ``with_values``), so ``dataloader`` must then be re-iterable.
+    ``model_type="regressor"``: NLL is the Gaussian one at variance f_var + exp(logvar), the other three entries nan."""
+    from .kfac import checked_scales
+    from .link import link_predictive
+    scales = checked_scales(scales)
+    regressor = model_type == "regressor"
+    if posterior not in ("kfac", "ekfac"):
+        if regressor:
+            raise ValueError("the regressor's Gaussian NLL on a grid is computed for posterior='kfac' and 'ekfac' only")
+        return [eval_dataset_closed_form(state, dataloader, Z, scaled_prior(alpha, s), full_set_size, model_type, posterior,
+                                         link, "diag", num_samples, seed, indices, rank, curvature=curvature,
+                                         route=route)[:4] for s in scales]
+    from .lla import predict_lla_ekfac_grid, predict_lla_kfac_grid
+    predict = predict_lla_kfac_grid if posterior == "kfac" else predict_lla_ekfac_grid
+    kw = {} if curvature is None else {"curvature": curvature}
+    if route is not None:
+        kw["route"] = route
+    G = len(scales)
+    parts, all_labels, offset = [[] for _ in range(G)], [], 0
+    for x_b, y_b in dataloader:
+        f_mean, f_var = predict(state, x_b, Z, model_type, alpha, scales, full_set_size=full_set_size, **kw)
+        for g in range(G):
+            if regressor:
+                parts[g].append(torch.stack([f_mean.reshape(-1), f_var[g].reshape(-1)]))
+            else:
+                parts[g].append(link_predictive(f_mean, f_var[g], link=link, num_samples=num_samples, seed=seed,
+                                                example_offset=offset))
+        all_labels.append(y_b.reshape(-1).to(f_mean.device))
+        offset += int(x_b.shape[0])
+    labels = torch.cat(all_labels)
+    if regressor:
+        from .ggn import _logvar
+        noise = math.exp(_logvar(state))
+        out = []
+        for g in range(G):
+            mv = torch.cat(parts[g], dim=1)
+            out.append((gaussian_nll(labels, mv[0], mv[1] + noise), float("nan"), float("nan"), float("nan")))
+        return out
+    return [_classifier_metrics(torch.cat(parts[g]), labels.long()) for g in range(G)]
+
+
 OOD_SCORES = ("max_prob", "entropy", "mutual_information")
 
 

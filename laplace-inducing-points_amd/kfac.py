@@ -123,8 +123,44 @@ def fit_blocks(blocks, As, Ss, rows, recal: float, M: int, classifier: bool):
             for b, A, S, a in zip(blocks, As, Ss, rows)]
 
 
+def block_eigenvalues(fits) -> List[torch.Tensor]:
+    """[Ev (Mt, N)] = c outer(lam, mu) of the :func:`fit_blocks` tuples: the eigenvalues of every block's curvature in its
+    whitened basis, R = 1 / (Ev + 1); what the grid predictive and :func:`rescale_fit` take next to (V, Ub)"""
+    return [(c * lam[:, None] * mu[None, :]).contiguous() for _, _, _, lam, mu, c in fits]
+
+
+def rescale_fit(triples, Evs, rem, s: float):
+    """The fit at the prior s a from the fit at a, without any ``eigh``: for a common factor s > 0 the whitened factor
+    D A D only scales, so the eigenvectors stay and the eigenvalues divide by s.  ``triples``: the (V, R, Ub) (or longer
+    ``fit_blocks`` tuples; R is not read) of every block, ``Evs``: their eigenvalues in the whitened basis
+    (:func:`block_eigenvalues`; ``recal * Lam.clamp_min(0)`` for EKFAC), ``rem`` = (indices, a_rem, h_rem): the remainder's
+    parameters, their precisions at a and their curvature.  -> ``([(V / sqrt(s), 1 / (Ev / s + 1), Ub)], rem_var)``,
+    the covariance V [1 / (Ev + s)] V^T (x) Ub Ub^T per block and 1 / (s a_d + h_d) for the remainder; float64 on the
+    device of the operands (CPU included)."""
+    s = float(s)
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError(f"the scale of a prior must be a finite positive number, got {s!r}")
+    out = [((f[0] / math.sqrt(s)).contiguous(), (1.0 / (Ev / s + 1.0)).contiguous(), f[2]) for f, Ev in zip(triples, Evs)]
+    _, a_rem, h_rem = rem
+    return out, 1.0 / (s * a_rem + h_rem)
+
+
+class Fit(tuple):
+    """The tuple a private ``_fit`` returns, unchanged in length and order, carrying next to it what the grid of prior
+    precisions needs of the same fit: ``Evs``, every block's eigenvalues in its whitened basis, and ``h_rem``, the
+    remainder's curvature.  With them the fit holds the posterior at every multiple of the prior (:func:`rescale_fit`)."""
+    Evs = None
+    h_rem = None
+
+    @classmethod
+    def of(cls, items, Evs, h_rem):
+        out = cls(items)
+        out.Evs, out.h_rem = Evs, h_rem
+        return out
+
+
 def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, curvature=None):
-    """(blocks, fits, rem_idx, rem_var, rem_prior); the prior is checked before anything is allocated"""
+    """(blocks, fits, rem_idx, rem_var, rem_prior), a :class:`Fit`; the prior is checked before anything is allocated"""
     blocks = block_table(map_state)
     D = flatten_nn_params(map_state.params)[0].numel()
     rows = [block_prior_rows(alpha, b, D) for b in blocks]
@@ -133,12 +169,13 @@ def _fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, curvatur
     blocks, As, Ss, M = compute_kfac_factors(map_state, Z, model_type, example_chunk=example_chunk, curvature=curvature)
     fits = fit_blocks(blocks, As, Ss, rows, _recal(map_state, M, model_type, full_set_size), M, model_type != "regressor")
     dev = As[0].device
-    rem_var = torch.zeros(0, device=dev, dtype=torch.float64)
+    rem_var = h_rem = torch.zeros(0, device=dev, dtype=torch.float64)
     if rem.numel():
         diag = _ggn.compute_ggn_diag(map_state, Z, model_type, full_set_size=full_set_size, example_chunk=example_chunk,
                                      curvature=curvature)
-        rem_var = 1.0 / (a_rem.to(dev) + diag.double()[rem.to(dev)])
-    return blocks, fits, rem.to(dev), rem_var, a_rem.to(dev)
+        h_rem = diag.double()[rem.to(dev)]
+        rem_var = 1.0 / (a_rem.to(dev) + h_rem)
+    return Fit.of((blocks, fits, rem.to(dev), rem_var, a_rem.to(dev)), block_eigenvalues(fits), h_rem)
 
 
 def _prior_key(alpha):
@@ -253,6 +290,54 @@ def predictive_from_fit(map_state, Xnew, model_type, triples, rem, cov: str, bat
     if model_type == "regressor":
         return MultivariateNormalFullCovariance(loc=f_mean.squeeze(), covariance_matrix=torch.diag(f_out.reshape(-1)))
     return MultivariateNormalFullCovariance(loc=f_mean.squeeze(), covariance_matrix=f_out)
+
+
+def checked_scales(scales) -> List[float]:
+    """the scales of a grid as floats; ``ValueError`` unless there is at least one and all are finite and positive"""
+    vals = [float(s) for s in torch.as_tensor(scales, dtype=torch.float64).reshape(-1).tolist()]
+    if not vals or not all(math.isfinite(s) and s > 0.0 for s in vals):
+        raise ValueError("scales must be one or more finite positive numbers")
+    return vals
+
+
+def grid_predictive_from_fit(map_state, Xnew, model_type, triples, Evs, rem, scales, batch: int, route: str = "rows"):
+    """the predictive of :func:`predict_lla_kfac_grid` from the (V, R, Ub) and Ev of every block and the remainder's
+    (indices, a_rem, h_rem): :meth:`LinearizedNet.kfac_predict_grid` on ``batch`` test points at a time, one pass over
+    their Jacobian rows for all scales.  ``route="sweep"``: :meth:`LinearizedNet.kfac_predict_sweep` once per scale on
+    the triples of :func:`rescale_fit`, no Jacobian row and no refit."""
+    scales = checked_scales(scales)
+    sweep = checked_route(route) == "sweep"
+    if sweep:
+        rescaled = [rescale_fit(triples, Evs, rem, s) for s in scales]
+    else:
+        bases = [(f[0], f[2]) for f in triples]
+    means, outs = [], []
+    for s0 in range(0, Xnew.shape[0], batch):
+        eng = _ggn.get_engine(map_state, Xnew[s0:s0 + batch], model_type)
+        if sweep:
+            outs.append(torch.stack([eng.kfac_predict_sweep(t, (rem[0], var), diag=True) for t, var in rescaled]))
+        else:
+            outs.append(eng.kfac_predict_grid(bases, Evs, rem, scales))
+        means.append(eng.outputs().double())
+    f_mean, f_var = torch.cat(means), torch.cat(outs, dim=1)
+    return (f_mean.squeeze(-1), f_var.squeeze(-1)) if model_type == "regressor" else (f_mean, f_var)
+
+
+def predict_lla_kfac_grid(map_state, Xnew, Z, model_type, alpha, scales, full_set_size=None, batch: int = 256,
+                          example_chunk: Optional[int] = None, *, curvature=None, route: Optional[str] = None):
+    """:func:`predict_lla_kfac` (``cov="diag"``) at the priors s_g ``alpha`` for every s_g of ``scales`` at once:
+    ``(f_mean (B, K), f_var (G, B, K))`` float64, (B,) and (G, B) for a regressor; ``alpha`` a scalar or a
+    :class:`prior.GroupedPrior`, which every s_g multiplies as a whole.  The whitened factor of a block only scales with
+    s, so ONE fit at ``alpha`` (cached as :func:`predict_lla_kfac`'s) and one projection T = V^T J Ub per test batch
+    serve the whole grid: var_g = sum T^2 / (Ev + s_g) + sum_d J_d^2 / (s_g a_d + h_d) (``lip_kfac_predict_grid``).
+    ``route="sweep"`` runs the row-free predictive once per scale on the rescaled fit instead (:func:`rescale_fit`);
+    the default (None) is ``"rows"``."""
+    checked_route(route)
+    scales = checked_scales(scales)
+    fit = _cached_fit(map_state, Z, model_type, alpha, full_set_size, example_chunk, curvature)
+    _, fits, rem_idx, _, a_rem = fit
+    return grid_predictive_from_fit(map_state, Xnew, model_type, [(V, R, Ub) for V, R, Ub, _, _, _ in fits], fit.Evs,
+                                    (rem_idx, a_rem, fit.h_rem), scales, batch, **route_kwargs(route))
 
 
 def predict_lla_kfac_scalable(map_state, Xnew, Z, model_type, alpha, key=None, full_set_size=None, num_samples=1,

@@ -19,9 +19,9 @@ from .last_layer import (LAST_LAYER_MAX_DIM, posterior_lla_last_layer, predict_l
                          predict_lla_last_layer_scalable)                                         # beside their diagonal twins
 from .last_layer_kron import (posterior_lla_last_layer_kron, predict_lla_last_layer_kron,            # noqa: F401
                               predict_lla_last_layer_kron_scalable)
-from .kfac import posterior_lla_kfac, predict_lla_kfac, predict_lla_kfac_scalable                 # noqa: F401
+from .kfac import posterior_lla_kfac, predict_lla_kfac, predict_lla_kfac_grid, predict_lla_kfac_scalable   # noqa: F401
 from .fisher import Cotangents, EmpiricalFisher, MCFisher, sample_head_cotangents                 # noqa: F401
-from .ekfac import posterior_lla_ekfac, predict_lla_ekfac, predict_lla_ekfac_scalable             # noqa: F401
+from .ekfac import posterior_lla_ekfac, predict_lla_ekfac, predict_lla_ekfac_grid, predict_lla_ekfac_scalable   # noqa: F401
 from .lowrank import posterior_lla_lowrank, predict_lla_lowrank, predict_lla_lowrank_scalable     # noqa: F401
 from .subnetwork import (SUBNETWORK_MAX_DIM, posterior_lla_subnetwork, predict_lla_subnetwork,      # noqa: F401
                          predict_lla_subnetwork_scalable, subnetwork_indices)

@@ -13,6 +13,9 @@ Layer-wise precisions (``*_layerwise``, not reference functions): with A = diag(
 det(A + r W W^T) = prod_g alpha_g^{D_g} det(I_d + r sum_g G_g / alpha_g) with the per-group Grams G_g of
 ``ggn.grouped_grams`` — again independent of the precisions, so ONE pass over the materialised factor is followed by
 d x d float64 algebra per evaluation (a Cholesky factorisation) for the value and the exact gradient in all log alpha_g.
+
+``grid_search_alpha`` is the reference's validation grid search (``src/grid_search.py:9-88``); for the closed-form KFAC
+and EKFAC posteriors the whole grid comes from one fit and one pass per validation batch (``kfac.predict_lla_kfac_grid``).
 """
 from __future__ import annotations
 
@@ -237,6 +240,77 @@ def fit_alpha_subnetwork(X, state, model_type, indices, full_set_size=None, alph
     N = full_set_size or X.shape[0]
     lam, DS, theta2 = _spectrum_subnetwork(X, state, model_type, indices)
     return _fit_from_spectrum(lam, DS, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
+
+
+# ---- validation grid search (the reference's ``src/grid_search.py:9-88``) ------------------------------------------------
+def refinement_points(grid, best: int):
+    """the three refinement values of ``grid_search_alpha`` (``:49-64``): one quarter, one half and three quarters, in
+    log10, of the bracket between the best point's two neighbours (at an end: the end point and its one neighbour)"""
+    n = len(grid)
+    if n < 2:
+        raise ValueError("the refinement needs a coarse grid of at least two points")
+    lo, hi = (0, 1) if best == 0 else ((n - 2, n - 1) if best == n - 1 else (best - 1, best + 1))
+    ll, lr = math.log10(grid[lo]), math.log10(grid[hi])
+    return [10.0 ** ((3.0 * ll + lr) / 4.0), 10.0 ** ((ll + lr) / 2.0), 10.0 ** ((ll + 3.0 * lr) / 4.0)]
+
+
+def grid_search_alpha(state, Z0, val_loader, full_set_size, model_type, num_mc_samples=30, scalable=True, log10_min=-3,
+                      log10_max=2, n_coarse=7, refine=True, rng_key=0, verbose=True, *, posterior: str = "inducing",
+                      link: str = "probit", alpha_base=None, seed: int = 0, indices=None, rank=None, curvature=None,
+                      route=None, return_history: bool = False):
+    """``src/grid_search.py:9-88``: the prior precision with the smallest validation NLL on a coarse log grid
+    ``logspace(log10_min, log10_max, n_coarse)`` (float64) followed, with ``refine``, by three points inside the bracket
+    around the coarse best (:func:`refinement_points`); the first minimum over coarse-then-refined values wins.
+
+    ``posterior="inducing"`` is the reference's search: every value goes through ``evaluate.eval_dataset`` (the MC
+    predictive of the inducing-point posterior, ``num_mc_samples`` / ``scalable``) with ``rng=rng_key``, which the
+    reference omits.  ``posterior="kfac"`` / ``"ekfac"``: two calls of ``evaluate.eval_dataset_closed_form_grid``, the
+    coarse grid and the refinement, so one fit and two passes over ``val_loader`` serve the whole search; every other
+    closed-form posterior of ``evaluate.eval_dataset_closed_form`` is evaluated value by value.  ``link`` / ``seed`` /
+    ``indices`` / ``rank`` / ``curvature`` / ``route`` go to the closed-form evaluation.
+
+    ``alpha_base=None``: the grid values are the precisions and a float comes back.  A :class:`prior.GroupedPrior`: the
+    grid values multiply it as a whole and the scaled ``GroupedPrior`` comes back.  ``return_history=True``:
+    ``(alpha, [(alpha, nll)])`` in evaluation order.  ``val_loader`` is walked once per evaluation, so it must be
+    re-iterable: a list of (x, y) batches or a ``DataLoader``, not a generator."""
+    from . import evaluate
+    grid = [float(a) for a in torch.logspace(float(log10_min), float(log10_max), int(n_coarse), dtype=torch.float64).tolist()]
+    base = 1.0 if alpha_base is None else alpha_base
+
+    def evaluate_values(values):
+        if posterior == "inducing":
+            return [evaluate.eval_dataset(state, val_loader, Z0, alpha=evaluate.scaled_prior(base, a),
+                                          full_set_size=full_set_size, model_type=model_type, num_mc_samples=num_mc_samples,
+                                          rng=rng_key, scalable=scalable)[0] for a in values]
+        res = evaluate.eval_dataset_closed_form_grid(state, val_loader, Z0, base, values, full_set_size, model_type, posterior,
+                                                     link, seed=seed, indices=indices, rank=rank, curvature=curvature,
+                                                     route=route)
+        return [r[0] for r in res]
+
+    def report(values, nlls):
+        if verbose:
+            for a, v in zip(values, nlls):
+                print(f"alpha={a:9.3e}  NLL={v:.4f}")
+
+    values = list(grid)
+    nlls = [float(v) for v in evaluate_values(grid)]
+    report(grid, nlls)
+    if refine:
+        best = min(range(len(grid)), key=lambda i: nlls[i])                   # the first minimum
+        fine = refinement_points(grid, best)
+        if verbose:
+            print("\n-- refinement pass --")
+        fine_nlls = [float(v) for v in evaluate_values(fine)]
+        report(fine, fine_nlls)
+        values += fine
+        nlls += fine_nlls
+    best = min(range(len(values)), key=lambda i: nlls[i])
+    if verbose:
+        print(f"\n>>> selected  alpha* = {values[best]:9.3e}  (val NLL = {nlls[best]:.4f})")
+    alpha = values[best] if alpha_base is None else evaluate.scaled_prior(alpha_base, values[best])
+    if return_history:
+        return alpha, [(a if alpha_base is None else evaluate.scaled_prior(alpha_base, a), v) for a, v in zip(values, nlls)]
+    return alpha
 
 
 # ---- layer-wise precisions ------------------------------------------------------------------------------------------
