@@ -69,8 +69,18 @@ enum {
      counted -- flax.linen.avg_pool, used by the reference's LeNet5 src/scalemodels.py:28,34) and its transpose */
   LIP_OP_MAXPOOL_PRIMAL = 9,  /* max pool of the primal activations + cached argmax (aux0)             */
   LIP_OP_MAXPOOL_FWD = 10,    /* tangent of max pool: gather at the cached argmax                      */
-  LIP_OP_MAXPOOL_BWD = 11     /* cotangent of max pool (gather over the covering windows), times dphi,
+  LIP_OP_MAXPOOL_BWD = 11,    /* cotangent of max pool (gather over the covering windows), times dphi,
                                  plus parameter reductions — same epilogue fields as LIP_OP_POOL_BWD   */
+  /* train tapes only (MAP training, below).  Both reuse fields of lip_op_t under the meaning given here:
+     BN_STATS     between a BN unit's IGEMM and its PRIMAL_POST: the batch statistics of z = seg[0].a ([R][N]) with the
+                  conv bias e0 (or NONE) and the BN scale e1, eps = bn_eps: aux0 <- mean, aux1 <- rsqrt(var + eps),
+                  scale <- s = gamma * rstd (CONST space, written through the binding's writable constants), and the
+                  running averages out (mean) / out2 (var) <- fscale * old + (1 - fscale) * batch, fscale the momentum
+     BN_TRAIN_BWD after the op that forms a BN unit's cotangent g = seg[0].a and its reductions: out <- g - (e0 + xhat * e1) / R
+                  with e0 = d beta, e1 = d gamma as reduced into YOUT; out is a tensor of its own (a residual consumer
+                  upstream keeps reading g)                                                           */
+  LIP_OP_BN_STATS = 12,
+  LIP_OP_BN_TRAIN_BWD = 13
 };
 
 /* head modes */
@@ -135,11 +145,12 @@ int lip_get_winograd(void);
  * Replaces the closure factories compute_ggn_vp / compute_W_vps (src/ggn.py:97,9): they
  * snapshot flat_params and Z at factory time; so does the engine (theta/consts/prim are
  * fixed until the next lip_engine_bind).                                                */
-enum { LIP_TAPE_PRIMAL = 0, LIP_TAPE_TANGENT = 1, LIP_TAPE_BACKWARD = 2 };
+enum { LIP_TAPE_PRIMAL = 0, LIP_TAPE_TANGENT = 1, LIP_TAPE_BACKWARD = 2,
+       LIP_TAPE_TRAIN_PRIMAL = 3, LIP_TAPE_TRAIN_BACKWARD = 4 };   /* the last two: MAP training only, optional */
 
 int lip_engine_create(lip_engine_t** out, int64_t D, int32_t n_img, int32_t K);
 int lip_engine_destroy(lip_engine_t* e);
-int lip_engine_set_tape(lip_engine_t* e, int32_t which, const lip_op_t* ops /*host*/, int32_t nops);
+int lip_engine_set_tape(lip_engine_t* e, int32_t which /*LIP_TAPE_*/, const lip_op_t* ops /*host*/, int32_t nops);
 int lip_engine_bind(lip_engine_t* e, const float* theta, const float* consts, float* prim,
                     float* work, int64_t work_floats_per_probe, int32_t max_probes_per_chunk);
 /* run the primal tape once (caches activations, BN-normalised values, act', softmax).   */
@@ -501,6 +512,60 @@ int lip_vjp_eigen_wnorm_scratch(lip_engine_t* e, int32_t P, int64_t* floats);
 int lip_vjp_eigen_wnorm(lip_engine_t* e, const float* U, const double* const* V, const double* const* Ub,
                         const float* const* Rw, const int32_t* Mt, int32_t nblocks, const float* w_rem, float* out, int32_t P,
                         int32_t head_mode, float c, float* scratch, int64_t scratch_floats, void* stream);
+/* ---- MAP training (replaces the jitted _map_step of src/train_map.py:52-88) ---------------------------------------------
+ * One step is a fixed number of calls whatever the depth: (load the batch into PRIM), lip_train_primal,
+ * lip_train_refresh, lip_train_loss_head, lip_train_backward, lip_train_adam.  The kernels are streaming passes over
+ * NHWC float32 without atomics: every sum runs in a fixed order, so equal inputs give equal bits.
+ *
+ * lip_engine_train_bind: the WRITABLE view of the constants of a bound engine (consts must be the pointer given to
+ * lip_engine_bind) and a float64 scratch of >= the largest lip_train_bn_stats_scratch(R, N) over the BN_STATS ops of the
+ * train primal tape (16-byte aligned; may be NULL for a net without BN).  Re-binding the engine drops it.
+ * lip_engine_set_refresh: the transposed kernels the backward tapes read, `count` rows of 6 int64 (host):
+ * (offset of W in THETA, offset of Wt in CONST, offset of s in CONST or -1, taps KH KW, Cin, Cout).
+ * lip_train_primal: the train primal tape (batch statistics instead of the constants' running ones; updates the running
+ * averages in CONST).  PRIM then holds train-mode activations: the sweeps of the other tapes refuse to run until the next
+ * lip_engine_primal.  lip_train_refresh: Wt[t][co][ci] = W[t][ci][co] * s[co] for every row of the table, from the
+ * current THETA and the s the train primal pass wrote.  lip_train_backward: Y (D,) = sum_i J_i^T U[i] through the train
+ * backward tape (Y is overwritten; U (n, K) are raw head cotangents), J the Jacobian of the train-mode network, the
+ * batch statistics differentiated through.  Status codes as lip_vjp; LIP_ERR_STATE without the train tapes, the
+ * writable constants or a train primal pass. */
+int lip_engine_train_bind(lip_engine_t* e, float* consts, double* scratch, int64_t scratch_doubles);
+int lip_engine_set_refresh(lip_engine_t* e, const int64_t* table /*host, count x 6*/, int32_t count);
+int lip_train_primal(lip_engine_t* e, void* stream);
+int lip_train_refresh(lip_engine_t* e, void* stream);
+int lip_train_backward(lip_engine_t* e, const float* U, float* Y, void* stream);
+/* The kernels on their own.
+ * lip_train_bn_stats: per channel c < N of z (R, N), with Flax BatchNorm's defaults: mean[c] = E[z] + bias[c],
+ * var[c] = E[(z - E z)^2] (biased), rstd[c] = rsqrt(var + eps), s[c] = gamma[c] * rstd[c] (float32 product; gamma NULL: 1),
+ * run_mean / run_var <- momentum * old + (1 - momentum) * (mean / var), in place.  Any output may be NULL.  The sums are
+ * float64 sums of d = z[r][c] - z[0][c] and d^2 over chunks of rows, folded in chunk order: no E[z^2] - E[z]^2 in
+ * float32.  scratch: >= lip_train_bn_stats_scratch(R, N) doubles, 16-byte aligned.  A null z / scratch, R or N <= 0,
+ * R N >= 2^31, a negative eps, a momentum outside [0, 1] or too small a scratch returns LIP_ERR_ARG, nothing written. */
+int lip_train_bn_stats_scratch(int32_t R, int32_t N, int64_t* doubles);
+int lip_train_bn_stats(const float* z, int32_t R, int32_t N, const float* bias, const float* gamma, float eps, float momentum,
+                       float* mean, float* var, float* rstd, float* s, float* run_mean, float* run_var, double* scratch,
+                       int64_t scratch_doubles, void* stream);
+/* out[r][c] = g[r][c] - (dbeta[c] + xhat[r][c] * dgamma[c]) / R; out must not be g. */
+int lip_train_bn_backward(const float* g, const float* xhat, const float* dbeta, const float* dgamma, int32_t R, int32_t N,
+                          float* out, void* stream);
+/* Wt[t][co][ci] = W[t][ci][co] * s[co], t < taps (s NULL: no scale): engine.build_consts' "wt" entries on the device. */
+int lip_train_wt_refresh(const float* W, const float* s, float* Wt, int32_t taps, int32_t cin, int32_t cout, void* stream);
+/* Loss head, one launch.  classifier != 0: outputs (n, K) logits, targets (n,) int64 labels; U (n, K) = (softmax - e_y) / n,
+ * out[0] = sum_i (logsumexp(f_i) - f_i[y_i]) in float64 (the caller divides by n), out[1] = 0; the log-sum-exp is taken
+ * about the row maximum, so logits of any finite size give finite results; a label outside [0, K) makes out[0] NaN.
+ * classifier == 0: outputs, targets (n, K) float32; U = (f - y) exp(-logvar) / (n K), out[0] = 0.5 sum (log(2 pi) + logvar
+ * + (f - y)^2 exp(-logvar)) (src/train_map.py:73-77 before its mean), out[1] = d(mean NLL)/d logvar.  out: 2 doubles. */
+int lip_train_loss_head(const float* outputs, const void* targets, int32_t n, int32_t K, int32_t classifier, float logvar, float* U,
+                        double* out, void* stream);
+/* One Adam step with the prior folded in (optax.adam, eps_root = 0), D entries, step t >= 1:
+ *   gt = g + a theta;  m = b1 m + (1 - b1) gt;  v = b2 v + (1 - b2) gt^2;
+ *   theta -= lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps)
+ * a: a (D,) precision vector, or NULL for the scalar a_scalar.  reg[0] = 0.5 sum a theta^2 of the theta BEFORE the step,
+ * float64.  One read and one write of theta, m, v; one read of g and a.  The five vectors must be 16-byte aligned.
+ * scratch: >= lip_train_adam_scratch(D) doubles. */
+int lip_train_adam_scratch(int64_t D, int64_t* doubles);
+int lip_train_adam(float* theta, float* m, float* v, const float* g, const float* a, float a_scalar, float lr, float b1, float b2,
+                   float eps, int64_t t, int64_t D, double* reg, double* scratch, int64_t scratch_doubles, void* stream);
 /* counter-based Rademacher (+-1) / standard-normal fill of a (P, N) block               */
 int lip_fill_rademacher(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);
 int lip_fill_normal(float* X, int32_t P, int64_t N, uint64_t seed, void* stream);

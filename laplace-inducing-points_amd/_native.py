@@ -17,8 +17,10 @@ LIP_OK = 0
 SP_NONE, SP_THETA, SP_CONST, SP_PRIM, SP_WORK, SP_VIN, SP_YOUT, SP_HEAD = -1, 0, 1, 2, 3, 4, 5, 6
 OP_IGEMM, OP_WGRAD, OP_REDUCE, OP_POOL_FWD, OP_POOL_BWD, OP_PRIMAL_POST, OP_SOFTMAX, OP_HEAD = 1, 2, 3, 4, 5, 6, 7, 8
 OP_MAXPOOL_PRIMAL, OP_MAXPOOL_FWD, OP_MAXPOOL_BWD = 9, 10, 11
+OP_BN_STATS, OP_BN_TRAIN_BWD = 12, 13                        # train tapes only
 HEAD_GGN, HEAD_LT, HEAD_L, HEAD_OUT, HEAD_IN = 0, 1, 2, 3, 4
 TAPE_PRIMAL, TAPE_TANGENT, TAPE_BACKWARD = 0, 1, 2
+TAPE_TRAIN_PRIMAL, TAPE_TRAIN_BACKWARD = 3, 4
 SEG_B_TRANS = 1
 
 
@@ -151,6 +153,20 @@ SIGNATURES = {
     "lip_evidence_terms_scratch": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
     "lip_evidence_terms": (C.c_int, [_V, C.c_int64, _V, _V, C.c_int32, _V, C.c_int64, C.c_int64, _V, _V, _V, C.c_int32,
                                      C.c_double, _V, _V, C.c_int64, _V]),
+    "lip_engine_train_bind": (C.c_int, [_V, _V, _V, C.c_int64]),
+    "lip_engine_set_refresh": (C.c_int, [_V, C.POINTER(C.c_int64), C.c_int32]),
+    "lip_train_primal": (C.c_int, [_V, _V]),
+    "lip_train_refresh": (C.c_int, [_V, _V]),
+    "lip_train_backward": (C.c_int, [_V, _V, _V, _V]),
+    "lip_train_bn_stats_scratch": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lip_train_bn_stats": (C.c_int, [_V, C.c_int32, C.c_int32, _V, _V, C.c_float, C.c_float, _V, _V, _V, _V, _V, _V, _V, C.c_int64,
+                                     _V]),
+    "lip_train_bn_backward": (C.c_int, [_V, _V, _V, _V, C.c_int32, C.c_int32, _V, _V]),
+    "lip_train_wt_refresh": (C.c_int, [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V]),
+    "lip_train_loss_head": (C.c_int, [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_float, _V, _V, _V]),
+    "lip_train_adam_scratch": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "lip_train_adam": (C.c_int, [_V, _V, _V, _V, _V, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int64,
+                                 _V, _V, C.c_int64, _V]),
     "lip_fill_rademacher": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_fill_normal": (C.c_int, [_V, C.c_int32, C.c_int64, C.c_uint64, _V]),
     "lip_head_sample": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _V, _V, _V]),

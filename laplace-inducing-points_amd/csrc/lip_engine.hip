@@ -31,9 +31,17 @@ using namespace lip;
 struct lip_engine {
   int64_t D = 0;
   int32_t n_img = 0, K = 0;
-  std::vector<lip_op_t> tape[3];
+  std::vector<lip_op_t> tape[5];         // LIP_TAPE_*: primal, tangent, backward; train primal, train backward
   const float* theta = nullptr;
   const float* consts = nullptr;
+  // MAP training (lip_engine_train_bind / lip_engine_set_refresh): the writable view of consts, the float64 scratch of the
+  // batch statistics, the table of transposed kernels, and whether PRIM holds a train primal pass
+  float* consts_rw = nullptr;
+  double* train_scratch = nullptr;
+  int64_t train_scratch_doubles = 0;
+  struct Refresh { int64_t w_off, wt_off, s_off; int taps, cin, cout; };
+  std::vector<Refresh> refresh;
+  bool train_primal_done = false;
   float* prim = nullptr;
   float* work = nullptr;
   int64_t work_pp = 0;      // workspace floats per probe
@@ -538,6 +546,38 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       RUN_CHECK(launch_softmax(in, pr, sq, op.n_img, op.N, c.st), "softmax launch");
       return LIP_OK;
     }
+    case LIP_OP_BN_STATS: {
+      if (!c.e->consts_rw) { set_error("BN_STATS: the binding has no writable constants (lip_engine_train_bind)"); return LIP_ERR_STATE; }
+      for (const lip_ref_t* r : {&op.aux0, &op.aux1, &op.scale, &op.out, &op.out2})
+        if (r->space != LIP_SP_CONST) { set_error("BN_STATS: statistics must live in the CONST space"); return LIP_ERR_ARG; }
+      BnStatsP p;
+      p.z = resolve(c, op.seg[0].a); p.R = op.n_img * op.OH * op.OW; p.N = op.N;
+      p.bias = resolve(c, op.e0); p.gamma = resolve(c, op.e1);
+      p.eps = op.bn_eps; p.momentum = op.fscale;
+      p.mean = resolve(c, op.aux0); p.var = nullptr; p.rstd = resolve(c, op.aux1); p.s = resolve(c, op.scale);
+      p.run_mean = resolve(c, op.out); p.run_var = resolve(c, op.out2);
+      p.scratch = c.e->train_scratch;
+      if (!p.z || !p.gamma || op.n_img <= 0 || op.OH <= 0 || op.OW <= 0 || p.N <= 0 || (long long)op.n_img * op.OH * op.OW * p.N >= (1ll << 31) ||
+          !(p.eps >= 0.f) || !(p.momentum >= 0.f && p.momentum <= 1.f)) { set_error("BN_STATS: bad operands"); return LIP_ERR_ARG; }
+      if (!p.scratch || bn_stats_scratch(p.R, p.N) > c.e->train_scratch_doubles) { set_error("BN_STATS: statistics scratch too small"); return LIP_ERR_ARG; }
+      RUN_CHECK(launch_bn_stats(p, c.st), "bn_stats launch");
+      return LIP_OK;
+    }
+    case LIP_OP_BN_TRAIN_BWD: {
+      BnTrainBwdP p;
+      p.g = resolve(c, op.seg[0].a); p.g_ps = op.seg[0].a.pstride;
+      p.xhat = resolve(c, op.xhat);
+      p.dbeta = resolve(c, op.e0); p.dgamma = resolve(c, op.e1); p.d_ps = op.e0.pstride;
+      p.out = resolve(c, op.out); p.out_ps = op.out.pstride;
+      p.R = op.n_img * op.OH * op.OW; p.N = op.N;
+      if (!p.g || !p.xhat || !p.dbeta || !p.dgamma || !p.out || p.out == p.g || op.n_img <= 0 || op.OH <= 0 || op.OW <= 0 || p.N <= 0 ||
+          (long long)op.n_img * op.OH * op.OW * p.N >= (1ll << 31) || op.e1.pstride != op.e0.pstride || c.per_example()) {
+        set_error("BN_TRAIN_BWD: bad operands");
+        return LIP_ERR_ARG;
+      }
+      RUN_CHECK(launch_bn_train_bwd(p, c.P, c.st), "bn_train_bwd launch");
+      return LIP_OK;
+    }
     case LIP_OP_HEAD: {
       HeadP p;
       memset(&p, 0, sizeof(p));
@@ -773,7 +813,7 @@ int lip_engine_destroy(lip_engine_t* e) {
 }
 
 int lip_engine_set_tape(lip_engine_t* e, int32_t which, const lip_op_t* ops, int32_t nops) {
-  if (!e || which < 0 || which > 2 || !ops || nops <= 0) { set_error("lip_engine_set_tape: bad argument"); return LIP_ERR_ARG; }
+  if (!e || which < 0 || which > LIP_TAPE_TRAIN_BACKWARD || !ops || nops <= 0) { set_error("lip_engine_set_tape: bad argument"); return LIP_ERR_ARG; }
   e->tape[which].assign(ops, ops + nops);
   if (which == LIP_TAPE_BACKWARD) {
     e->kron_off.assign(nops, 0);
@@ -787,6 +827,7 @@ int lip_engine_set_tape(lip_engine_t* e, int32_t which, const lip_op_t* ops, int
     }
   }
   if (which == LIP_TAPE_PRIMAL) e->primal_done = false;
+  if (which == LIP_TAPE_TRAIN_PRIMAL) e->train_primal_done = false;
   return LIP_OK;
 }
 
@@ -802,6 +843,8 @@ int lip_engine_bind(lip_engine_t* e, const float* theta, const float* consts, fl
   }
   // re-binding only a (grown) workspace keeps the cached primal pass valid
   if (e->theta != theta || e->consts != consts || e->prim != prim) e->primal_done = false;
+  e->train_primal_done = false;
+  e->consts_rw = nullptr; e->train_scratch = nullptr; e->train_scratch_doubles = 0;
   if (e->cache) e->cache->release();
   e->theta = theta; e->consts = consts; e->prim = prim; e->work = work;
   e->work_pp = work_floats_per_probe; e->max_chunk = max_probes_per_chunk;
@@ -816,7 +859,74 @@ int lip_engine_primal(lip_engine_t* e, void* stream) {
   const int rc = run_tape(RunCtx{e, nullptr, nullptr, nullptr, 1, 0, 1.f, (hipStream_t)stream}, LIP_TAPE_PRIMAL, false);
   if (e->cache) e->cache->invalidate();
   if (rc == LIP_OK) e->primal_done = true;
+  e->train_primal_done = false;          // PRIM holds eval-mode activations again
   return rc;
+}
+
+int lip_engine_train_bind(lip_engine_t* e, float* consts, double* scratch, int64_t scratch_doubles) {
+  if (!e || !consts || scratch_doubles < 0 || (scratch_doubles > 0 && !scratch) || (((uintptr_t)scratch) & 15)) {
+    set_error("lip_engine_train_bind: bad argument");
+    return LIP_ERR_ARG;
+  }
+  if (!e->theta || !e->prim || e->consts != consts) { set_error("lip_engine_train_bind: consts is not the bound constants buffer"); return LIP_ERR_STATE; }
+  e->consts_rw = consts; e->train_scratch = scratch; e->train_scratch_doubles = scratch_doubles;
+  return LIP_OK;
+}
+
+int lip_engine_set_refresh(lip_engine_t* e, const int64_t* table, int32_t count) {
+  if (!e || count < 0 || (count > 0 && !table)) { set_error("lip_engine_set_refresh: bad argument"); return LIP_ERR_ARG; }
+  std::vector<lip_engine::Refresh> rows;
+  for (int i = 0; i < count; ++i) {
+    const int64_t* r = table + 6 * (int64_t)i;
+    if (r[0] < 0 || r[1] < 0 || r[2] < -1 || r[3] <= 0 || r[3] > 65535 || r[4] <= 0 || r[5] <= 0 || r[4] >= (1ll << 31) || (r[5] + 31) / 32 > 65535 ||
+        r[0] + r[3] * r[4] * r[5] > e->D) {
+      set_error("lip_engine_set_refresh: bad row %d", i);
+      return LIP_ERR_ARG;
+    }
+    rows.push_back({r[0], r[1], r[2], (int)r[3], (int)r[4], (int)r[5]});
+  }
+  e->refresh.swap(rows);
+  return LIP_OK;
+}
+
+// the engine is bound for training: the train tapes, the writable constants
+static int ready_train(const lip_engine* e, const char* who, bool args_ok) {
+  if (!e) { set_error("%s: null engine", who); return LIP_ERR_ARG; }
+  if (!e->theta || !e->prim || !e->work || e->max_chunk <= 0) { set_error("%s: engine not bound", who); return LIP_ERR_STATE; }
+  if (!e->consts_rw) { set_error("%s: no writable constants (lip_engine_train_bind)", who); return LIP_ERR_STATE; }
+  if (e->tape[LIP_TAPE_TRAIN_PRIMAL].empty() || e->tape[LIP_TAPE_TRAIN_BACKWARD].empty()) { set_error("%s: train tapes missing", who); return LIP_ERR_STATE; }
+  if (!args_ok) { set_error("%s: bad argument", who); return LIP_ERR_ARG; }
+  return LIP_OK;
+}
+
+int lip_train_primal(lip_engine_t* e, void* stream) {
+  int rc = ready_train(e, "lip_train_primal", true);
+  if (rc) return rc;
+  // THETA may have changed in place and PRIM is rewritten: as in lip_engine_primal, whatever the cache holds is stale
+  e->primal_done = false; e->train_primal_done = false;
+  if (e->cache) e->cache->invalidate();
+  rc = run_tape(RunCtx{e, nullptr, nullptr, nullptr, 1, 0, 1.f, (hipStream_t)stream}, LIP_TAPE_TRAIN_PRIMAL, false);
+  if (e->cache) e->cache->invalidate();
+  if (rc == LIP_OK) e->train_primal_done = true;
+  return rc;
+}
+
+int lip_train_refresh(lip_engine_t* e, void* stream) {
+  const int rc = ready_train(e, "lip_train_refresh", true);
+  if (rc) return rc;
+  if (e->cache) e->cache->invalidate();       // the transformed copies of the transposed kernels are stale
+  for (const lip_engine::Refresh& r : e->refresh)
+    RUN_CHECK(launch_wt_refresh(e->theta + r.w_off, r.s_off >= 0 ? e->consts_rw + r.s_off : nullptr, e->consts_rw + r.wt_off, r.taps, r.cin,
+                                r.cout, (hipStream_t)stream), "wt_refresh launch");
+  return LIP_OK;
+}
+
+int lip_train_backward(lip_engine_t* e, const float* U, float* Y, void* stream) {
+  int rc = ready_train(e, "lip_train_backward", U && Y);
+  if (rc) return rc;
+  if (!e->train_primal_done) { set_error("lip_train_backward: train primal pass not run"); return LIP_ERR_STATE; }
+  RUN_CHECK(hipMemsetAsync(Y, 0, sizeof(float) * (size_t)e->D, (hipStream_t)stream), "memset Y");
+  return run_tape(RunCtx{e, nullptr, Y, const_cast<float*>(U), 1, LIP_HEAD_IN, 1.f, (hipStream_t)stream}, LIP_TAPE_TRAIN_BACKWARD, false);
 }
 
 int lip_engine_profile(lip_engine_t* e, int32_t enable) {
@@ -852,7 +962,7 @@ int lip_engine_run_op(lip_engine_t* e, const lip_op_t* op, const float* V, float
 
 int lip_debug_run_ops(lip_engine_t* e, int32_t which, int32_t first, int32_t count, const float* V, float* Y,
                       float* H, int32_t P, int32_t head_mode, float head_c, void* stream) {
-  if (!e || which < 0 || which > 2 || P <= 0 || P > e->max_chunk) { set_error("lip_debug_run_ops: bad argument"); return LIP_ERR_ARG; }
+  if (!e || which < 0 || which > LIP_TAPE_TRAIN_BACKWARD || P <= 0 || P > e->max_chunk) { set_error("lip_debug_run_ops: bad argument"); return LIP_ERR_ARG; }
   const std::vector<lip_op_t>& t = e->tape[which];
   if (first < 0 || count < 0 || (size_t)(first + count) > t.size()) { set_error("lip_debug_run_ops: bad op range"); return LIP_ERR_ARG; }
   const RunCtx c{e, V, Y, H, P, head_mode, head_c, (hipStream_t)stream};

@@ -138,6 +138,24 @@ struct HeadP {
   int n, K, mode, classifier; float c;
 };
 
+// ---- MAP training (lip_train.hip) ---------------------------------------------------------------------------------------
+struct BnStatsP {
+  const float* z; int R, N;             // raw conv output [R][N]
+  const float* bias; const float* gamma;                 // conv bias / BN scale (THETA) or null
+  float eps, momentum;
+  float* mean; float* var; float* rstd; float* s;        // per channel; any may be null
+  float* run_mean; float* run_var;      // running averages, updated in place; or null
+  double* scratch;                      // >= bn_stats_scratch(R, N) doubles, 16-byte aligned
+};
+
+struct BnTrainBwdP {
+  const float* g; long long g_ps;       // cotangent of the BN output [P][R][N]
+  const float* xhat;                    // [R][N] primal
+  const float* dbeta; const float* dgamma; long long d_ps;   // the reduced BN cotangents, per probe
+  float* out; long long out_ps;         // corrected cotangent [P][R][N], not g
+  int R, N;
+};
+
 // ---- code path of the non-GEMM kernels that pick one from the channel count and the pointer alignment ----------
 // One predicate per kernel, used by the kernel (per block, on the block's own pointers) and by its launcher (per probe,
 // for the route census), so a census label cannot drift from the branch that ran.
@@ -184,6 +202,12 @@ hipError_t launch_maxpool_fwd(const MaxPoolP& p, int P, hipStream_t st);
 hipError_t launch_maxpool_bwd(const MaxPoolP& p, int P, hipStream_t st);
 hipError_t launch_softmax(const float* logits, float* prob, float* sqrtp, int n, int K, hipStream_t st);
 hipError_t launch_head(const HeadP& p, int P, hipStream_t st);
+// MAP training: batch statistics of a BN unit (two launches: chunk partials, fold), the train-mode correction of its
+// cotangent, and one transposed, BN-scaled kernel Wt[t][co][ci] = W[t][ci][co] s[co] (s null: no scale)
+long long bn_stats_scratch(int R, int N);
+hipError_t launch_bn_stats(const BnStatsP& p, hipStream_t st);
+hipError_t launch_bn_train_bwd(const BnTrainBwdP& p, int P, hipStream_t st);
+hipError_t launch_wt_refresh(const float* W, const float* s, float* Wt, int taps, int cin, int cout, hipStream_t st);
 hipError_t launch_gemm_nt(const float* A, long long lda, int m, const float* B, long long ldb, int n, long long K, float* C,
                           hipStream_t st);
 hipError_t launch_gemm_nn_axpy(const float* T, long long ldt, int m, int k, const float* B, long long ldb, long long N,

@@ -72,6 +72,8 @@ class CompiledNet:
     prob_off: int
     input_off: int
     meta: Dict[str, Any] = dataclasses.field(default_factory=dict)   # per-tensor offsets the second-order pass needs
+    train_tapes: List[List[nv.Op]] = dataclasses.field(default_factory=list)   # compile_net(train=True): [primal, backward]
+    train_work_pp: int = 0            # workspace floats of the train backward tape (one probe: the minibatch)
 
     def last_unit(self) -> Unit:
         """the final unit, a plain Dense (:func:`last_dense_unit`)"""
@@ -162,7 +164,14 @@ def _seg(a, b, IH, IW, Cc, KH, KW, stride, pad_h, pad_w, mode):
     return dict(a=a, b=b, IH=IH, IW=IW, C=Cc, KH=KH, KW=KW, stride=stride, pad_h=pad_h, pad_w=pad_w, mode=mode)
 
 
-def compile_net(net: NetSpec, n: int, params: Dict[str, Any]) -> CompiledNet:
+BN_MOMENTUM = 0.99       # flax.linen.BatchNorm's default: running = momentum * running + (1 - momentum) * batch
+
+
+def compile_net(net: NetSpec, n: int, params: Dict[str, Any], train: bool = False) -> CompiledNet:
+    """The three tapes of a binding of ``n`` examples.  ``train=True`` adds the two train tapes of MAP training
+    (``CompiledNet.train_tapes``: primal with batch statistics, backward through them), slots for the running statistics
+    at the END of the constants (the offsets of everything else, and the three tapes, are those of ``train=False``) and
+    the workspace the train backward tape needs (``train_work_pp``)."""
     layout = {path: (off, shape) for path, off, shape in param_layout(params)}
     D = sum(int(torch.Size(s).numel()) for _, s in layout.values())
     K = net.num_outputs
@@ -235,6 +244,12 @@ def compile_net(net: NetSpec, n: int, params: Dict[str, Any]) -> CompiledNet:
             wt_off[u.dst] = calloc(u.kh * u.kw * u.cout * u.cin)
             const_plan.append(("wt", u, wt_off[u.dst], s_off.get(u.dst)))
     cst = max(cst, 4)
+    run_off: Dict[int, Tuple[int, int]] = {}
+    if train:
+        for u in net.units:
+            if u.kind == "conv" and u.bn_scale is not None:
+                run_off[u.dst] = (calloc(u.cout), calloc(u.cout))
+                const_plan.append(("run", u, run_off[u.dst][0], run_off[u.dst][1]))
 
     P = lambda off: (nv.SP_PRIM, off, 0)
     TH = lambda off: (nv.SP_THETA, off, 0)
@@ -291,6 +306,25 @@ def compile_net(net: NetSpec, n: int, params: Dict[str, Any]) -> CompiledNet:
         primal.append(SymOp(nv.OP_SOFTMAX, dict(n_img=n, OH=1, OW=1, N=K),
                             dict(out=P(prob_off), out2=P(sqrtp_off)), [dict(a=P(a_off[net.out]), b=NONE)]))
 
+    # the train primal tape: the same ops without the SOFTMAX (the loss head takes the logits), and BN_STATS between a
+    # BN unit's IGEMM and its PRIMAL_POST, which then normalises with the batch statistics BN_STATS left in CONST
+    train_primal: List[SymOp] = []
+    if train:
+        conv_at = {a_off[u.dst]: u for u in net.units if u.kind == "conv"}
+        for op in primal:
+            if op.kind == nv.OP_SOFTMAX:
+                continue
+            if op.kind == nv.OP_PRIMAL_POST and "e1" in op.refs:
+                u = conv_at[op.refs["out"][1]]
+                refs = dict(e1=op.refs["e1"], aux0=op.refs["aux0"], aux1=op.refs["aux1"], scale=CS(s_off[u.dst]),
+                            out=CS(run_off[u.dst][0]), out2=CS(run_off[u.dst][1]))
+                if "e0" in op.refs:
+                    refs["e0"] = op.refs["e0"]
+                train_primal.append(SymOp(nv.OP_BN_STATS, dict(n_img=n, OH=op.f["OH"], OW=op.f["OW"], N=op.f["N"],
+                                                               bn_eps=float(u.bn_eps), fscale=BN_MOMENTUM), refs,
+                                          [dict(a=P(z_off), b=NONE)]))
+            train_primal.append(op)
+
     # ------------------------------------------------------------------ tangent tape
     def tsize(t):
         h, w, c = tens[t]
@@ -346,102 +380,125 @@ def compile_net(net: NetSpec, n: int, params: Dict[str, Any]) -> CompiledNet:
                          dict(head_refs), [dict(a=W(da[net.out]), b=NONE)]))
 
     # ------------------------------------------------------------------ backward tape
-    backward: List[SymOp] = []
-    # head input lives in HEAD space (vjp calls); its seg a is unused in modes L / IN
-    backward.append(SymOp(nv.OP_HEAD, dict(n_img=n, OH=1, OW=1, N=K, classifier=int(classifier)),
-                          dict(head_refs), [dict(a=W(g_head), b=NONE)]))
     consumers: Dict[int, List[Tuple[Unit, str]]] = {}
     for u in net.units:
         consumers.setdefault(u.src, []).append((u, "src"))
         if u.res is not None:
             consumers.setdefault(u.res, []).append((u, "res"))
-    gp: Dict[int, VT] = {net.out: g_head}
 
-    def param_reds(u: Unit) -> Dict[str, Any]:
-        """reductions into the bias / BN cotangents of the unit that produced the tensor"""
-        r: Dict[str, Any] = {}
-        if u.kind != "conv":
+    def build_backward(train: bool) -> List[SymOp]:
+        """the backward tape; ``train``: every BN unit's cotangent g is followed by BN_TRAIN_BWD, whose corrected copy g'
+        feeds the unit's WGRAD and the data-gradient segments through its kernel, while a residual consumer upstream
+        keeps reading g (for y = BN(z) + res, d/d res is g, not g')"""
+        backward: List[SymOp] = []
+        # head input lives in HEAD space (vjp calls); its seg a is unused in modes L / IN
+        backward.append(SymOp(nv.OP_HEAD, dict(n_img=n, OH=1, OW=1, N=K, classifier=int(classifier)),
+                              dict(head_refs), [dict(a=W(g_head), b=NONE)]))
+        gp: Dict[int, VT] = {net.out: g_head}
+        gq: Dict[int, VT] = {}            # train: the corrected cotangent g' of a BN unit's output
+
+        def through_kernel(t: int) -> VT:
+            """the cotangent that goes through the kernel of the unit producing t (its WGRAD, its data gradient)"""
+            return gq.get(t, gp[t])
+
+        def bn_correction(u: Unit, t: int) -> None:
+            if not (train and u.kind == "conv" and u.bn_scale is not None):
+                return
+            h, w, c = tens[t]
+            gq[t] = VT(tsize(t), f"gq{t}")
+            backward.append(SymOp(nv.OP_BN_TRAIN_BWD, dict(n_img=n, OH=h, OW=w, N=c),
+                                  dict(out=W(gq[t]), e0=YO(poff(u.bn_bias)), e1=YO(poff(u.bn_scale)), xhat=P(xhat_off[t])),
+                                  [dict(a=W(gp[t]), b=NONE)]))
+
+        def param_reds(u: Unit) -> Dict[str, Any]:
+            """reductions into the bias / BN cotangents of the unit that produced the tensor"""
+            r: Dict[str, Any] = {}
+            if u.kind != "conv":
+                return r
+            if u.bn_scale is not None:
+                r["red0"] = YO(poff(u.bn_bias))
+                r["red1"] = YO(poff(u.bn_scale))
+                r["xhat2"] = P(xhat_off[u.dst])
+            elif u.bias is not None:
+                r["red0"] = YO(poff(u.bias))
             return r
-        if u.bn_scale is not None:
-            r["red0"] = YO(poff(u.bn_bias))
-            r["red1"] = YO(poff(u.bn_scale))
-            r["xhat2"] = P(xhat_off[u.dst])
-        elif u.bias is not None:
-            r["red0"] = YO(poff(u.bias))
-        return r
 
-    order = [u.dst for u in net.units if u.kind != "view"]
-    for t in reversed(order):
-        u = producer[t]
-        if not _has_grad(net, t):
-            continue
-        h, w, c = tens[t]
-        if t != net.out:
-            cons = consumers.get(t, [])
-            conv_c = [cu for cu, role in cons if role == "src" and cu.kind == "conv"]
-            res_c = [cu for cu, role in cons if role == "res"]
-            pool_c = [cu for cu, role in cons if role == "src" and cu.kind == "meanpool"]
-            mpool_c = [cu for cu, role in cons if role == "src" and cu.kind in ("maxpool", "avgpool")]
-            view_c = [cu for cu, role in cons if cu.kind == "view"]
-            if view_c:
-                raise NotImplementedError("flatten of a non-input tensor is not supported by the HIP engine yet")
-            if len(res_c) > 1 or len(conv_c) > 3 or ((pool_c or mpool_c) and (conv_c or res_c)) or len(mpool_c) > 1:
-                raise NotImplementedError(f"unsupported fan-out at tensor {t}")
-            reds = param_reds(u)
-            if mpool_c:
-                mu = mpool_c[0]
-                moh, mow, _ = tens[mu.dst]
-                out = VT(tsize(t), f"g{t}")
-                refs = dict(out=W(out), aux0=AMAX(mu.dst), **reds)
-                if t in dphi_off:
-                    refs["dphi"] = P(dphi_off[t])
-                backward.append(SymOp(nv.OP_MAXPOOL_BWD, dict(n_img=n, OH=moh, OW=mow, N=c), refs,
-                                      [pool_seg(mu, W(gp[mu.dst]))]))
-                gp[t] = out
-            elif pool_c:
-                pu = pool_c[0]
-                out = VT(tsize(t), f"g{t}")
-                refs = dict(out=W(out), **reds)
-                if t in dphi_off:
-                    refs["dphi"] = P(dphi_off[t])
-                backward.append(SymOp(nv.OP_POOL_BWD, dict(n_img=n, OH=h, OW=w, N=c, fscale=1.0 / (h * w)), refs,
-                                      [dict(a=W(gp[pu.dst]), b=NONE)]))
-                gp[t] = out
-            elif not conv_c:
-                # only a residual consumer and no activation of its own: the cotangent is an alias
-                if t in dphi_off:
-                    raise NotImplementedError("activated tensor consumed only as a residual")
-                gp[t] = gp[res_c[0].dst]
+        order = [u.dst for u in net.units if u.kind != "view"]
+        for t in reversed(order):
+            u = producer[t]
+            if not _has_grad(net, t):
+                continue
+            h, w, c = tens[t]
+            if t != net.out:
+                cons = consumers.get(t, [])
+                conv_c = [cu for cu, role in cons if role == "src" and cu.kind == "conv"]
+                res_c = [cu for cu, role in cons if role == "res"]
+                pool_c = [cu for cu, role in cons if role == "src" and cu.kind == "meanpool"]
+                mpool_c = [cu for cu, role in cons if role == "src" and cu.kind in ("maxpool", "avgpool")]
+                view_c = [cu for cu, role in cons if cu.kind == "view"]
+                if view_c:
+                    raise NotImplementedError("flatten of a non-input tensor is not supported by the HIP engine yet")
+                if len(res_c) > 1 or len(conv_c) > 3 or ((pool_c or mpool_c) and (conv_c or res_c)) or len(mpool_c) > 1:
+                    raise NotImplementedError(f"unsupported fan-out at tensor {t}")
+                reds = param_reds(u)
+                if mpool_c:
+                    mu = mpool_c[0]
+                    moh, mow, _ = tens[mu.dst]
+                    out = VT(tsize(t), f"g{t}")
+                    refs = dict(out=W(out), aux0=AMAX(mu.dst), **reds)
+                    if t in dphi_off:
+                        refs["dphi"] = P(dphi_off[t])
+                    backward.append(SymOp(nv.OP_MAXPOOL_BWD, dict(n_img=n, OH=moh, OW=mow, N=c), refs,
+                                          [pool_seg(mu, W(gp[mu.dst]))]))
+                    gp[t] = out
+                elif pool_c:
+                    pu = pool_c[0]
+                    out = VT(tsize(t), f"g{t}")
+                    refs = dict(out=W(out), **reds)
+                    if t in dphi_off:
+                        refs["dphi"] = P(dphi_off[t])
+                    backward.append(SymOp(nv.OP_POOL_BWD, dict(n_img=n, OH=h, OW=w, N=c, fscale=1.0 / (h * w)), refs,
+                                          [dict(a=W(gp[pu.dst]), b=NONE)]))
+                    gp[t] = out
+                elif not conv_c:
+                    # only a residual consumer and no activation of its own: the cotangent is an alias
+                    if t in dphi_off:
+                        raise NotImplementedError("activated tensor consumed only as a residual")
+                    gp[t] = gp[res_c[0].dst]
+                    if reds:
+                        backward.append(SymOp(nv.OP_REDUCE, dict(n_img=n, OH=h, OW=w, N=c), dict(reds),
+                                              [dict(a=W(gp[t]), b=NONE)]))
+                else:
+                    out = VT(tsize(t), f"g{t}")
+                    segs = []
+                    for cu in conv_c:
+                        coh, cow, cc = tens[cu.dst]
+                        segs.append(_seg(W(through_kernel(cu.dst)), CS(wt_off[cu.dst]), coh, cow, cu.cout, cu.kh, cu.kw, cu.stride,
+                                         cu.pad_h, cu.pad_w, 1))
+                    refs = dict(out=W(out), **reds)
+                    if res_c:
+                        refs["res"] = W(gp[res_c[0].dst])
+                    if t in dphi_off:
+                        refs["dphi"] = P(dphi_off[t])
+                    backward.append(SymOp(nv.OP_IGEMM, dict(n_img=n, OH=h, OW=w, N=c), refs, segs))
+                    gp[t] = out
+            else:
+                reds = param_reds(u)
                 if reds:
                     backward.append(SymOp(nv.OP_REDUCE, dict(n_img=n, OH=h, OW=w, N=c), dict(reds),
                                           [dict(a=W(gp[t]), b=NONE)]))
-            else:
-                out = VT(tsize(t), f"g{t}")
-                segs = []
-                for cu in conv_c:
-                    coh, cow, cc = tens[cu.dst]
-                    segs.append(_seg(W(gp[cu.dst]), CS(wt_off[cu.dst]), coh, cow, cu.cout, cu.kh, cu.kw, cu.stride,
-                                     cu.pad_h, cu.pad_w, 1))
-                refs = dict(out=W(out), **reds)
-                if res_c:
-                    refs["res"] = W(gp[res_c[0].dst])
-                if t in dphi_off:
-                    refs["dphi"] = P(dphi_off[t])
-                backward.append(SymOp(nv.OP_IGEMM, dict(n_img=n, OH=h, OW=w, N=c), refs, segs))
-                gp[t] = out
-        else:
-            reds = param_reds(u)
-            if reds:
-                backward.append(SymOp(nv.OP_REDUCE, dict(n_img=n, OH=h, OW=w, N=c), dict(reds),
-                                      [dict(a=W(gp[t]), b=NONE)]))
-        if u.kind == "conv":
-            g = geom(u)
-            refs = dict(out=YO(poff(u.kernel)))
-            if u.bn_scale is not None:
-                refs["scale"] = CS(s_off[u.dst])
-            backward.append(SymOp(nv.OP_WGRAD, dict(n_img=n, OH=h, OW=w, N=c, ksplit=0, M=u.kh * u.kw * u.cin), refs,
-                                  [_seg(P(a_off[u.src]), W(gp[t]), g["IH"], g["IW"], g["Cc"], g["KH"], g["KW"],
-                                        g["stride"], g["pad_h"], g["pad_w"], 0)]))
+            bn_correction(u, t)
+            if u.kind == "conv":
+                g = geom(u)
+                refs = dict(out=YO(poff(u.kernel)))
+                if u.bn_scale is not None:
+                    refs["scale"] = CS(s_off[u.dst])
+                backward.append(SymOp(nv.OP_WGRAD, dict(n_img=n, OH=h, OW=w, N=c, ksplit=0, M=u.kh * u.kw * u.cin), refs,
+                                      [_seg(P(a_off[u.src]), W(through_kernel(t)), g["IH"], g["IW"], g["Cc"], g["KH"], g["KW"],
+                                            g["stride"], g["pad_h"], g["pad_w"], 0)]))
+        return backward
+
+    backward = build_backward(False)
 
     # ------------------------------------------------------------------ workspace placement
     work_pp = 0
@@ -449,11 +506,18 @@ def compile_net(net: NetSpec, n: int, params: Dict[str, Any]) -> CompiledNet:
         work_pp = max(work_pp, _place(tape, g_head))
 
     tapes = [[_lower(op) for op in tape] for tape in (primal, tangent, backward)]
+    train_tapes: List[List[nv.Op]] = []
+    train_work_pp = 0
+    if train:
+        train_backward = build_backward(True)
+        train_work_pp = _place(train_backward, g_head)
+        train_tapes = [[_lower(op) for op in tape] for tape in (train_primal, train_backward)]
     return CompiledNet(net=net, n=n, D=D, K=K, classifier=classifier, offsets=layout, prim_floats=max(prim, 4),
                        const_floats=cst, work_pp=work_pp, tapes=tapes, a_off=a_off, const_plan=const_plan,
                        prob_off=prob_off, input_off=a_off[0],
                        meta=dict(dphi_off=dphi_off, xhat_off=xhat_off, s_off=s_off, rstd_off=rstd_off, wt_off=wt_off, amax_off=amax_off,
-                                 sqrtp_off=sqrtp_off, layout=layout))
+                                 sqrtp_off=sqrtp_off, layout=layout, mean_off=mean_off, run_off=run_off),
+                       train_tapes=train_tapes, train_work_pp=train_work_pp)
 
 
 def _has_grad(net: NetSpec, t: int) -> bool:
@@ -548,6 +612,10 @@ def build_consts(cn: CompiledNet, params: Dict[str, Any], batch_stats: Dict[str,
             out[so:so + u.cout] = s
             out[mo:mo + u.cout] = mean
             out[ro:ro + u.cout] = rstd
+        elif item[0] == "run":
+            _, u, mo, vo = item
+            out[mo:mo + u.cout] = _get(batch_stats, u.bn_mean).to(device=device, dtype=dtype)
+            out[vo:vo + u.cout] = _get(batch_stats, u.bn_var).to(device=device, dtype=dtype)
     for item in cn.const_plan:
         if item[0] == "wt":
             _, u, wo, so = item

@@ -260,12 +260,16 @@ class NetSpec:
 
     # ---------------------------------------------------------------- forward
     def forward(self, params: Dict[str, Any], batch_stats: Dict[str, Any], x: torch.Tensor,
-                return_all: bool = False):
+                return_all: bool = False, train: bool = False, momentum: float = 0.99):
         """Torch functional forward, any dtype/device, differentiable in ``params``.
 
         ``x`` is one example (``input_shape``) or a batch ``(B, *input_shape)``;
         returns ``(K,)`` or ``(B, K)``.  ``params`` is the tree containing
         ``param_root`` (e.g. ``{'params': {...}}``).
+
+        ``train=True``: BatchNorm normalises with the statistics of the batch (Flax defaults: biased variance) and the
+        call returns ``(out, new_batch_stats)``, the running statistics moved by ``momentum`` towards the batch's
+        (detached; both running mean and running var take the biased batch variance).
         """
         raw = self.input_shape_raw
         if tuple(x.shape) == raw:
@@ -275,6 +279,7 @@ class NetSpec:
             single = False
             xb = self.prepare_input(x)
         vals: Dict[int, torch.Tensor] = {0: xb}
+        new_stats: Dict[str, Any] = {}
         for u in self.units:
             a = vals[u.src]
             if u.kind == "view":
@@ -317,11 +322,22 @@ class NetSpec:
                 z = z + _get(params, u.bias)
             if u.bn_scale is not None:
                 mean, var = _get(batch_stats, u.bn_mean), _get(batch_stats, u.bn_var)
+                if train:
+                    run_mean, run_var = mean, var
+                    mean = z.mean(dim=(0, 1, 2))
+                    var = ((z - mean) ** 2).mean(dim=(0, 1, 2))
+                    for path, run, batch in ((u.bn_mean, run_mean, mean), (u.bn_var, run_var, var)):
+                        tree = new_stats
+                        for k in path[:-1]:
+                            tree = tree.setdefault(k, {})
+                        tree[path[-1]] = (momentum * run + (1.0 - momentum) * batch).detach()
                 z = (z - mean) * torch.rsqrt(var + u.bn_eps) * _get(params, u.bn_scale) + _get(params, u.bn_bias)
             if u.res is not None:
                 z = z + vals[u.res]
             vals[u.dst] = act_fn(u.act, z)
         out = vals[self.out].reshape(xb.shape[0], -1)
+        if train:
+            return (out[0] if single else out), new_stats
         if return_all:
             return out, vals
         return out[0] if single else out
@@ -334,6 +350,7 @@ class NetSpec:
                     (``src/toymodels.py:9-24``)
         classifier: ``apply_fn(variables, x, train=False, mutable=False)`` -> logits
         ``variables`` may carry ``'batch_stats'``; otherwise the stats given here.
+        ``train=True`` with ``mutable=["batch_stats"]`` follows Flax's return shape: ``(outputs, {"batch_stats": new})``.
         """
         default_stats = batch_stats if batch_stats is not None else {}
 
@@ -341,9 +358,15 @@ class NetSpec:
             stats = variables.get("batch_stats", default_stats) if isinstance(variables, dict) else default_stats
             if stats is None or (isinstance(stats, dict) and not stats):
                 stats = default_stats
-            out = self.forward(variables, stats, x)
+            new_vars = None
+            if train:
+                out, new_stats = self.forward(variables, stats, x, train=True)
+                if mutable:
+                    new_vars = {"batch_stats": new_stats}
+            else:
+                out = self.forward(variables, stats, x)
             if model_type == "regressor" and return_logvar:
-                return out, variables["logvar"]["logvar"]
-            return out
+                out = (out, variables["logvar"]["logvar"])
+            return out if new_vars is None else (out, new_vars)
 
         return apply_fn

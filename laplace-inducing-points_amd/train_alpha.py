@@ -1,7 +1,7 @@
 """Log-marginal-likelihood in the prior precision alpha — the reference's ``src/train_alpha.py`` ("next" row N2).
 
-``log_marginal_likelihood`` (``:13-44``), ``update_alpha`` (``:47-59``), plus ``fit_alpha`` (the alpha hyper-steps of
-``train_map_then_alpha`` ``:65-121`` for a fixed theta; the interleaved MAP training is out of scope).
+``log_marginal_likelihood`` (``:13-44``), ``update_alpha`` (``:47-59``), ``train_map_then_alpha`` (``:65-121``: MAP steps
+on theta interleaved with hyper-steps on alpha) and ``fit_alpha`` (its alpha hyper-steps for a fixed theta).
 
   log p(D | alpha) = -1/2 alpha ||theta||^2 + 1/2 D log alpha - 1/2 [ log det(I_d + (N/n)/alpha W^T W) + D log alpha ]
 
@@ -113,6 +113,40 @@ def fit_alpha(X, state, model_type, full_set_size=None, alpha0: float = 1.0, alp
     N = full_set_size or X.shape[0]
     lam, D, theta2 = _spectrum(X, state, model_type)
     return _fit_from_spectrum(lam, D, theta2, N / X.shape[0], alpha0, alpha_lr, steps)
+
+
+def train_map_then_alpha(state, train_loader, test_loader, *, model_type: str, num_epochs: int = 500, alpha0: float = 1.0,
+                         alpha_lr: float = 5e-2, alpha_every: int = 5, burnin: int = 100, full_set_size: Optional[int] = None,
+                         optimizer=None, log=None):
+    """``src/train_alpha.py:65-121``: every epoch runs the MAP steps of ``train_map.MapTrainer`` over ``train_loader`` at
+    the prior precision exp(log_alpha); after epoch ``e >= burnin`` with ``(e + 1) % alpha_every == 0`` one hyper-step
+    (:func:`update_alpha`) moves log_alpha on the evidence of the epoch's LAST batch at the current state.  Returns
+    ``(state, alpha)``.  ``optimizer``: the ``train_map.Adam`` of the MAP steps (default ``Adam(1e-3)``).  ``log``, when
+    given, is called after every epoch with ``dict(epoch, train_loss, alpha, hyper_state, hyper_batch)`` (the state and
+    batch of the epoch's hyper-step, or None) and, every fourth epoch as in the reference, ``test_nll`` / ``test_acc`` of
+    ``test_loader`` in eval mode."""
+    from .train_map import MapTrainer
+    log_alpha = math.log(alpha0)
+    opt_h = Adam(alpha_lr)
+    opt_hs = opt_h.init()
+    trainer = MapTrainer(state, model_type, alpha0, optimizer)
+    for epoch in range(int(num_epochs)):
+        trainer.set_alpha(math.exp(log_alpha))
+        loss, last = float("nan"), None
+        for x, y in train_loader:
+            loss = trainer.step(x, y)
+            last = x
+        hyper_state = None
+        if last is not None and epoch >= burnin and (epoch + 1) % alpha_every == 0:
+            hyper_state = trainer.state()
+            log_alpha, opt_hs = update_alpha(log_alpha, opt_hs, opt_h, last, hyper_state, model_type, full_set_size)
+        if log is not None:
+            rec = dict(epoch=epoch, train_loss=loss, alpha=math.exp(log_alpha), hyper_state=hyper_state,
+                       hyper_batch=last if hyper_state is not None else None)
+            if epoch % 4 == 0:
+                rec["test_nll"], rec["test_acc"] = trainer.evaluate(test_loader)
+            log(rec)
+    return trainer.state(), math.exp(log_alpha)
 
 
 def log_marginal_likelihood_last_layer(alpha, X, state, model_type: str, full_set_size: Optional[int] = None) -> float:
