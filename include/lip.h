@@ -140,6 +140,14 @@ int lip_set_split_k(int32_t on);
  * variable LIP_NOWINO is read once; this call overrides it.                                             */
 int lip_set_winograd(int32_t mode);
 int lip_get_winograd(void);
+/* Probe walk of the Winograd conv kernel: a block handles w consecutive probes of its (tile block, column block).
+ * 0 = automatic (default: the largest w in {1, 2, 4} that leaves the launch enough blocks; 1 for launches of at most
+ * 8 probes), 1 / 2 / 4 = forced (capped by the probe count of the launch).  Every output except the float-atomic
+ * column sums is bit-identical for every w.  lip_wino_walk_plan: what the automatic rule takes for a launch of gx
+ * blocks per probe and P probes (a pure query).                                                        */
+int lip_set_wino_walk(int32_t w);
+int lip_get_wino_walk(void);
+int lip_wino_walk_plan(int64_t gx, int32_t P);
 
 /* ---- engine: one per (network, theta_MAP, data slice Z) binding on one device --------
  * Replaces the closure factories compute_ggn_vp / compute_W_vps (src/ggn.py:97,9): they

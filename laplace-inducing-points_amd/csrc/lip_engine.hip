@@ -796,6 +796,9 @@ int lip_set_precision(int32_t mode) { if (mode != 0 && mode != 1) { set_error("l
 int lip_set_split_k(int32_t on) { set_split_k_mode(on != 0); return LIP_OK; }
 int lip_set_winograd(int32_t mode) { if (mode < 0 || mode > 2) { set_error("lip_set_winograd: mode must be 0 (off), 1 (auto) or 2 (every eligible launch)"); return LIP_ERR_ARG; } set_wino_mode(mode); return LIP_OK; }
 int lip_get_winograd(void) { return wino_mode(); }
+int lip_set_wino_walk(int32_t w) { if (w != 0 && w != 1 && w != 2 && w != 4) { set_error("lip_set_wino_walk: w must be 0 (automatic), 1, 2 or 4"); return LIP_ERR_ARG; } set_wino_walk(w); return LIP_OK; }
+int lip_get_wino_walk(void) { return wino_walk(); }
+int lip_wino_walk_plan(int64_t gx, int32_t P) { return wino_walk_plan((long long)gx, P); }
 int lip_get_precision(void) { return precision_mode(); }
 
 int lip_engine_create(lip_engine_t** out, int64_t D, int32_t n_img, int32_t K) {

@@ -408,6 +408,9 @@ void set_precision_mode(int m);
 void set_split_k_mode(int on);
 void set_wino_mode(int m);
 int wino_mode();
+void set_wino_walk(int w);
+int wino_walk();
+int wino_walk_plan(long long gx, int P);
 
 // ---- wave / block reductions (wave = 64 lanes on gfx950) --------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

@@ -281,8 +281,8 @@ __device__ __forceinline__ void pipelined_k_loop(int T, float* As, float* Bs, Lo
 #endif
 // PAR == 2 (Winograd): the block's 32 accumulator rows are tiles; `rowtab[i]` (LDS) holds the tensor row of pixel (0, 0)
 // of tile i or -1, the wave writes pixel (ph, pw) of every tile, `tab_full` says that no tile of the block is masked.
-template <int WM, int WN, int TM, int TN, int PAR = 0>
-__device__ __forceinline__ void igemm_epilogue(const IgemmP& prm, f32x16 (&acc)[TM][TN], float* redbuf, int p, int r0,
+template <int WM, int WN, int TM, int TN, int PAR = 0, class PRM = IgemmP>
+__device__ __forceinline__ void igemm_epilogue(const PRM& prm, f32x16 (&acc)[TM][TN], float* redbuf, int p, int r0,
                                                int n0, int wm, int wn, int lane, int tid, int ph = 0, int pw = 0,
                                                const int* rowtab = nullptr, bool tab_full = false) {
   using T = Tile<WM, WN, TM, TN>;
@@ -290,11 +290,15 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmP& prm, f32x16 (&acc)[
   const int N = prm.N, R = PAR == 1 ? prm.Rc : prm.R;
   const int tab_shift = ph * prm.OW + pw;
   auto row_of = [&](int r) -> int {
-    if (PAR == 2) return rowtab[r] + tab_shift;
-    if (!PAR) return r;
-    const int i = prm.dOHW2.div(r), rem = r - i * prm.OHW2;
-    const int a = prm.dOW2.div(rem), b = rem - a * prm.OW2;
-    return i * prm.OHW + (2 * a + ph) * prm.OW + 2 * b + pw;
+    if constexpr (PAR == 2) {
+      return rowtab[r] + tab_shift;
+    } else if constexpr (!PAR) {
+      return r;
+    } else {
+      const int i = prm.dOHW2.div(r), rem = r - i * prm.OHW2;
+      const int a = prm.dOW2.div(rem), b = rem - a * prm.OW2;
+      return i * prm.OHW + (2 * a + ph) * prm.OW + 2 * b + pw;
+    }
   };
   const int l31 = lane & 31, lh = lane >> 5;
   const bool do_red = (prm.red0 != nullptr) || (prm.red1 != nullptr);
@@ -1069,6 +1073,10 @@ __global__ __launch_bounds__(256) void igemm_adirect_kernel(const IgemmP prm) {
 //     launch geometry alone — they come from a per-geometry table (wino_table_kernel, filled once per stream and
 //     geometry); a block adds its base pixel and tests the borders against per-block scalars.  The block index is taken
 //     apart on the scalar unit.  First buffer_load at instruction ~250 of the kernel (454 with the decode in the kernel);
+//   * probe walk: a block handles WinoX::walk consecutive probes of its (tile block, column block) — the set-up once,
+//     and the request behind a probe's last chunk (redundant without a walk) fetches the next probe's first chunk, whose
+//     round trip then runs under the output transform, exchange and epilogue ("Probe walk": how the
+//     loop stays inside the three-wave register budget, the hazards, the launcher's rule).
 // Several K-segments (tangent: conv(da, W) + conv(a, dW_p)) accumulate in the transformed domain: one output transform.
 // Mode-1 segments (data gradient, stride 1) are the same correlation with the kernel flipped — the weight transform does it.
 // Never used for the primal tape (ReLU gates / pooling arg-maxima are taken from the direct sums).
@@ -1079,6 +1087,7 @@ struct WinoX {
   unsigned a_bytes[3]; unsigned u_bytes[3];
   const i32x4v* tab;                    // geometry table of the launch (wino_table_kernel)
   int BWs, BHs, NI, FC9, nbx, n_img, TH, TW, H;   // FC9 = 9 * FC: one footprint row in 16-byte LDS units; H = OHW / OW
+  int walk, P;                          // probes a block walks (grid y = ceil(P / walk)), probes of the launch
   FastDiv dnb, dbxy, dnbx, dgx;         // N / 32, nbx * nby, nbx, gridDim.x
 };
 
@@ -1161,7 +1170,8 @@ __global__ __launch_bounds__(256) void wino_weight_transform_kernel(const float*
 // tile are four consecutive floats of the exchange area ([a][q][reg][lane], lane = column) and of every operand tensor,
 // so the three exchange reads, the operand loads and the store of a tile are one ds_read_b128 / dwordx4 each (20 memory
 // instructions per lane where the accumulator-layout epilogue issues 80).  Used when every operand is 16-byte aligned.
-__device__ __forceinline__ void wino_epilogue_v4(const IgemmP& prm, const float* xch, float* redbuf, const int* rowtab, int p, int n0,
+template <class PRM>
+__device__ __forceinline__ void wino_epilogue_v4(const PRM& prm, const float* xch, float* redbuf, const int* rowtab, int p, int n0,
                                                  int lane, int tid, int a, bool blk_full) {
   const int po = a >> 1, qo = a & 1;
   const int cq = lane & 7, ti = lane >> 3;
@@ -1263,11 +1273,13 @@ constexpr int WINO_SLOTS = 224;     // LDS pixel slots of the staged footprint (
 
 template <bool VEPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void igemm_wino_kernel(const IgemmP prm, const WinoX wx) {
-  // stage [WINO_SLOTS][36] floats, later the exchange [4 a][2 q][16 reg][64 lane] (aliased); then rowtab[32], redbuf[64]
+  // stage [WINO_SLOTS][36] floats, later the exchange [4 a][2 q][16 reg][64 lane] (aliased); then rowtab[32], redbuf[64],
+  // park[9][256]
   extern __shared__ __attribute__((aligned(16))) float wino_lds[];
   constexpr int BN = 32;
   int* rowtab = reinterpret_cast<int*>(wino_lds + 8192);
   float* redbuf = wino_lds + 8192 + 32;
+  int* park = reinterpret_cast<int*>(wino_lds + 8192 + 96);
   f32x4v* lds4 = reinterpret_cast<f32x4v*>(wino_lds);
   const int tid = threadIdx.x, lane = tid & 63;
   const int a = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1278,13 +1290,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
 #pragma unroll
   for (int j = 0; j < 4; ++j) st4[j] = wx.tab[(tid >> 3) * 4 + j];
   const i32x4v tile4 = wx.tab[128 + l31];
-  // block index -> (tile block (bi, by, bx), column block cb, probe p): wave-uniform, on the scalar unit
+  // block index -> (tile block (bi, by, bx), column block cb, first probe p0 of the walk): wave-uniform, on the scalar unit
   int bid = __builtin_amdgcn_readfirstlane((int)blockIdx.x), byp = __builtin_amdgcn_readfirstlane((int)blockIdx.y);
   xcd_block_order(bid, byp, (int)gridDim.x, (int)gridDim.y, wx.dgx);
   const int tbid = wx.dnb.div(bid), cb = bid - tbid * (int)wx.dnb.d;
   const int bi = wx.dbxy.div(tbid), brem = tbid - bi * (int)wx.dbxy.d;
   const int by = wx.dnbx.div(brem), bx = brem - by * wx.nbx;
-  const int p = byp;
+  const int walk = wx.walk;
+  const int p0 = byp * walk, p_last = min(p0 + walk, wx.P) - 1;
+  int p = p0;
   const int n0 = cb * BN;
   if (tid < 2 * BN) redbuf[tid] = 0.f;
 
@@ -1305,8 +1319,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
   const int r1 = (a == 0) ? 0 : (a == 2 ? 2 : 1);
   const int r2 = (a == 0) ? 2 : (a == 1 ? 2 : (a == 2 ? 1 : 3));
   const float sg = (a == 1) ? 1.f : -1.f;
-  const int rq1 = tile4[2] + r1 * wx.FC9 + h;                              // LDS read bases in 16-byte units
-  const int rq2 = tile4[2] + r2 * wx.FC9 + h;
+  int rq1 = tile4[2] + r1 * wx.FC9 + h;                                    // LDS read bases in 16-byte units
+  int rq2 = tile4[2] + r2 * wx.FC9 + h;
   // staging: thread -> (pixel slot, 16-byte part) x 7; a pixel outside the map or past the last image is not requested
   const int part = tid & 7;
   int spix[7];
@@ -1324,9 +1338,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
   f32x4v sreg[7], bq[2][4];
   // (buffer loads are cast to float vectors whole: element access through __builtin_bit_cast(float, v[j]) on the
   //  unsigned vector the builtin returns is miscompiled by hipcc 7.2 — only element 0 survives)
-  auto stage_load = [&](int seg, int k) __attribute__((always_inline)) {
+  auto stage_load = [&](int pp, int seg, int k) __attribute__((always_inline)) {
     const SegP& s = prm.seg[seg];
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.a + (long long)p * s.a_ps), 0, wx.a_bytes[seg], 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.a + (long long)pp * s.a_ps), 0, wx.a_bytes[seg], 0x00020000);
     const int C = s.C;
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
@@ -1341,9 +1355,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
       if (slot < WINO_SLOTS) lds4[slot * 9 + part] = sreg[j];
     }
   };
-  auto load_b = [&](int seg, int g, f32x4v (&dst)[4]) __attribute__((always_inline)) {
+  auto load_b = [&](int pp, int seg, int g, f32x4v (&dst)[4]) __attribute__((always_inline)) {
     const SegP& s = prm.seg[seg];
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.b + (long long)p * s.b_ps), 0, wx.u_bytes[seg], 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.b + (long long)pp * s.b_ps), 0, wx.u_bytes[seg], 0x00020000);
     const int c4 = s.C >> 2;
     const unsigned uvoff = (unsigned)((((4 * a) * c4 + h) * N + n0 + l31) * 16);
     const unsigned ub_stride = (unsigned)(c4 * N * 16), ug_stride = (unsigned)(2 * N * 16);
@@ -1360,7 +1374,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
       raw[cc] = lds4[rq1 + cc * 9 + 2 * g];
       raw[4 + cc] = lds4[rq2 + cc * 9 + 2 * g];
     }
-    load_b(seg_n, g_n, bn);
+    load_b(p, seg_n, g_n, bn);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1375,56 +1389,94 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void i
       for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[b][j], bc[b][j], acc[b], 0, 0, 0);
   };
 
-  stage_load(0, 0);
-  load_b(0, 0, bq[0]);
+  // a walk parks what the set-up made for the staging requests and the LDS reads (9 dwords per thread) and reads it
+  // back after each epilogue: those registers are free while the epilogue holds its operands
+  if (walk > 1) {
+#pragma unroll
+    for (int j = 0; j < 7; ++j) park[j * 256 + tid] = spix[j];
+    park[7 * 256 + tid] = rq1; park[8 * 256 + tid] = rq2;
+  }
+  stage_load(p, 0, 0);
   const int nseg = prm.nseg;
-  for (int seg = 0; seg < nseg; ++seg) {
-    const int chunks = prm.seg[seg].C >> 5, GT = prm.seg[seg].C >> 3;
-    const bool more_seg = seg + 1 < nseg;
-    for (int k = 0; k < chunks; ++k) {
-      stage_store();
-      __syncthreads();
-      const int g0 = 4 * k;
-      const bool last = k + 1 == chunks;
-      // what follows this chunk: the next chunk of the segment, the first of the next segment, or (at the very end) this
-      // chunk again — a redundant request instead of a branch in the loop
-      const int seg_n = (last && more_seg) ? seg + 1 : seg;
-      const int k_n = last ? (more_seg ? 0 : k) : k + 1;
-      const int g_n = last ? (more_seg ? 0 : GT - 1) : g0 + 4;
-      __builtin_amdgcn_sched_barrier(0);
-      group(0, seg, g0 + 1, bq[0], bq[1]);
-      group(1, seg, g0 + 2, bq[1], bq[0]);
-      group(2, seg, g0 + 3, bq[0], bq[1]);
-      group(3, seg_n, g_n, bq[1], bq[0]);
-      __builtin_amdgcn_sched_barrier(0);
-      stage_load(seg_n, k_n);
-      __syncthreads();
+  for (;;) {
+    // the probe whose first chunk the tail request of this probe's K loop fetches: the next one of the walk
+    const int pn = min(p + 1, p_last);
+    const bool adv = p < p_last;
+    load_b(p, 0, 0, bq[0]);
+    zero_acc(acc);
+    for (int seg = 0; seg < nseg; ++seg) {
+      const int chunks = prm.seg[seg].C >> 5, GT = prm.seg[seg].C >> 3;
+      const bool more_seg = seg + 1 < nseg;
+      for (int k = 0; k < chunks; ++k) {
+        stage_store();
+        __syncthreads();
+        const int g0 = 4 * k;
+        const bool last = k + 1 == chunks;
+        // what follows this chunk: the next chunk of the segment, the first of the next segment, at the very end the first
+        // chunk of the walk's next probe (its round trip runs under this probe's output transform, exchange and epilogue;
+        // the 28 staging registers are carried across them) or, on the walk's last probe, this chunk again — a redundant
+        // request instead of a branch in the loop.  The B request behind the last group stays redundant: the first B group
+        // of a probe is requested at its top (16 more carried registers took the kernel past three waves per SIMD)
+        const bool hop = last && !more_seg && adv;
+        const int seg_n = last ? (more_seg ? seg + 1 : (hop ? 0 : seg)) : seg;
+        const int k_n = last ? ((more_seg || hop) ? 0 : k) : k + 1;
+        const int seg_bn = (last && more_seg) ? seg + 1 : seg;
+        const int g_n = last ? (more_seg ? 0 : GT - 1) : g0 + 4;
+        __builtin_amdgcn_sched_barrier(0);
+        group(0, seg, g0 + 1, bq[0], bq[1]);
+        group(1, seg, g0 + 2, bq[1], bq[0]);
+        group(2, seg, g0 + 3, bq[0], bq[1]);
+        group(3, seg_bn, g_n, bq[1], bq[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        stage_load(hop ? pn : p, seg_n, k_n);
+        __syncthreads();
+      }
     }
-  }
 
-  // output transform, in-wave part (A^T rows: m0+m1+m2, m1-m2-m3 over b) ...
+    // output transform, in-wave part (A^T rows: m0+m1+m2, m1-m2-m3 over b) ...
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float m0 = acc[0][r], m1 = acc[1][r], m2 = acc[2][r], m3 = acc[3][r];
-    wino_lds[((a * 2 + 0) * 16 + r) * 64 + lane] = m0 + m1 + m2;
-    wino_lds[((a * 2 + 1) * 16 + r) * 64 + lane] = m1 - m2 - m3;
-  }
-  __syncthreads();
-  // ... and across the waves over a: wave w owns output pixel (po, qo) of every tile
-  if (VEPI) {
-    wino_epilogue_v4(prm, wino_lds, redbuf, rowtab, p, n0, lane, tid, a, blk_full);
-    return;
-  }
-  const int po = a >> 1, qo = a & 1;
-  f32x16 y[1][1];
+    for (int r = 0; r < 16; ++r) {
+      const float m0 = acc[0][r], m1 = acc[1][r], m2 = acc[2][r], m3 = acc[3][r];
+      wino_lds[((a * 2 + 0) * 16 + r) * 64 + lane] = m0 + m1 + m2;
+      wino_lds[((a * 2 + 1) * 16 + r) * 64 + lane] = m1 - m2 - m3;
+    }
+    __syncthreads();
+    // ... and across the waves over a: wave w owns output pixel (po, qo) of every tile.  Two devices keep the epilogue's
+    // operands out of the K loop's registers now that both sit in one loop: its lane constants derive from a per-probe
+    // opaque copy of the thread index (else they are hoisted out of the probe loop and live through the K loop), and it
+    // reads its launch parameters through the kernel-argument pointer, made opaque per probe too — scalar loads per
+    // probe instead of ~40 SGPRs held through the K loop (which spilled).  (prm is the first kernel argument.)
+    int tid_e = tid;
+    asm volatile("" : "+v"(tid_e));
+    const int lane_e = tid_e & 63;
+    typedef const __attribute__((address_space(4))) IgemmP KPrm;
+    KPrm* kp = (KPrm*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    if (VEPI) {
+      wino_epilogue_v4(*kp, wino_lds, redbuf, rowtab, p, n0, lane_e, tid_e, a, blk_full);
+    } else {
+      const int po = a >> 1, qo = a & 1;
+      f32x16 y[1][1];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float t1 = wino_lds[((1 * 2 + qo) * 16 + r) * 64 + lane];
-    const float t2 = wino_lds[((2 * 2 + qo) * 16 + r) * 64 + lane];
-    const float t03 = wino_lds[(((po ? 3 : 0) * 2 + qo) * 16 + r) * 64 + lane];
-    y[0][0][r] = po ? (t1 - t2 - t03) : (t03 + t1 + t2);
+      for (int r = 0; r < 16; ++r) {
+        const float t1 = wino_lds[((1 * 2 + qo) * 16 + r) * 64 + lane_e];
+        const float t2 = wino_lds[((2 * 2 + qo) * 16 + r) * 64 + lane_e];
+        const float t03 = wino_lds[(((po ? 3 : 0) * 2 + qo) * 16 + r) * 64 + lane_e];
+        y[0][0][r] = po ? (t1 - t2 - t03) : (t03 + t1 + t2);
+      }
+      igemm_epilogue<1, 1, 1, 1, 2>(*kp, y, redbuf, p, 0, n0, 0, 0, lane_e, tid_e, po, qo, rowtab, blk_full);
+    }
+    if (p == p_last) break;
+    // next probe of the walk.  The threads that read the column sums clear them (each its own two entries, after its
+    // reads); the barrier orders that, and every exchange read of this probe, before the next probe's staging stores
+    // (the exchange area is the staging area).  rowtab stays as the set-up wrote it.
+    if (tid_e < BN) { redbuf[tid_e] = 0.f; redbuf[BN + tid_e] = 0.f; }
+    __syncthreads();
+    p = pn;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) spix[j] = park[j * 256 + tid_e];
+    rq1 = park[7 * 256 + tid_e]; rq2 = park[8 * 256 + tid_e];
   }
-  igemm_epilogue<1, 1, 1, 1, 2>(prm, y, redbuf, p, 0, n0, 0, 0, lane, tid, po, qo, rowtab, blk_full);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1646,6 +1698,22 @@ void set_wino_mode(int m) { g_wino = (m < 0 || m > 2) ? 1 : m; }
 int wino_mode() {
   const Switches& sw = switches();
   return g_wino < 0 ? (sw.nowino ? 0 : (sw.wino_f ? 2 : 1)) : g_wino;
+}
+
+// Probe walk of the Winograd kernel (igemm_wino_kernel): W consecutive probes per block, W in {1, 2, 4}.  0 = the rule
+// below (default), 1 / 2 / 4 forced (capped by the probe count).  The rule: the largest W that still leaves
+// WINO_WALK_K blocks per resident slot (three blocks per CU), and one probe per block for launches of at most 8 probes
+// (the few-probe and Krylov call shapes keep today's grid).
+constexpr int WINO_WALK_K = 8;
+static int g_wino_walk = 0;
+void set_wino_walk(int w) { g_wino_walk = (w == 1 || w == 2 || w == 4) ? w : 0; }
+int wino_walk() { return g_wino_walk; }
+int wino_walk_plan(long long gx, int P) {
+  if (P <= 8 || gx < 1) return 1;
+  const long long need = (long long)WINO_WALK_K * 3 * cu_count();
+  for (int w = 4; w > 1; w >>= 1)
+    if (gx * ((P + w - 1) / w) >= need) return w;
+  return 1;
 }
 
 static bool igemm_first_ok(const IgemmP& p, int P) {
@@ -3282,10 +3350,13 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st, BindCac
   wx.BWs = g.BWs; wx.BHs = g.BHs; wx.NI = g.NI; wx.FC9 = 9 * g.FC; wx.nbx = g.nbx;
   wx.n_img = (int)n_img; wx.TH = g.TH; wx.TW = g.TW; wx.H = OH;
   const long long gx = (long long)g.nbx * g.nby * g.nbi * (p.N / 32);
+  const int forced = wino_walk();
+  wx.walk = forced ? (forced < P ? forced : P) : wino_walk_plan(gx, P);
+  wx.P = P;
   wx.dnb = FastDiv((unsigned)(p.N / 32)); wx.dbxy = FastDiv((unsigned)(g.nbx * g.nby)); wx.dnbx = FastDiv((unsigned)g.nbx);
   wx.dgx = FastDiv((unsigned)gx);
   q.zeros = nullptr; q.dbg = nullptr; q.partial = nullptr;
-  const size_t shmem = (size_t)(8192 + 32 + 64) * sizeof(float);
+  const size_t shmem = (size_t)(8192 + 32 + 64 + 9 * 256) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute((const void*)igemm_wino_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
@@ -3296,7 +3367,7 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st, BindCac
   // 16-byte epilogue accesses when every operand tensor allows them (A/B switch LIP_WINO_NOVEPI)
   auto al16 = [](const void* ptr, long long ps) { return ptr == nullptr || ((((uintptr_t)ptr) & 15) == 0 && (ps & 3) == 0); };
   const bool vepi = !switches().wino_novepi && al16(p.out, p.out_ps) && al16(p.res, p.res_ps) && al16(p.xhat, 0) && al16(p.dphi, 0) && al16(p.xhat2, 0);
-  dim3 grid((unsigned)gx, (unsigned)P, 1);
+  dim3 grid((unsigned)gx, (unsigned)((P + wx.walk - 1) / wx.walk), 1);
   with_flag(vepi, [&](auto v) {
     LIP_ROUTE("igemm_wino%s", v ? "/vepi" : ""); hipLaunchKernelGGL(igemm_wino_kernel<v>, grid, dim3(256), shmem, st, q, wx);
   });
