@@ -124,7 +124,16 @@ typedef struct lip_engine lip_engine_t;
 int lip_abi_version(void);                 /* bumps on incompatible changes of this header (added entry points keep it) */
 const char* lip_last_error(void);          /* text of the last failure on this thread            */
 int lip_sizeof_op(void);                   /* sizeof(lip_op_t): lets the ctypes mirror self-check */
-/* arithmetic of the MFMA kernels (process-wide): 0 = exact f32 MFMA (default, dtype "f32");
+/* The route of a product: precision, split-K, Winograd and the Winograd probe walk, four process-wide modes with the
+ * setters below.  An entry point that launches kernels reads the four ONCE, before its first launch, and uses that
+ * snapshot for every pass and every launch it makes:
+ *   - a setter takes effect at the next entry-point call;
+ *   - a call in flight, on this or another thread, keeps the route it started with (the modes are atomic words: a
+ *     setter may run at any time without tearing a call's plan).
+ * A launch whose route needs per-stream scratch that cannot be had (the library keeps scratch for 16 (device, stream)
+ * pairs; or the allocation fails) runs on the direct kernels instead, with the same result to rounding.
+ *
+ * arithmetic of the MFMA kernels: 0 = exact f32 MFMA (default, dtype "f32");
  * 1 = split-precision operands x = hi + lo in bf16, three bf16 MFMAs per product with f32 accumulation
  *     ("bf16x3": ~1e-5 relative error per product, ~5x fewer matrix-pipe cycles).                     */
 int lip_set_precision(int32_t mode);
@@ -268,8 +277,9 @@ int lip_cg_direction(float* p, const float* r, const float* rr_new, const float*
 /* C (m, n) float64, overwritten = A B^T with A (m, K), B (n, K) float32 rows (row strides lda / ldb >= K, 4-byte
  * alignment suffices) accumulated in float64: the tall-skinny inner products whose float32 accumulation is too coarse —
  * the sampler's stiff-direction coefficients (src/sample.py:130-139 at cond 3e9), the Gram of Hutch++'s tall-skinny
- * orthonormalisation and its projections G Q^T (src/stochtrace.py:124-131).  Uses one partial-sum buffer per DEVICE:
- * calls on different streams of one device must not overlap (the package issues them on one stream).          */
+ * orthonormalisation and its projections G Q^T (src/stochtrace.py:124-131).  Uses one partial-sum buffer per (device,
+ * stream), so calls on different streams may overlap; without a buffer (a 17th (device, stream) pair, a failed
+ * allocation) the partial tiles are added with float64 atomics instead.                                        */
 int lip_dot_nt_f64(const float* A, int64_t lda, int32_t m, const float* B, int64_t ldb, int32_t n, int64_t K, double* C,
                    void* stream);
 /* C (m, n) float32, overwritten = A B^T, same operand layout as lip_dot_nt_f64, float32 MFMA with the long reduction

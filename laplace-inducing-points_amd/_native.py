@@ -244,7 +244,11 @@ def winograd_route(mode: int):
     """Process-wide switch of the Winograd route (``lip_set_winograd``) for the duration of a block; restores the
     previous setting.  0 = the direct implicit GEMMs everywhere: bit-for-bit fmaf chains, and an absolute rounding error
     ~4x smaller than the Winograd transforms' on products whose result cancels to far below ||A|| ||v|| (the deflated
-    Krylov routes work exactly there); 1 / 2 = the route on."""
+    Krylov routes work exactly there); 1 / 2 = the route on.
+
+    The library takes its route (precision, Winograd, probe walk, split-K) once per entry-point call, so the setting
+    holds for every engine call that STARTS inside the block; a call already in flight, on this or another thread,
+    keeps the route it started with."""
     lib = load()
     before = lib.lip_get_winograd()
     check(lib.lip_set_winograd(int(mode)), "lip_set_winograd")

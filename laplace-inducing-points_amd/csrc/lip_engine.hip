@@ -94,6 +94,16 @@ struct EigenBlock {
   const float* Rw = nullptr;
 };
 
+// The overwrite plan of one pass of a summed product (lip_ggn_vp / lip_vjp): the parameter ranges of Y, ascending, that
+// init_output left unwritten because a fused weight gradient of the backward tape writes them outright.  Made once per
+// pass; make_wgrad sets overwrite for exactly the ops whose range is in it, so the two cannot disagree.
+struct SkipRange { int64_t off, len; };
+using OverwritePlan = std::vector<SkipRange>;
+inline bool planned(const OverwritePlan& plan, int64_t off) {
+  const auto it = std::lower_bound(plan.begin(), plan.end(), off, [](const SkipRange& r, int64_t o) { return r.off < o; });
+  return it != plan.end() && it->off == off;
+}
+
 struct RunCtx {
   const lip_engine* e;
   const float* V;   // chunk-shifted
@@ -102,6 +112,7 @@ struct RunCtx {
   int P;            // probes in this chunk
   int head_mode;
   float head_c;
+  Route route;      // taken once per entry-point call (current_route()), before its first pass
   hipStream_t st;
   Sweep mode = Sweep::SUMMED;
   float* scratch = nullptr;       // SQSUM / WNORM: the square-accumulating kernels' scratch
@@ -112,19 +123,19 @@ struct RunCtx {
   double* kron_scratch = nullptr; // ... and the partial tiles of one Gram
   long long kron_doubles = 0;
   const EigenBlock* eigen = nullptr;  // EIGEN / EWNORM: the blocks of the WGRAD ops in tape order (run_tape picks the op's), scratch as SQSUM's
-  // summed products (lip_ggn_vp / lip_vjp): a weight gradient that reduces all rows in one block may WRITE
-  // y = s acc + alpha v instead of adding to an initialised block (the initialisation then skips its parameters)
-  bool fuse = false;
+  // summed products (lip_ggn_vp / lip_vjp): a weight gradient that reduces all rows in one block WRITES
+  // y = s acc + alpha v instead of adding to an initialised block where the pass's plan says the initialisation skipped
+  // its parameters; a context without a plan never overwrites
+  const OverwritePlan* plan = nullptr;
   float alpha = 0.f;
 
   bool per_example() const { return mode != Sweep::SUMMED; }      // cotangents are taken per example
   // no parameter cotangent is formed (an EWNORM sweep without a weight vector launches no reduction either)
   bool no_params() const { return mode == Sweep::KRON || mode == Sweep::EIGEN || (mode == Sweep::EWNORM && !Y); }
-  bool may_overwrite(const lip_ref_t& out) const { return fuse && mode == Sweep::SUMMED && out.space == LIP_SP_YOUT; }
 };
 
-// The kinds of sweep, from the operands of one pass (a plain RunCtx{..., st} is summed and not fused)
-inline RunCtx fused_sum(RunCtx c, float alpha) { c.fuse = true; c.alpha = alpha; return c; }
+// The kinds of sweep, from the operands of one pass (a plain RunCtx{..., route, st} is summed and not fused)
+inline RunCtx fused_sum(RunCtx c, float alpha, const OverwritePlan* plan) { c.alpha = alpha; c.plan = plan; return c; }
 inline RunCtx example_rows(RunCtx c) { c.mode = Sweep::ROWS; return c; }
 inline RunCtx square_sum(RunCtx c, float* scratch, long long floats) {
   c.mode = Sweep::SQSUM; c.scratch = scratch; c.scratch_floats = floats;
@@ -229,7 +240,8 @@ int check_space(const RunCtx& c, const lip_ref_t& r, const char* what) {
   return LIP_OK;
 }
 
-// resolved parameter block of a WGRAD op in this context (also queried by the initialisation plan of lip_ggn_vp / lip_vjp)
+// resolved parameter block of a WGRAD op in this context (init_output makes it too, in a context that has no plan yet, to
+// ask wgrad_will_overwrite about the op)
 int make_wgrad(const RunCtx& c, const lip_op_t& op, WgradP& p) {
   const lip_seg_t& g = op.seg[0];
   p = WgradP();
@@ -255,7 +267,7 @@ int make_wgrad(const RunCtx& c, const lip_op_t& op, WgradP& p) {
     return LIP_ERR_ARG;
   }
   if ((p.C & 3) == 0 && (((uintptr_t)p.a) & 15)) { set_error("WGRAD: activations not 16-byte aligned"); return LIP_ERR_ARG; }
-  if (c.may_overwrite(op.out) && wgrad_will_overwrite(p, c.P)) {
+  if (c.plan && op.out.space == LIP_SP_YOUT && planned(*c.plan, op.out.off)) {
     p.overwrite = 1;
     p.v = c.V ? c.V + op.out.off : nullptr; p.v_ps = op.out.pstride; p.alpha = c.alpha;
   }
@@ -457,7 +469,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
       if (p.red1 && !p.xhat2) { set_error("IGEMM: red1 without xhat2"); return LIP_ERR_ARG; }
       unsigned fixed_b = 0;
       for (int s = 0; s < op.nseg; ++s) fixed_b |= bound_space(op.seg[s].b) ? 1u << s : 0u;
-      return launch_with_reductions(c, p, [&](const IgemmP& q) { return launch_igemm(q, c.P, c.st, c.e->cache, fixed_b); }, "IGEMM launch",
+      return launch_with_reductions(c, p, [&](const IgemmP& q) { return launch_igemm(q, c.P, c.st, c.route, c.e->cache, fixed_b); }, "IGEMM launch",
                                     op.n_img, p.OHW, p.N, p.xhat2);
     }
     case LIP_OP_WGRAD: {
@@ -473,7 +485,7 @@ int run_op(const RunCtx& c, const lip_op_t& op) {
           RUN_CHECK(launch_wgrad_wnorm(p, c.P, op.n_img, c.wones ? nullptr : p.y, c.wout, c.scratch, c.scratch_floats, c.st), "weighted-norm wgrad launch");
           break;
         case Sweep::SQSUM: RUN_CHECK(launch_wgrad_sqsum(p, c.P, op.n_img, c.scratch, c.scratch_floats, c.st), "square-sum wgrad launch"); break;
-        default: RUN_CHECK(launch_wgrad(p, c.P, c.st, bound_space(op.seg[0].a) ? c.e->cache : nullptr), "wgrad launch");
+        default: RUN_CHECK(launch_wgrad(p, c.P, c.st, c.route, bound_space(op.seg[0].a) ? c.e->cache : nullptr), "wgrad launch");
       }
       return LIP_OK;
     }
@@ -645,31 +657,32 @@ int run_tape(const RunCtx& c, int which, bool skip_head) {
 }
 
 // Initialise the (pc, D) output block of a summed product: alpha * V (or 0) everywhere EXCEPT the parameters a fused
-// weight gradient of the backward tape will write outright (make_wgrad sets overwrite for exactly those ops).
-int init_output(const RunCtx& c, int64_t D) {
-  struct Range { int64_t off, len; };
-  std::vector<Range> skip;
+// weight gradient of the backward tape will write outright.  c is the pass's plain context; the ranges left out are
+// returned in `skip`, the plan that the pass's fused context (fused_sum) then runs the tapes with.  This is the one place
+// where a pass asks wgrad_will_overwrite, once per WGRAD op.
+int init_output(const RunCtx& c, float alpha, int64_t D, OverwritePlan& skip) {
+  skip.clear();
   for (const lip_op_t& op : c.e->tape[LIP_TAPE_BACKWARD]) {
     if (op.kind != LIP_OP_WGRAD) continue;
     WgradP p;
     const int rc = make_wgrad(c, op, p);
     if (rc) return rc;
-    if (p.overwrite) skip.push_back({op.out.off, (int64_t)p.M * p.N});
+    if (op.out.space == LIP_SP_YOUT && wgrad_will_overwrite(p, c.P, c.route)) skip.push_back({op.out.off, (int64_t)p.M * p.N});
   }
-  const float* v = c.alpha != 0.f ? c.V : nullptr;
+  const float* v = alpha != 0.f ? c.V : nullptr;
   if (skip.empty()) {
-    if (v) RUN_CHECK(launch_scale_copy(c.Y, v, c.alpha, (long long)c.P * D, c.st), "scale_copy");
+    if (v) RUN_CHECK(launch_scale_copy(c.Y, v, alpha, (long long)c.P * D, c.st), "scale_copy");
     else RUN_CHECK(hipMemsetAsync(c.Y, 0, sizeof(float) * (size_t)c.P * D, c.st), "memset Y");
     return LIP_OK;
   }
-  std::sort(skip.begin(), skip.end(), [](const Range& a, const Range& b) { return a.off < b.off; });
+  std::sort(skip.begin(), skip.end(), [](const SkipRange& a, const SkipRange& b) { return a.off < b.off; });
   int64_t pos = 0;
-  for (const Range& r : skip) {
+  for (const SkipRange& r : skip) {
     if (r.off < pos) { set_error("init_output: overlapping weight-gradient outputs"); return LIP_ERR_STATE; }
-    RUN_CHECK(launch_scale_copy_range(c.Y, v, c.alpha, pos, r.off - pos, c.P, D, c.st), "scale_copy_range");
+    RUN_CHECK(launch_scale_copy_range(c.Y, v, alpha, pos, r.off - pos, c.P, D, c.st), "scale_copy_range");
     pos = r.off + r.len;
   }
-  RUN_CHECK(launch_scale_copy_range(c.Y, v, c.alpha, pos, D - pos, c.P, D, c.st), "scale_copy_range");
+  RUN_CHECK(launch_scale_copy_range(c.Y, v, alpha, pos, D - pos, c.P, D, c.st), "scale_copy_range");
   return LIP_OK;
 }
 
@@ -710,12 +723,15 @@ inline float* head_block(const lip_engine* e, const float* U, int c0) { return c
 // lip_ggn_vp, and lip_ggn_vp_diag (a != null): the same sweep with alpha = 0, its overwrite plan unchanged, then the
 // prior term a (.) V over the pass
 int ggn_sweep(const lip_engine* e, const float* V, float* Y, int P, float scale, float alpha, const float* a, hipStream_t st) {
+  const Route route = current_route();
+  OverwritePlan plan;
   return for_each_pass(e, P, [&](int c0, int pc) {
     const float* v = V + c0 * e->D;
     float* y = Y + c0 * e->D;
-    const RunCtx c = fused_sum(RunCtx{e, v, y, nullptr, pc, LIP_HEAD_GGN, scale, st}, alpha);
-    int rc;
-    if ((rc = init_output(c, e->D)) || (rc = run_tape(c, LIP_TAPE_TANGENT, false)) || (rc = run_tape(c, LIP_TAPE_BACKWARD, true))) return rc;
+    const RunCtx plain{e, v, y, nullptr, pc, LIP_HEAD_GGN, scale, route, st};
+    int rc = init_output(plain, alpha, e->D, plan);
+    const RunCtx c = fused_sum(plain, alpha, &plan);
+    if (rc || (rc = run_tape(c, LIP_TAPE_TANGENT, false)) || (rc = run_tape(c, LIP_TAPE_BACKWARD, true))) return rc;
     if (a) RUN_CHECK(launch_add_diag(y, v, a, pc, (long long)e->D, st), "add_diag");
     return LIP_OK;
   });
@@ -795,11 +811,11 @@ int lip_sizeof_op(void) { return (int)sizeof(lip_op_t); }
 int lip_set_precision(int32_t mode) { if (mode != 0 && mode != 1) { set_error("lip_set_precision: mode must be 0 (f32) or 1 (bf16x3)"); return LIP_ERR_ARG; } set_precision_mode(mode); return LIP_OK; }
 int lip_set_split_k(int32_t on) { set_split_k_mode(on != 0); return LIP_OK; }
 int lip_set_winograd(int32_t mode) { if (mode < 0 || mode > 2) { set_error("lip_set_winograd: mode must be 0 (off), 1 (auto) or 2 (every eligible launch)"); return LIP_ERR_ARG; } set_wino_mode(mode); return LIP_OK; }
-int lip_get_winograd(void) { return wino_mode(); }
+int lip_get_winograd(void) { return current_route().wino; }
 int lip_set_wino_walk(int32_t w) { if (w != 0 && w != 1 && w != 2 && w != 4) { set_error("lip_set_wino_walk: w must be 0 (automatic), 1, 2 or 4"); return LIP_ERR_ARG; } set_wino_walk(w); return LIP_OK; }
-int lip_get_wino_walk(void) { return wino_walk(); }
+int lip_get_wino_walk(void) { return current_route().walk; }
 int lip_wino_walk_plan(int64_t gx, int32_t P) { return wino_walk_plan((long long)gx, P); }
-int lip_get_precision(void) { return precision_mode(); }
+int lip_get_precision(void) { return current_route().precision; }
 
 int lip_engine_create(lip_engine_t** out, int64_t D, int32_t n_img, int32_t K) {
   if (!out || D <= 0 || n_img <= 0 || K <= 0) { set_error("lip_engine_create: bad argument"); return LIP_ERR_ARG; }
@@ -859,7 +875,7 @@ int lip_engine_primal(lip_engine_t* e, void* stream) {
   // the pass rewrites PRIM from a THETA that may have changed in place: whatever the cache holds is stale from here on
   // (dropped before the launches and after them, so nothing a failed pass left half-written is taken for current)
   if (e->cache) e->cache->invalidate();
-  const int rc = run_tape(RunCtx{e, nullptr, nullptr, nullptr, 1, 0, 1.f, (hipStream_t)stream}, LIP_TAPE_PRIMAL, false);
+  const int rc = run_tape(RunCtx{e, nullptr, nullptr, nullptr, 1, 0, 1.f, current_route(), (hipStream_t)stream}, LIP_TAPE_PRIMAL, false);
   if (e->cache) e->cache->invalidate();
   if (rc == LIP_OK) e->primal_done = true;
   e->train_primal_done = false;          // PRIM holds eval-mode activations again
@@ -908,7 +924,7 @@ int lip_train_primal(lip_engine_t* e, void* stream) {
   // THETA may have changed in place and PRIM is rewritten: as in lip_engine_primal, whatever the cache holds is stale
   e->primal_done = false; e->train_primal_done = false;
   if (e->cache) e->cache->invalidate();
-  rc = run_tape(RunCtx{e, nullptr, nullptr, nullptr, 1, 0, 1.f, (hipStream_t)stream}, LIP_TAPE_TRAIN_PRIMAL, false);
+  rc = run_tape(RunCtx{e, nullptr, nullptr, nullptr, 1, 0, 1.f, current_route(), (hipStream_t)stream}, LIP_TAPE_TRAIN_PRIMAL, false);
   if (e->cache) e->cache->invalidate();
   if (rc == LIP_OK) e->train_primal_done = true;
   return rc;
@@ -929,7 +945,7 @@ int lip_train_backward(lip_engine_t* e, const float* U, float* Y, void* stream) 
   if (rc) return rc;
   if (!e->train_primal_done) { set_error("lip_train_backward: train primal pass not run"); return LIP_ERR_STATE; }
   RUN_CHECK(hipMemsetAsync(Y, 0, sizeof(float) * (size_t)e->D, (hipStream_t)stream), "memset Y");
-  return run_tape(RunCtx{e, nullptr, Y, const_cast<float*>(U), 1, LIP_HEAD_IN, 1.f, (hipStream_t)stream}, LIP_TAPE_TRAIN_BACKWARD, false);
+  return run_tape(RunCtx{e, nullptr, Y, const_cast<float*>(U), 1, LIP_HEAD_IN, 1.f, current_route(), (hipStream_t)stream}, LIP_TAPE_TRAIN_BACKWARD, false);
 }
 
 int lip_engine_profile(lip_engine_t* e, int32_t enable) {
@@ -960,7 +976,7 @@ int lip_engine_run_op(lip_engine_t* e, const lip_op_t* op, const float* V, float
                       float head_c, void* stream) {
   if (!e || !op || P <= 0 || P > e->max_chunk) { set_error("lip_engine_run_op: bad argument"); return LIP_ERR_ARG; }
   if (!e->theta || !e->prim) { set_error("lip_engine_run_op: engine not bound"); return LIP_ERR_STATE; }
-  return run_op(RunCtx{e, V, Y, H, P, head_mode, head_c, (hipStream_t)stream}, *op);
+  return run_op(RunCtx{e, V, Y, H, P, head_mode, head_c, current_route(), (hipStream_t)stream}, *op);
 }
 
 int lip_debug_run_ops(lip_engine_t* e, int32_t which, int32_t first, int32_t count, const float* V, float* Y,
@@ -968,7 +984,7 @@ int lip_debug_run_ops(lip_engine_t* e, int32_t which, int32_t first, int32_t cou
   if (!e || which < 0 || which > LIP_TAPE_TRAIN_BACKWARD || P <= 0 || P > e->max_chunk) { set_error("lip_debug_run_ops: bad argument"); return LIP_ERR_ARG; }
   const std::vector<lip_op_t>& t = e->tape[which];
   if (first < 0 || count < 0 || (size_t)(first + count) > t.size()) { set_error("lip_debug_run_ops: bad op range"); return LIP_ERR_ARG; }
-  const RunCtx c{e, V, Y, H, P, head_mode, head_c, (hipStream_t)stream};
+  const RunCtx c{e, V, Y, H, P, head_mode, head_c, current_route(), (hipStream_t)stream};
   for (int i = first; i < first + count; ++i) {
     const int rc = run_op(c, t[i]);
     if (rc) return rc;
@@ -997,18 +1013,21 @@ int lip_ggn_vp_diag(lip_engine_t* e, const float* V, float* Y, int32_t P, float 
 int lip_jvp(lip_engine_t* e, const float* V, float* U, int32_t P, int32_t head_mode, float cc, void* stream) {
   const int rc = ready(e, "lip_jvp", V && U && P > 0 && (head_mode == LIP_HEAD_LT || head_mode == LIP_HEAD_OUT));
   if (rc) return rc;
+  const Route route = current_route();
   return for_each_pass(e, P, [&](int c0, int pc) {
-    return run_tape(RunCtx{e, V + c0 * e->D, nullptr, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream}, LIP_TAPE_TANGENT, false);
+    return run_tape(RunCtx{e, V + c0 * e->D, nullptr, head_block(e, U, c0), pc, head_mode, cc, route, (hipStream_t)stream}, LIP_TAPE_TANGENT, false);
   });
 }
 
 int lip_vjp(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t head_mode, float cc, void* stream) {
   const int rc = ready_vjp(e, "lip_vjp", U, Y, P, head_mode);
   if (rc) return rc;
+  const Route route = current_route();
+  OverwritePlan plan;
   return for_each_pass(e, P, [&](int c0, int pc) {
-    const RunCtx c = fused_sum(RunCtx{e, nullptr, Y + c0 * e->D, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream}, 0.f);
-    const int rc = init_output(c, e->D);
-    return rc ? rc : run_tape(c, LIP_TAPE_BACKWARD, false);
+    const RunCtx plain{e, nullptr, Y + c0 * e->D, head_block(e, U, c0), pc, head_mode, cc, route, (hipStream_t)stream};
+    const int rc = init_output(plain, 0.f, e->D, plan);
+    return rc ? rc : run_tape(fused_sum(plain, 0.f, &plan), LIP_TAPE_BACKWARD, false);
   });
 }
 
@@ -1017,10 +1036,11 @@ int lip_vjp_rows(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t h
   if (rc) return rc;
   const int64_t ystride = (int64_t)e->n_img * e->D;
   hipStream_t st = (hipStream_t)stream;
+  const Route route = current_route();
   return for_each_pass(e, P, [&](int c0, int pc) {
     float* y = Y + c0 * ystride;
     RUN_CHECK(hipMemsetAsync(y, 0, sizeof(float) * (size_t)pc * ystride, st), "memset Y");
-    return run_tape(example_rows(RunCtx{e, nullptr, y, head_block(e, U, c0), pc, head_mode, cc, st}), LIP_TAPE_BACKWARD, false);
+    return run_tape(example_rows(RunCtx{e, nullptr, y, head_block(e, U, c0), pc, head_mode, cc, route, st}), LIP_TAPE_BACKWARD, false);
   });
 }
 
@@ -1032,8 +1052,9 @@ int lip_vjp_sqsum(lip_engine_t* e, const float* U, float* Y, int32_t P, int32_t 
                   int64_t scratch_floats, void* stream) {
   int rc = ready_vjp(e, "lip_vjp_sqsum", U, Y, P, head_mode, scratch_floats >= 0);
   if (rc || (rc = scratch_fits(e, "lip_vjp_sqsum", Sweep::SQSUM, P, scratch, scratch_floats))) return rc;
+  const Route route = current_route();
   return for_each_pass(e, P, [&](int c0, int pc) {
-    const RunCtx c{e, nullptr, Y, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    const RunCtx c{e, nullptr, Y, head_block(e, U, c0), pc, head_mode, cc, route, (hipStream_t)stream};
     return run_tape(square_sum(c, scratch, scratch_floats), LIP_TAPE_BACKWARD, false);
   });
 }
@@ -1046,9 +1067,10 @@ int lip_vjp_wnorm(lip_engine_t* e, const float* U, const float* w, float* out, i
                   float* scratch, int64_t scratch_floats, void* stream) {
   int rc = ready_vjp(e, "lip_vjp_wnorm", U, out, P, head_mode, scratch_floats >= 0);
   if (rc || (rc = scratch_fits(e, "lip_vjp_wnorm", Sweep::WNORM, P, scratch, scratch_floats))) return rc;
+  const Route route = current_route();
   return for_each_pass(e, P, [&](int c0, int pc) {
     // (w == NULL: theta stands in for the weight vector — a (D,) device block whose slices are addressed, never read)
-    const RunCtx c{e, nullptr, const_cast<float*>(w ? w : e->theta), head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    const RunCtx c{e, nullptr, const_cast<float*>(w ? w : e->theta), head_block(e, U, c0), pc, head_mode, cc, route, (hipStream_t)stream};
     return run_tape(weighted_norm(c, scratch, scratch_floats, w == nullptr, out + (int64_t)c0 * e->n_img), LIP_TAPE_BACKWARD, false);
   });
 }
@@ -1084,8 +1106,9 @@ int lip_vjp_kron(lip_engine_t* e, const float* U, double* S, int32_t P, int32_t 
       set_error("lip_vjp_kron: 2^31 or more cotangent rows on a pass; bind fewer examples per engine");
       return LIP_ERR_ARG;
     }
+  const Route route = current_route();
   return for_each_pass(e, P, [&](int c0, int pc) {
-    const RunCtx c{e, nullptr, nullptr, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    const RunCtx c{e, nullptr, nullptr, head_block(e, U, c0), pc, head_mode, cc, route, (hipStream_t)stream};
     return run_tape(kron_factors(c, S, scratch, scratch_doubles), LIP_TAPE_BACKWARD, false);
   });
 }
@@ -1133,8 +1156,9 @@ int lip_vjp_eigen(lip_engine_t* e, const float* U, const double* const* V, const
     blocks.push_back(EigenBlock{V[k], Ub[k], Lam[k], (int)Mt[k]});
   }
   if (blocks.size() != (size_t)nblocks) { set_error("lip_vjp_eigen: %d blocks, the backward tape has %zu weight gradients", (int)nblocks, blocks.size()); return LIP_ERR_ARG; }
+  const Route route = current_route();
   return for_each_pass(e, P, [&](int c0, int pc) {
-    const RunCtx c{e, nullptr, nullptr, head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    const RunCtx c{e, nullptr, nullptr, head_block(e, U, c0), pc, head_mode, cc, route, (hipStream_t)stream};
     return run_tape(eigen_moments(c, blocks.data(), scratch, scratch_floats), LIP_TAPE_BACKWARD, false);
   });
 }
@@ -1179,9 +1203,10 @@ int lip_vjp_eigen_wnorm(lip_engine_t* e, const float* U, const double* const* V,
     blocks.push_back(b);
   }
   if (blocks.size() != (size_t)nblocks) { set_error("lip_vjp_eigen_wnorm: %d blocks, the backward tape has %zu weight gradients", (int)nblocks, blocks.size()); return LIP_ERR_ARG; }
+  const Route route = current_route();
   return for_each_pass(e, P, [&](int c0, int pc) {
     // (Y is the remainder's weight vector, read at the slices of the reductions only; null: no reduction runs)
-    const RunCtx c{e, nullptr, const_cast<float*>(w_rem), head_block(e, U, c0), pc, head_mode, cc, (hipStream_t)stream};
+    const RunCtx c{e, nullptr, const_cast<float*>(w_rem), head_block(e, U, c0), pc, head_mode, cc, route, (hipStream_t)stream};
     return run_tape(eigen_weighted_norm(c, blocks.data(), scratch, scratch_floats, out + (int64_t)c0 * e->n_img), LIP_TAPE_BACKWARD, false);
   });
 }

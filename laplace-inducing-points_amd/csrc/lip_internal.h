@@ -87,7 +87,8 @@ struct WgradP {
   // fused output of a weight gradient whose launch reduces all R rows in one block (no row split):
   //   overwrite == 1:  y = s * acc + alpha * v     (v = the probe's own slice of V at the same offset, or null)
   // instead of y += s * acc on a block the caller initialised with alpha * V — the initialisation pass over these
-  // parameters is then skipped (lip_ggn_vp).  Set by the engine only where wgrad_will_overwrite() says so.
+  // parameters is then skipped (lip_ggn_vp).  Set by the engine only for the ops whose range its initialisation skipped,
+  // which it decides with wgrad_will_overwrite().
   int overwrite; const float* v; long long v_ps; float alpha;
   int sk_mg0, sk_tiles, sk_tn0;         // wgrad_skinny_kernel: first m-group of the launch, column tiles per probe it walks, first of them
 };
@@ -184,13 +185,28 @@ __host__ __device__ __forceinline__ bool head_scales(int classifier, int mode) {
   return !classifier || mode == LIP_HEAD_OUT || mode == LIP_HEAD_IN;
 }
 
+// ---- the arithmetic route of a call ---------------------------------------------------------------------------------------
+// The four process-wide modes with setters (lip_set_precision / lip_set_winograd / lip_set_wino_walk / lip_set_split_k),
+// as ONE value.  An entry point takes current_route() once, before its first launch, and hands that value to every
+// predicate and launcher of the call: a setter takes effect at the next entry-point call, and a call in flight, on this or
+// another thread, keeps the route it started with.
+struct Route {
+  int precision;   // 0: exact f32 MFMA; 1: split-precision bf16x3 operands
+  int wino;        // Winograd route of the 3x3 / stride-1 layers: 0 off, 1 on, 2 on (same launches as 1)
+  int walk;        // probes per block of igemm_wino_kernel: 0 = the rule wino_walk_plan(), or 1 / 2 / 4 forced
+  bool split_k;    // split-K of under-filled implicit GEMMs
+};
+Route current_route();     // the only function that reads the four process-wide modes
+
 // ---- launchers (return hipError_t of the launch) ------------------------------------------
-// cache: the engine's cache of binding-fixed Winograd transforms, or null (per-launch transforms).  launch_igemm takes
+// route: the call's route (above).  cache: the engine's cache of binding-fixed Winograd transforms, or null (per-launch transforms).  launch_igemm takes
 // the transformed weights of segment s from it when bit s of fixed_b is set (the engine sets it where the segment's
 // shared B operand lives in THETA / CONST); launch_wgrad is handed a cache only when p.a lives in PRIM / CONST.  The
 // cache never changes the route of a launch, only where the Winograd kernels' transformed operand comes from.
-hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st, BindCache* cache = nullptr, unsigned fixed_b = 0);
-hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st, BindCache* cache = nullptr);
+hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st, const Route& route, BindCache* cache = nullptr, unsigned fixed_b = 0);
+// An op with p.overwrite set whose fused launch cannot be made for want of scratch (a 17th (device, stream) pair, a failed
+// allocation) has its block of Y initialised here (alpha * v, or 0) and then takes the accumulating direct kernels.
+hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st, const Route& route, BindCache* cache = nullptr);
 // a cache with the device allocator and the per-engine cap of bind_cache_policy(), or null when the policy is off
 BindCache* new_bind_cache();
 hipError_t launch_reduce(const ReduceP& p, int P, hipStream_t st);
@@ -218,8 +234,8 @@ hipError_t launch_scale_copy(float* y, const float* x, float a, long long count,
 hipError_t launch_scale_copy_range(float* y, const float* x, float a, long long off, long long len, int P, long long ld, hipStream_t st);
 // y[p][j] += a[j] * x[p][j], p < P, j < N (rows of N floats): the vector-prior term of lip_ggn_vp_diag
 hipError_t launch_add_diag(float* y, const float* x, const float* a, int P, long long N, hipStream_t st);
-// true when launch_wgrad(p, P) will run the one-block-per-tile kernel that honours WgradP::overwrite
-bool wgrad_will_overwrite(const WgradP& p, int P);
+// true when launch_wgrad(p, P, st, route) takes the one-block-per-tile kernel that honours WgradP::overwrite
+bool wgrad_will_overwrite(const WgradP& p, int P, const Route& route);
 
 // ---- square-accumulating reductions of lip_vjp_sqsum ----------------------------------------
 // y[j] += sum_{p < P} sum_{i < n} (per-(probe, example) partial product)_j^2, no (P, n, .) intermediate and no float
@@ -403,13 +419,11 @@ void set_error(const char* fmt, ...);
     hipError_t _e = (expr);                                                        \
     if (_e != hipSuccess) { set_error("%s: %s", #expr, hipGetErrorString(_e)); return LIP_ERR_HIP; } \
   } while (0)
-int precision_mode();
+// the setters of the four modes of a Route (read back by current_route() alone)
 void set_precision_mode(int m);
 void set_split_k_mode(int on);
 void set_wino_mode(int m);
-int wino_mode();
 void set_wino_walk(int w);
-int wino_walk();
 int wino_walk_plan(long long gx, int P);
 
 // ---- wave / block reductions (wave = 64 lanes on gfx950) --------------------------------

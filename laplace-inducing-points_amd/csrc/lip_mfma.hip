@@ -1650,13 +1650,12 @@ static const float* zero_page() {
 }
 
 static int cu_count() {
-  static int n = 0;
-  if (!n) {
+  static const int n = [] {
     int dev = 0;
     hipDeviceProp_t pr;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-            ? pr.multiProcessorCount : 256;
-  }
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
+               ? pr.multiProcessorCount : 256;
+  }();
   return n;
 }
 
@@ -1680,34 +1679,35 @@ static float* stream_scratch(size_t floats, hipStream_t st) {
   });
 }
 
-// The three modes with setters: -1 until the first setter call, and the environment's default (Switches) holds until then.
-// precision 0: exact f32 MFMA (default); 1: split-precision bf16x3 operands (lip_set_precision / LIP_PRECISION=bf16x3)
-static int g_precision = -1;
-int precision_mode() { return g_precision < 0 ? (switches().precision_x3 ? 1 : 0) : g_precision; }
-void set_precision_mode(int m) { g_precision = m ? 1 : 0; }
-
-// split-K of under-filled implicit GEMMs: 0 = off, 1 = on (default; LIP_NOKSPLIT: off)
-static int g_split_k = -1;
-void set_split_k_mode(int on) { g_split_k = on ? 1 : 0; }
-static bool split_k_enabled() { return g_split_k < 0 ? !switches().noksplit : g_split_k == 1; }
-
-// Winograd route of the 3x3 / stride-1 layers: 0 = off (LIP_NOWINO), 1 = on (default: every eligible launch), 2 = on
-// (LIP_WINO=f; kept for the tests that force the route; same launches as 1 since the fill rule went)
-static int g_wino = -1;
-void set_wino_mode(int m) { g_wino = (m < 0 || m > 2) ? 1 : m; }
-int wino_mode() {
+// The four modes with setters, and their one reader.  -1 until the first setter call: the environment's default (Switches)
+// holds until then.  Relaxed atomics: a setter on one thread and a call starting on another do not race, and nothing else
+// is ordered by these words: a call takes current_route() once and keeps that value (Route in lip_internal.h).
+//   precision  0: exact f32 MFMA (default); 1: split-precision bf16x3 operands (lip_set_precision / LIP_PRECISION=bf16x3)
+//   split_k    split-K of under-filled implicit GEMMs: 0 = off, 1 = on (default; LIP_NOKSPLIT: off)
+//   wino       Winograd route of the 3x3 / stride-1 layers: 0 = off (LIP_NOWINO), 1 = on (default: every eligible launch),
+//              2 = on (LIP_WINO=f; kept for the tests that force the route; same launches as 1 since the fill rule went)
+//   wino_walk  probe walk of the Winograd kernel (igemm_wino_kernel): W consecutive probes per block, W in {1, 2, 4}.
+//              0 = the rule of wino_walk_plan (default), 1 / 2 / 4 forced (capped by the probe count)
+static std::atomic<int> g_precision{-1}, g_split_k{-1}, g_wino{-1}, g_wino_walk{0};
+void set_precision_mode(int m) { g_precision.store(m ? 1 : 0, std::memory_order_relaxed); }
+void set_split_k_mode(int on) { g_split_k.store(on ? 1 : 0, std::memory_order_relaxed); }
+void set_wino_mode(int m) { g_wino.store((m < 0 || m > 2) ? 1 : m, std::memory_order_relaxed); }
+void set_wino_walk(int w) { g_wino_walk.store((w == 1 || w == 2 || w == 4) ? w : 0, std::memory_order_relaxed); }
+Route current_route() {
   const Switches& sw = switches();
-  return g_wino < 0 ? (sw.nowino ? 0 : (sw.wino_f ? 2 : 1)) : g_wino;
+  const int precision = g_precision.load(std::memory_order_relaxed), split_k = g_split_k.load(std::memory_order_relaxed);
+  const int wino = g_wino.load(std::memory_order_relaxed);
+  Route r;
+  r.precision = precision < 0 ? (sw.precision_x3 ? 1 : 0) : precision;
+  r.wino = wino < 0 ? (sw.nowino ? 0 : (sw.wino_f ? 2 : 1)) : wino;
+  r.walk = g_wino_walk.load(std::memory_order_relaxed);
+  r.split_k = split_k < 0 ? !sw.noksplit : split_k == 1;
+  return r;
 }
 
-// Probe walk of the Winograd kernel (igemm_wino_kernel): W consecutive probes per block, W in {1, 2, 4}.  0 = the rule
-// below (default), 1 / 2 / 4 forced (capped by the probe count).  The rule: the largest W that still leaves
-// WINO_WALK_K blocks per resident slot (three blocks per CU), and one probe per block for launches of at most 8 probes
-// (the few-probe and Krylov call shapes keep today's grid).
+// The automatic probe walk: the largest W that still leaves WINO_WALK_K blocks per resident slot (three blocks per CU),
+// and one probe per block for launches of at most 8 probes (the few-probe and Krylov call shapes keep today's grid).
 constexpr int WINO_WALK_K = 8;
-static int g_wino_walk = 0;
-void set_wino_walk(int w) { g_wino_walk = (w == 1 || w == 2 || w == 4) ? w : 0; }
-int wino_walk() { return g_wino_walk; }
 int wino_walk_plan(long long gx, int P) {
   if (P <= 8 || gx < 1) return 1;
   const long long need = (long long)WINO_WALK_K * 3 * cu_count();
@@ -1716,8 +1716,8 @@ int wino_walk_plan(long long gx, int P) {
   return 1;
 }
 
-static bool igemm_first_ok(const IgemmP& p, int P) {
-  if (switches().nofirst || switches().generic || precision_mode() != 0 || p.nseg != 1 || P < 8) return false;
+static bool igemm_first_ok(const IgemmP& p, int P, const Route& route) {
+  if (switches().nofirst || switches().generic || route.precision != 0 || p.nseg != 1 || P < 8) return false;
   const SegP& s = p.seg[0];
   return s.mode == 0 && s.Ktot <= 64 && (s.C & 15) != 0 && p.N == 32 && s.a_ps == 0 && !s.b_trans && !p.res && !p.red0 &&
          !p.red1 && (!p.e1 || p.xhat) && (long long)p.R * 32 < (1ll << 31);
@@ -2292,8 +2292,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-static bool wgrad_skinny_ok(const WgradP& p) {
-  return !switches().noskinny && !switches().generic && precision_mode() == 0 && p.seg_rows == 0 && p.ksplit <= 1 && p.R <= 64 && p.OHW == 1 && p.pad_h == 0 &&
+static bool wgrad_skinny_ok(const WgradP& p, const Route& route) {
+  return !switches().noskinny && !switches().generic && route.precision == 0 && p.seg_rows == 0 && p.ksplit <= 1 && p.R <= 64 && p.OHW == 1 && p.pad_h == 0 &&
          p.pad_w == 0 && p.KH == p.IH && p.KW == p.IW && (long long)p.R * p.M < (1ll << 31) && p.M >= 32 && p.N <= (1 << 20);
 }
 
@@ -2420,8 +2420,8 @@ __global__ __launch_bounds__(256) void wgrad_first_kernel(const WgradP prm, int 
   }
 }
 
-static bool wgrad_first_ok(const WgradP& p, int P) {
-  return !switches().nofirst && !switches().generic && precision_mode() == 0 && p.seg_rows == 0 && p.ksplit <= 0 && p.M <= 32 && p.N <= 32 && (p.C & 3) != 0 &&
+static bool wgrad_first_ok(const WgradP& p, int P, const Route& route) {
+  return !switches().nofirst && !switches().generic && route.precision == 0 && p.seg_rows == 0 && p.ksplit <= 0 && p.M <= 32 && p.N <= 32 && (p.C & 3) != 0 &&
          p.R >= 2048 && P >= 8 && (long long)p.R * p.N < (1ll << 31);
 }
 
@@ -2680,8 +2680,8 @@ static int wgrad_wino_splits(const WgradP& p, int P) {
   return (int)(S < 1 ? 1 : S);
 }
 
-static bool wgrad_wino_ok(const WgradP& p, int P) {
-  if (wino_mode() == 0 || precision_mode() != 0 || p.seg_rows > 0) return false;
+static bool wgrad_wino_ok(const WgradP& p, int P, const Route& route) {
+  if (route.wino == 0 || route.precision != 0 || p.seg_rows > 0) return false;
   if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad_h != 1 || p.pad_w != 1) return false;
   if ((p.C & 31) != 0 || (p.N & 31) != 0 || p.M != 9 * p.C) return false;
   const int OH = p.OHW / p.OW;
@@ -2696,7 +2696,9 @@ static bool wgrad_wino_ok(const WgradP& p, int P) {
   return true;
 }
 
-bool wgrad_will_overwrite(const WgradP& p, int P) { return wgrad_skinny_ok(p) || (wgrad_wino_ok(p, P) && wgrad_wino_splits(p, P) == 1); }
+bool wgrad_will_overwrite(const WgradP& p, int P, const Route& route) {
+  return wgrad_skinny_ok(p, route) || (wgrad_wino_ok(p, P, route) && wgrad_wino_splits(p, P) == 1);
+}
 
 // The engine's transform cache (lip_bindcache.h) on the device allocator, switched and capped by bind_cache_policy()
 BindCache* new_bind_cache() {
@@ -2743,15 +2745,14 @@ static hipError_t run_wgrad_wino(const WgradP& p, int P, hipStream_t st, BindCac
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { if (hit.buf) cache->forget(hit.buf); return e; }
   }
-  const size_t shmem = 12 * 1024 * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
+  constexpr size_t shmem = 12 * 1024 * sizeof(float);
+  static const hipError_t attr = [] {                 // once per process, by whichever thread comes first
     hipError_t e = hipFuncSetAttribute((const void*)wgrad_wino_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wgrad_wino_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)wgrad_wino_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+    return e;
+  }();
+  if (attr != hipSuccess) return attr;
   const dim3 grid((unsigned)((p.C / 32) * (p.N / 32) * S), (unsigned)P);
   with_flag((TW & 3) == 0, [&](auto rq) { with_flag(decltype(rq)::value && !wgw_nostage(), [&](auto stage) {
     constexpr bool rowq = decltype(rq)::value;
@@ -3144,7 +3145,7 @@ static unsigned long long* igemm_dbg_begin(IgemmDbg& d, hipStream_t st) {
   return d.buf;
 }
 
-static void igemm_dbg_report(IgemmDbg& d, int WM, int WN, int TM, int TN, long long blocks, const IgemmP& p, hipStream_t st) {
+static void igemm_dbg_report(IgemmDbg& d, int WM, int WN, int TM, int TN, long long blocks, const IgemmP& p, hipStream_t st, const Route& route) {
   if (d.reports >= 60) return;
   ++d.reports;
   (void)hipStreamSynchronize(st);
@@ -3157,11 +3158,11 @@ static void igemm_dbg_report(IgemmDbg& d, int WM, int WN, int TM, int TN, long l
     ++cnt;
   }
   if (cnt) fprintf(stderr, "[lip dbg] igemm<%d,%d,%d,%d> split=%d blocks=%lld (of %lld) nseg=%d N=%d: K-loop %.0f cycles, epilogue+drain %.0f cycles per block\n",
-                   WM, WN, TM, TN, precision_mode(), cnt, blocks, p.nseg, p.N, loop / cnt, epi / cnt);
+                   WM, WN, TM, TN, route.precision, cnt, blocks, p.nseg, p.N, loop / cnt, epi / cnt);
 }
 
 template <int WM, int WN, int TM, int TN>
-static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
+static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st, const Route& route) {
   using T = Tile<WM, WN, TM, TN>;
   const Switches& sw = switches();
   const long long tiles = (long long)((p.R + T::BM - 1) / T::BM) * ((p.N + T::BN - 1) / T::BN);
@@ -3172,7 +3173,7 @@ static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
     return hipGetLastError();
   }
   // ---- the decision: which of the fast kernels, with which flags ----
-  const bool split = precision_mode() == 1;      // bf16x3 operands
+  const bool split = route.precision == 1;       // bf16x3 operands
   // stride-2 data gradient on an even grid: parity-class row order, unreachable taps skipped (A/B: LIP_NOPAR)
   const int OH = p.OHW / p.OW;
   bool par = !sw.nopar && (OH % 2 == 0) && (p.OW % 2 == 0), any_s2 = false;
@@ -3194,7 +3195,7 @@ static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
   constexpr bool KS_TILE = WM == 2 && TM == 1 && TN == 1;
   const size_t plane = (size_t)P * p.R * p.N;
   long long ks = 1;                                // split-K shares
-  if (KS_TILE && plain && split_k_enabled() && !p.no_ksplit && 2 * tiles * P <= cu_count()) {
+  if (KS_TILE && plain && route.split_k && !p.no_ksplit && 2 * tiles * P <= cu_count()) {
     int kt = 0;
     for (int s = 0; s < p.nseg; ++s) kt += p.seg[s].Ktot / BK;
     ks = (4ll * cu_count()) / (tiles * P > 0 ? tiles * P : 1);
@@ -3243,7 +3244,7 @@ static hipError_t run_igemm(const IgemmP& p, int P, hipStream_t st) {
       hipLaunchKernelGGL((igemm_fast_kernel<WM, WN, TM, TN, S, PR, v>), grid, dim3(T::NT), 0, st, q);
     }
   }); }); });
-  if (sw.dbg) igemm_dbg_report(dbg, WM, WN, TM, TN, tiles * P, p, st);
+  if (sw.dbg) igemm_dbg_report(dbg, WM, WN, TM, TN, tiles * P, p, st, route);
   return hipGetLastError();
 }
 
@@ -3281,9 +3282,8 @@ static const i32x4v* wino_table(const WinoGeom& g, int H, int W, hipStream_t st)
   });
 }
 
-static bool igemm_wino_ok(const IgemmP& p, int P) {
-  const int mode = wino_mode();
-  if (mode == 0 || precision_mode() != 0 || p.no_ksplit) return false;
+static bool igemm_wino_ok(const IgemmP& p, int P, const Route& route) {
+  if (route.wino == 0 || route.precision != 0 || p.no_ksplit) return false;
   if (p.nseg < 1 || p.N < 32 || (p.N & 31) != 0) return false;
   const int OH = p.OHW / p.OW;
   if ((OH & 1) || (p.OW & 1) || OH * p.OW != p.OHW) return false;
@@ -3304,7 +3304,7 @@ static bool igemm_wino_ok(const IgemmP& p, int P) {
   return true;
 }
 
-static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st, BindCache* cache, unsigned fixed_b) {
+static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st, const Route& route, BindCache* cache, unsigned fixed_b) {
   IgemmP q = p;
   WinoX wx;
   const int OH = p.OHW / p.OW;
@@ -3350,20 +3350,18 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st, BindCac
   wx.BWs = g.BWs; wx.BHs = g.BHs; wx.NI = g.NI; wx.FC9 = 9 * g.FC; wx.nbx = g.nbx;
   wx.n_img = (int)n_img; wx.TH = g.TH; wx.TW = g.TW; wx.H = OH;
   const long long gx = (long long)g.nbx * g.nby * g.nbi * (p.N / 32);
-  const int forced = wino_walk();
-  wx.walk = forced ? (forced < P ? forced : P) : wino_walk_plan(gx, P);
+  wx.walk = route.walk ? (route.walk < P ? route.walk : P) : wino_walk_plan(gx, P);
   wx.P = P;
   wx.dnb = FastDiv((unsigned)(p.N / 32)); wx.dbxy = FastDiv((unsigned)(g.nbx * g.nby)); wx.dnbx = FastDiv((unsigned)g.nbx);
   wx.dgx = FastDiv((unsigned)gx);
   q.zeros = nullptr; q.dbg = nullptr; q.partial = nullptr;
-  const size_t shmem = (size_t)(8192 + 32 + 64 + 9 * 256) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
+  constexpr size_t shmem = (size_t)(8192 + 32 + 64 + 9 * 256) * sizeof(float);
+  static const hipError_t attr = [] {                 // once per process, by whichever thread comes first
     hipError_t e = hipFuncSetAttribute((const void*)igemm_wino_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)igemm_wino_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+    return e;
+  }();
+  if (attr != hipSuccess) return attr;
   // 16-byte epilogue accesses when every operand tensor allows them (A/B switch LIP_WINO_NOVEPI)
   auto al16 = [](const void* ptr, long long ps) { return ptr == nullptr || ((((uintptr_t)ptr) & 15) == 0 && (ps & 3) == 0); };
   const bool vepi = !switches().wino_novepi && al16(p.out, p.out_ps) && al16(p.res, p.res_ps) && al16(p.xhat, 0) && al16(p.dphi, 0) && al16(p.xhat2, 0);
@@ -3374,11 +3372,11 @@ static hipError_t run_igemm_wino(const IgemmP& p, int P, hipStream_t st, BindCac
   return hipGetLastError();
 }
 
-hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st, BindCache* cache, unsigned fixed_b) {
-  if (igemm_first_ok(p, P)) return run_igemm_first(p, P, st);
-  if (igemm_wino_ok(p, P)) {
+hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st, const Route& route, BindCache* cache, unsigned fixed_b) {
+  if (igemm_first_ok(p, P, route)) return run_igemm_first(p, P, st);
+  if (igemm_wino_ok(p, P, route)) {
     // (no scratch for the transformed weights — a 17th stream, or the allocation failed: the direct kernels below)
-    const hipError_t e = run_igemm_wino(p, P, st, cache, fixed_b);
+    const hipError_t e = run_igemm_wino(p, P, st, route, cache, fixed_b);
     if (e != hipErrorOutOfMemory) return e;
     (void)hipGetLastError();
   }
@@ -3387,20 +3385,20 @@ hipError_t launch_igemm(const IgemmP& p, int P, hipStream_t st, BindCache* cache
   // of the CIFAR net run 25 blocks of 144 K-tiles otherwise (measured 177 us per launch).  A/B switch LIP_NOSMALLP.
   const long long blocks128 = (long long)((p.R + 127) / 128) * ((p.N + (p.N > 64 ? 127 : (p.N > 32 ? 63 : 31))) / (p.N > 64 ? 128 : (p.N > 32 ? 64 : 32))) * P;
   if (!switches().nosmallp && p.R > 64 && blocks128 < (long long)switches().smallp_factor * cu_count()) {
-    if (p.N > 32) return run_igemm<2, 2, 1, 1>(p, P, st);
-    return run_igemm<2, 1, 1, 1>(p, P, st);
+    if (p.N > 32) return run_igemm<2, 2, 1, 1>(p, P, st, route);
+    return run_igemm<2, 1, 1, 1>(p, P, st, route);
   }
   // experiment switches (A/B only): LIP_TILE=2 one-wave blocks (32 x 32 / 32 x 64 per block, no cross-wave barrier),
   // LIP_TILE=3 one wave with two row tiles (64 x 32), LIP_TILE=4 two-wave 64-row blocks
   const int tile = switches().tile;
-  if (tile == 2 && p.N <= 64) return p.N > 32 ? run_igemm<1, 1, 1, 2>(p, P, st) : run_igemm<1, 1, 1, 1>(p, P, st);
-  if (tile == 3 && p.N <= 32) return run_igemm<1, 1, 2, 1>(p, P, st);
-  if (tile == 4 && p.N <= 32) return run_igemm<2, 1, 1, 1>(p, P, st);
+  if (tile == 2 && p.N <= 64) return p.N > 32 ? run_igemm<1, 1, 1, 2>(p, P, st, route) : run_igemm<1, 1, 1, 1>(p, P, st, route);
+  if (tile == 3 && p.N <= 32) return run_igemm<1, 1, 2, 1>(p, P, st, route);
+  if (tile == 4 && p.N <= 32) return run_igemm<2, 1, 1, 1>(p, P, st, route);
   const bool small_m = p.R <= 64;
   const bool big_m = p.R >= 4096 && tile == 1;    // LIP_TILE=1: 256-row tiles (A/B: slower on every shape, r1 and r2)
-  if (p.N > 64) return small_m ? run_igemm<2, 2, 1, 2>(p, P, st) : run_igemm<2, 2, 2, 2>(p, P, st);
-  if (p.N > 32) return small_m ? run_igemm<2, 2, 1, 1>(p, P, st) : (big_m ? run_igemm<4, 1, 2, 2>(p, P, st) : run_igemm<4, 1, 1, 2>(p, P, st));
-  return small_m ? run_igemm<2, 1, 1, 1>(p, P, st) : (big_m ? run_igemm<4, 1, 2, 1>(p, P, st) : run_igemm<4, 1, 1, 1>(p, P, st));
+  if (p.N > 64) return small_m ? run_igemm<2, 2, 1, 2>(p, P, st, route) : run_igemm<2, 2, 2, 2>(p, P, st, route);
+  if (p.N > 32) return small_m ? run_igemm<2, 2, 1, 1>(p, P, st, route) : (big_m ? run_igemm<4, 1, 2, 2>(p, P, st, route) : run_igemm<4, 1, 1, 2>(p, P, st, route));
+  return small_m ? run_igemm<2, 1, 1, 1>(p, P, st, route) : (big_m ? run_igemm<4, 1, 2, 1>(p, P, st, route) : run_igemm<4, 1, 1, 1>(p, P, st, route));
 }
 
 
@@ -3457,7 +3455,7 @@ static long long wgrad_tile_count(int M, int N) {
 }
 
 template <int WM, int WN, int TM, int TN>
-static hipError_t run_wgrad(Tile<WM, WN, TM, TN>, const WgradP& p0, int P, hipStream_t st) {
+static hipError_t run_wgrad(Tile<WM, WN, TM, TN>, const WgradP& p0, int P, hipStream_t st, const Route& route) {
   using T = Tile<WM, WN, TM, TN>;
   const long long tiles = (long long)((p0.M + T::BM - 1) / T::BM) * ((p0.N + T::BN - 1) / T::BN);
   WgradP p = p0;
@@ -3470,7 +3468,7 @@ static hipError_t run_wgrad(Tile<WM, WN, TM, TN>, const WgradP& p0, int P, hipSt
     // cotangent rows as float4 (N % 4 == 0, 16-byte aligned slot): in split precision (bf16x3 operands) on every tile
     // width whose loader has the form, else on the 64+ column tiles (A/B switch LIP_NOBV4)
     const bool v4 = (p.N & 3) == 0 && (p.g_ps & 3) == 0 && (((uintptr_t)p.g) & 15) == 0;
-    const bool x3 = T::AQ == 2 && precision_mode() == 1 && v4;
+    const bool x3 = T::AQ == 2 && route.precision == 1 && v4;
     with_flag(x3, [&](auto s) { with_flag(x3 || (!switches().nobv4 && T::BN >= 64 && v4), [&](auto b) {
       constexpr bool S = decltype(s)::value;
       if constexpr (!S || (b && T::AQ == 2)) {
@@ -3490,7 +3488,7 @@ static hipError_t run_wgrad(Tile<WM, WN, TM, TN>, const WgradP& p0, int P, hipSt
 // M = KH*KW*C is a multiple of 96 but not of 128 (288, 576).  The row reduction is split (float atomics) until
 // the launch has ~6 blocks per CU.
 template <int WM, int WN, int TM, int TN>
-static hipError_t run_wgrad_pb(const WgradP& p, int P, hipStream_t st) {
+static hipError_t run_wgrad_pb(const WgradP& p, int P, hipStream_t st, const Route& route) {
   using T = Tile<WM, WN, TM, TN>;
   const long long tiles = (long long)((p.M + T::BM - 1) / T::BM) * (((long long)P * p.N + T::BN - 1) / T::BN);
   WgradP q = p;
@@ -3507,7 +3505,7 @@ static hipError_t run_wgrad_pb(const WgradP& p, int P, hipStream_t st) {
   }
   dim3 grid((unsigned)tiles, 1, (unsigned)q.ksplit);
   constexpr bool X3_TILE = T::NT % (T::BM / 4) == 0;        // (the split-precision loader needs one m-quad per thread)
-  with_flag(X3_TILE && precision_mode() == 1, [&](auto s) {
+  with_flag(X3_TILE && route.precision == 1, [&](auto s) {
     if constexpr (!s || X3_TILE) {
       LIP_ROUTE("wgrad_pb<%d,%d,%d,%d>%s", WM, WN, TM, TN, s ? "/x3" : "");
       hipLaunchKernelGGL((wgrad_fast_kernel<WM, WN, TM, TN, true, true, s>), grid, dim3(T::NT), 0, st, q);
@@ -3516,19 +3514,29 @@ static hipError_t run_wgrad_pb(const WgradP& p, int P, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st, BindCache* cache) {
-  if (wgrad_first_ok(p, P)) return run_wgrad_first(p, P, st);
-  if (wgrad_skinny_ok(p)) {
-    if (p.R <= 16) return run_wgrad_skinny<2, 8>(p, P, st);
-    if (p.R <= 52) return run_wgrad_skinny<2, 26>(p, P, st);
-    return run_wgrad_skinny<2, 32>(p, P, st);
+hipError_t launch_wgrad(const WgradP& p0, int P, hipStream_t st, const Route& route, BindCache* cache) {
+  if (wgrad_first_ok(p0, P, route)) return run_wgrad_first(p0, P, st);
+  if (wgrad_skinny_ok(p0, route)) {
+    if (p0.R <= 16) return run_wgrad_skinny<2, 8>(p0, P, st);
+    if (p0.R <= 52) return run_wgrad_skinny<2, 26>(p0, P, st);
+    return run_wgrad_skinny<2, 32>(p0, P, st);
   }
-  if (wgrad_wino_ok(p, P)) {
+  WgradP p = p0;
+  if (wgrad_wino_ok(p, P, route)) {
     const hipError_t e = run_wgrad_wino(p, P, st, cache);
-    if (e != hipErrorOutOfMemory) return e;             // (no scratch for the transformed activations: the direct kernels)
+    if (e != hipErrorOutOfMemory) return e;
     (void)hipGetLastError();
+    // No scratch for the transformed activations (a 17th (device, stream) pair, or the allocation failed): the direct
+    // kernels below.  They accumulate, and the caller that planned the fused output has not initialised this op's
+    // block: y = alpha * v (or 0) here, as its initialisation pass would have written it.
+    if (p.overwrite) {
+      if (p.v && p.v_ps != p.y_ps) return hipErrorInvalidValue;
+      const hipError_t ei = launch_scale_copy_range(p.y, p.alpha != 0.f ? p.v : nullptr, p.alpha, 0, (long long)p.M * p.N, P, p.y_ps, st);
+      if (ei != hipSuccess) return ei;
+      p.overwrite = 0;
+    }
   }
-  if (p.overwrite) return hipErrorInvalidValue;       // the engine asks for it only where wgrad_will_overwrite() holds
+  if (p.overwrite) return hipErrorInvalidValue;       // set where no fused route was ever eligible: not what wgrad_will_overwrite() said
   const Switches& sw = switches();
   const bool pb_ok = !sw.nopb && !sw.generic && P > 1 && p.N <= 64 && (p.N & 3) == 0 && p.M >= 96 && (p.g_ps & 3) == 0 && (((uintptr_t)p.g) & 15) == 0 && (p.C & 3) == 0 && (((uintptr_t)p.a) & 15) == 0 &&
                      (long long)(P - 1) * p.g_ps + (long long)p.R * p.N < (1ll << 32);
@@ -3540,13 +3548,13 @@ hipError_t launch_wgrad(const WgradP& p, int P, hipStream_t st, BindCache* cache
     // probe's channels) — the three-wave form <3,1,1,4> (208 registers: two blocks of three waves per CU) put 2-2-1-1
     // waves on the four SIMDs; it stays for the split-precision mode, whose row-pair loader needs one m-quad per thread
     if (p.M % 96 == 0 && p.M % 128 != 0)
-      return (precision_mode() == 1 || sw.wgrad3) ? run_wgrad_pb<3, 1, 1, 4>(p, P, st) : run_wgrad_pb<1, 4, 3, 1>(p, P, st);
-    return run_wgrad_pb<2, 2, 2, 2>(p, P, st);
+      return (route.precision == 1 || sw.wgrad3) ? run_wgrad_pb<3, 1, 1, 4>(p, P, st, route) : run_wgrad_pb<1, 4, 3, 1>(p, P, st, route);
+    return run_wgrad_pb<2, 2, 2, 2>(p, P, st, route);
   }
   // (64-row per-probe tiles for M = 288 were measured slower than 128-row ones: 54.6 vs 52.4 ms per step — removed;
   //  a 96 x 256 probe-batched tile <1,4,3,2> — the transposed im2col gather shared by eight probes instead of four — ran
   //  the M = 288 / 576 launches at 105 instead of 113 TFLOP/s: removed)
-  return with_wgrad_tile(p.M, p.N, [&](auto tile, int) { return run_wgrad(tile, p, P, st); });
+  return with_wgrad_tile(p.M, p.N, [&](auto tile, int) { return run_wgrad(tile, p, P, st, route); });
 }
 
 
